@@ -2,6 +2,11 @@
 """bench.py -- LU GFLOP/s (2n^3/3) of the MI355X-native recursive LU, the metric of BASELINE.json.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size SIZE] [--dtype f64|f32] [--nopivot] [--blocksize B]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line; everything else it can measure or check (the extra
+objects below, the residual check and, with N > 1, the same n on one GPU) runs only with --full, and its keys are null or empty
+otherwise.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 A "step" is one factorization  lu!(A, ipiv)  of a dense uniform [0,1) n x n matrix that is already resident in HBM in
 the reference's column-major layout; the result (packed L\\U, ipiv) is left in HBM.  lu! works in place, so the input is
@@ -54,7 +59,35 @@ def parse_args():
     ap.add_argument("--no-extras", action="store_true", help="skip the in-schedule timer pass and the block-size sweep (profiling runs)")
     ap.add_argument("--cpu-n", type=int, default=6144, help="size of the bounded CPU-baseline sample (~10-30 s of CPU work)")
     ap.add_argument("--block", type=int, default=512, help="block-column width of the multi-GPU layout")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements and checks (roofline, laswp, block-size sweep, variants, host entry, "
+                         "residual check, CPU baseline, same n on one GPU); the --no-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the factors (a fixed sample), ipiv and info of the last timed step as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 21   # factor entries kept by --dump-outputs: 2 x 16 MiB (values + indices) in float64
+DUMP_SEED = 20240521
+
+
+def dump_outputs(out_dir, A, ipiv, info, n):
+    """What the caller of rflu_getrf_*_dev receives after the last timed step: the packed factors L\\U (n x n, column-major in A's
+    memory), ipiv (1-based) and info.  The factors are a fixed sample: the column-major linear indices i + j*n drawn from DUMP_SEED
+    (every entry when n*n <= DUMP_SAMPLE), saved beside the values, so that two builds can be compared entry for entry."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    if n * n <= DUMP_SAMPLE:
+        idx = np.arange(n * n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n * n, size=DUMP_SAMPLE, dtype=np.int64))
+    vals = A.reshape(-1)[torch.from_numpy(idx).to(A.device)].cpu().numpy()   # A's memory order is column-major
+    np.save(os.path.join(out_dir, "factors_sample.npy"), vals)               # float64 or float32, as computed
+    np.save(os.path.join(out_dir, "factors_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "ipiv.npy"), ipiv.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "info.npy"), np.array([info], dtype=np.float64))
 
 
 def cpu_baseline(cpu_n: int):
@@ -218,6 +251,8 @@ def main():
             torch.cuda.synchronize(dev)
 
     single = world == 1 and not force_dist
+    if args.dump_outputs and not single:
+        raise SystemExit("bench.py --dump-outputs: supported for the single-GPU path (--gpus 1) only")
     if single:
         A = torch.empty((n, n), dtype=tdt, device=dev)  # memory = column-major n x n (lda = n)
         ipiv = torch.empty(n, dtype=torch.int64, device=dev)
@@ -297,11 +332,13 @@ def main():
     total_s = float(total.item())
     ms_per_step = 1e3 * total_s / max(args.steps, 1)
     gflops = flops * args.steps / total_s / 1e9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, A, ipiv, int(info.value), n)
 
     # ---- N > 1: the SAME n on ONE GPU in the same run (rank 0, device 0), so that the line carries the ratio the north star's
     # scaling target is defined on (">= 6x at 8 GPUs over 1 GPU on N=65536"): strong scaling, same matrix, same seed ----
     one_gpu_same_n = None
-    if not single and world > 1:
+    if args.full and not single and world > 1:
         if rank == 0 and not args.no_one_gpu:
             A1 = torch.empty((n, n), dtype=tdt, device=dev)
             ip1 = torch.empty(n, dtype=torch.int64, device=dev)
@@ -329,7 +366,7 @@ def main():
     # ---- roofline of the dominant kernel: one extra profiled factorization (HIP events on the launch stream) ----
     roof = None
     kern = {}
-    if True:
+    if args.full:
         regenerate()
         barrier()
         # mode 3: the single-stream blocked schedule with an event pair around every launch and no host wait in between (mode 1 waits
@@ -388,7 +425,7 @@ def main():
     # what the GEMM achieves next to the critical-path stream, and the HBM rate of the row interchanges (laswp)
     laswp = None
     sweep = None
-    if single and not args.no_extras:
+    if args.full and single and not args.no_extras:
         regenerate()
         barrier()
         h.profile_enable(2)
@@ -551,7 +588,7 @@ def main():
     # (src/butterflylu.jl:45-55): ONE pass A <- U'AV (HBM-bound), then lu!(A, Val(false)) -- no pivot search, hence no per-column
     # latency chain -- and x = V ((U'AV) \ (U'b)) with the outer products as O(n) butterflies
     variants = None
-    if single and not args.no_extras and pivot and args.blocksize == 0 and n % 4 == 0 and n >= 1024:
+    if args.full and single and not args.no_extras and pivot and args.blocksize == 0 and n % 4 == 0 and n >= 1024:
         from recursivefactorization.jl_amd import butterfly as BF
 
         esz = 8 if sfx == "f64" else 4
@@ -669,7 +706,7 @@ def main():
     # of `value` (inputs resident in HBM); quoted so that the cost of the two PCIe crossings is on record.  The way back overlaps the
     # factorization (driver.cpp: getrf_host); the way in cannot (the first update touches every column).
     host_entry = None
-    if single and not args.no_extras and n >= 1024 and args.blocksize == 0:
+    if args.full and single and not args.no_extras and n >= 1024 and args.blocksize == 0:
         regenerate(); barrier()
         Ah = np.ascontiguousarray(A.cpu().numpy())   # the same n*n values in the same order: the library reads them column-major
         if True:
@@ -696,7 +733,7 @@ def main():
 
     # ---- checks on the last factorization: residual on device (torch as an independent checker) ----
     check = {}
-    if not args.no_check and single and n <= 32768:
+    if args.full and not args.no_check and single and n <= 32768:
         regenerate()
         barrier()
         A0 = A.clone()  # column-major memory; A.T is the logical matrix in torch's row-major view
@@ -725,7 +762,7 @@ def main():
         check["info"] = int(info.value)
         del L, U, R, PA
 
-    if not args.no_check and not single:
+    if args.full and not args.no_check and not single:
         if job is not None:
             check["residual_matvec"] = job.matvec_residual()
             check["info"] = int(job.info)
@@ -739,7 +776,7 @@ def main():
                 check["info"] = int(mg_info[0])
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and single:
+    if args.full and rank == 0 and not args.no_cpu_baseline and single:
         cpu, cpu_ipiv = cpu_baseline(args.cpu_n)
         if pivot and sfx == "f64":
             # ipiv parity on the CPU sample size: same generator, same seed -> must be bit-exact

@@ -5,7 +5,7 @@ set -e
 TAG=${1:-r03}
 SIZE=${2:-16384}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-CMD="python bench.py --size $SIZE --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras"
+CMD="python bench.py --full --size $SIZE --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 rocprofv3 --kernel-trace --stats -d $OUT/trace -- $CMD > $OUT/bench_trace.json 2>$OUT/trace.err
@@ -17,7 +17,7 @@ python scripts/rocpd_queues.py $DB 3 >> $OUT/kernel_stats.txt
 # counter collection runs ONE kernel at a time across all queues: device-side gates cannot make progress, so the counter passes ask
 # for the schedule whose cross-stream edges are hipEvents (same kernels, same shapes for the bulk GEMM)
 export RFLU_SCHEDULE_PMC=events
-CMD1="env RFLU_SCHEDULE=events python bench.py --size $SIZE --steps 1 --warmup 0 --no-cpu-baseline --no-check --no-extras"
+CMD1="env RFLU_SCHEDULE=events python bench.py --full --size $SIZE --steps 1 --warmup 0 --no-cpu-baseline --no-check --no-extras"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $OUT/pmc_fetch -- $CMD1 > /dev/null 2>$OUT/pmc_fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $OUT/pmc_write -- $CMD1 > /dev/null 2>$OUT/pmc_write.err
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVES -f csv -d $OUT/pmc_mfma -- $CMD1 > /dev/null 2>$OUT/pmc_mfma.err

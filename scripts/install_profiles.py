@@ -13,7 +13,7 @@ P = os.path.join(ROOT, "profiles")
 rd = lambda *p: open(os.path.join(G, *p)).read()
 
 def stats_header(n):
-    return (f"# round {int(rnd[1:])}, shipped build (sources sha1 {sha}, profiles/gemm_traffic.json) -- rocprofv3 --kernel-trace --stats -- python bench.py --size {n} --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras\n"
+    return (f"# round {int(rnd[1:])}, shipped build (sources sha1 {sha}, profiles/gemm_traffic.json) -- rocprofv3 --kernel-trace --stats -- python bench.py --full --size {n} --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras\n"
             "# (3 timed factorizations incl. warm-up in the shipped schedule + 1 profiled single-stream pass; Float64, one MI355X; scripts/collect_profiles.sh)\n"
             "# first table: all kernels of the run (scripts/rocpd_summary.py); second: one timed factorization split by HIP queue\n"
             "# (scripts/rocpd_queues.py): the caller's stream = critical path; the 224-CU stream (updates of the lookahead part, then -- from the\n"
@@ -23,7 +23,7 @@ def stats_header(n):
 
 def pmc_header(n):
     return (f"# round {int(rnd[1:])}, shipped build (sources sha1 {sha}) -- PMC passes, each its own run with --kernel-trace only (scripts/collect_profiles.sh):\n"
-            f"#   rocprofv3 --kernel-trace --pmc <COUNTERS> -f csv -- python bench.py --size {n} --steps 1 --warmup 0 --no-cpu-baseline --no-check --no-extras\n"
+            f"#   rocprofv3 --kernel-trace --pmc <COUNTERS> -f csv -- python bench.py --full --size {n} --steps 1 --warmup 0 --no-cpu-baseline --no-check --no-extras\n"
             "# Counter collection serialises kernels across queues, so these runs use the block-column lookahead schedule with event edges only\n"
             "# (device-side gates cannot make progress when one kernel runs at a time) -- same kernels, same shapes for the bulk GEMM.  Two\n"
             "# factorizations per run (timed schedule + profiled single-stream pass).  FETCH_SIZE / WRITE_SIZE are KiB; on gfx950 FETCH_SIZE reports\n"
@@ -86,11 +86,11 @@ for f in sorted(os.listdir(os.path.join(G, rnd))):
                      f"{d['config']['n']:6d}  {d['dtype']}   {str(d['config'].get('pivot', True)):5s} {d['ms_per_step']:10.3f} {d['value'] / 1e3:9.2f}  {d['frac_of_mfma_peak']:.4f}   {res}"))
 rows.sort()
 dflt = json.loads(rd(rnd, "bench_default.json"))
-out = [f"# round {int(rnd[1:])}, shipped build (sources sha1 {sha}): python bench.py --size N [--dtype f32] [--nopivot] --steps 5|3 --warmup 1 --no-cpu-baseline --no-extras",
+out = [f"# round {int(rnd[1:])}, shipped build (sources sha1 {sha}): python bench.py --full --size N [--dtype f32] [--nopivot] --steps 5|3 --warmup 1 --no-cpu-baseline --no-extras",
        "# one MI355X box, one gpurun call (boxes of the pool differ by 3-5 % on the GEMM-bound sizes); the JSON lines are under gpurun_out/" + rnd + "/ (scratch)",
        "# n      dtype pivot   ms/step   TFLOP/s  frac of dense MFMA peak (78.6 f64 / 157.3 f32)   ||PA-LU||/||A||"]
 out += [r[3] for r in rows]
-out += ["", "# default bench line of the same call (python bench.py --steps 8 --warmup 2), extra keys:"]
+out += ["", "# default bench line of the same call (python bench.py --full --steps 8 --warmup 2), extra keys:"]
 rf = dflt["roofline"]
 out.append("# roofline: " + json.dumps({k: rf.get(k) for k in ("achieved", "frac", "achieved_profiled", "frac_profiled", "achieved_in_schedule", "frac_in_schedule", "avg_launch_ms", "traffic") if k in rf}))
 out.append("# host_entry: " + json.dumps(dflt.get("host_entry")))

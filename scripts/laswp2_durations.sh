@@ -3,7 +3,7 @@
 # two kernels behind them on the critical-path queue
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/lw2_$1; rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace -d $OUT/trace -- python bench.py --size 16384 --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras > $OUT/bench.json 2>$OUT/trace.err
+rocprofv3 --kernel-trace -d $OUT/trace -- python bench.py --full --size 16384 --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras > $OUT/bench.json 2>$OUT/trace.err
 DB=$(find $OUT/trace -name "*.db" | head -1)
 python - "$DB" <<'PY'
 import sqlite3, sys, statistics

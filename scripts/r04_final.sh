@@ -5,7 +5,7 @@ TAG=${1:-r04i}
 cd "$(dirname "$0")/.."
 O=gpurun_out/r04; mkdir -p $O
 rm -f $O/bench_n*.json
-B="python bench.py --warmup 1 --no-cpu-baseline --no-extras"
+B="python bench.py --full --warmup 1 --no-cpu-baseline --no-extras"
 $B --size 4096 --steps 5 > $O/bench_n4096.json 2>/dev/null
 $B --size 8192 --steps 5 > $O/bench_n8192.json 2>/dev/null
 $B --size 12288 --steps 5 > $O/bench_n12288.json 2>/dev/null
@@ -15,7 +15,7 @@ $B --size 16384 --steps 5 --nopivot > $O/bench_n16384_nopivot.json 2>/dev/null
 $B --size 32768 --steps 3 > $O/bench_n32768.json 2>/dev/null
 $B --size 65536 --steps 3 --no-check > $O/bench_n65536.json 2>/dev/null
 $B --size 65536 --steps 3 --no-check --dtype f32 > $O/bench_n65536_f32.json 2>/dev/null
-python bench.py --steps 8 --warmup 2 > $O/bench_default.json 2>$O/bench_default.err
+python bench.py --full --steps 8 --warmup 2 > $O/bench_default.json 2>$O/bench_default.err
 python scripts/microbench_gemm_sustained.py > $O/gemm_sustained.txt 2>&1
 python scripts/microbench_gemm_sustained.py 15872 512 f32 > $O/gemm_sustained_f32.txt 2>&1
 python scripts/microbench_gemm_k.py > $O/gemm_k.txt 2>&1

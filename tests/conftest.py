@@ -10,6 +10,32 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run by the driver with -m gpu on the GPU box)")
+    config.addinivalue_line("markers", "gpu_exclusive: times the GPU, so no other GPU test may run next to it")
+
+
+# ---- a test that times the GPU reads the load of other GPU tests as its own failure (another process's kernels look like a
+# shared hardware pipe to tests/test_gpu_queues.py).  When the suite runs in several processes (pytest-xdist), every GPU test holds
+# a shared lock for its duration and a gpu_exclusive test an exclusive one; while an exclusive test waits, the turnstile keeps new
+# shared holders out.  In a single process the locks are never contended.
+@pytest.fixture(autouse=True)
+def _gpu_lock(request, tmp_path_factory):
+    if request.node.get_closest_marker("gpu") is None:
+        yield
+        return
+    import fcntl
+
+    root = tmp_path_factory.getbasetemp().parent   # shared by the xdist workers of one run
+    exclusive = request.node.get_closest_marker("gpu_exclusive") is not None
+    with open(root / "gpu_turnstile.lock", "a") as turnstile, open(root / "gpu.lock", "a") as lock:
+        fcntl.flock(turnstile, fcntl.LOCK_EX)
+        try:
+            fcntl.flock(lock, fcntl.LOCK_EX if exclusive else fcntl.LOCK_SH)
+        finally:
+            fcntl.flock(turnstile, fcntl.LOCK_UN)
+        try:
+            yield
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
 
 
 def _has_gpu() -> bool:

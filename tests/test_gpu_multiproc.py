@@ -34,7 +34,7 @@ def test_bench_contract_two_ranks_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RFLU_BENCH_ONE_GPU="1", RFLU_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--size", "3072",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = out.stdout.strip().splitlines()[-1]
@@ -55,7 +55,7 @@ def test_bench_contract_c_entry_two_ranks_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RFLU_BENCH_ONE_GPU="1", RFLU_BENCH_BACKEND="gloo", RFLU_BENCH_MGPU="c")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--size", "3072",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -5,7 +5,7 @@ has to run as fast as with a clean history (a shared pipe costs +65 % at n = 409
 import os, re, subprocess, sys
 import pytest
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.gpu_exclusive]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SCRIPT = r"""
