@@ -22,6 +22,7 @@
 
 #include "rflu_internal.hpp"
 #include "engine.hpp"
+#include "schedule_plan.hpp"
 #include <atomic>
 #include <chrono>
 #include <thread>
@@ -370,12 +371,16 @@ static int gemm_public(Handle* h, int64_t M, int64_t N, int64_t K, const T* A, i
     return RFLU_OK;
 }
 
-// measured on MI355X (bench.py --blocksize sweep): the knee moves right with the matrix size
-static int64_t default_blocksize(int64_t mn)
+// the inputs of plan_schedule (schedule_plan.hpp) as the handle has them now
+static SchedIn sched_in(const Handle* h, int64_t m, int64_t n, size_t esize, int pivot, int64_t blocksize, int entry, bool aligned16, int64_t ld)
 {
-    // (512 from 11265 columns on: where the update engine, which wants 512-wide block columns, starts to win -- N=11264 38.4 vs 38.6 ms at 256
-    // through the streams, N=12288 41.5 vs 43.5, N=10240 33.8 vs 32.9: round 6)
-    return mn < 1024 ? -1 : (mn <= 11264 ? 256 : (mn <= 16384 ? 512 : (mn <= 24576 ? 1024 : 2048)));
+    SchedIn in;
+    in.m = m; in.n = n; in.esize = esize; in.pivot = pivot; in.blocksize = blocksize; in.entry = entry;
+    in.tune = h->tune;
+    in.num_cus = h->num_cus; in.prof = h->prof || h->prof_one_stream; in.mask_failed = h->mask_failed; in.progress = (bool)h->progress;
+    in.panel_local = h->panel_local; in.coop_launch = h->coop_launch;
+    in.aligned16 = aligned16; in.ld = ld;
+    return in;
 }
 
 template <typename T>
@@ -866,18 +871,6 @@ static int factor_lookahead(Fact<T>& f, int64_t W, int64_t b_end, hipStream_t* U
     return RFLU_OK;
 }
 
-// The persistent update engine (engine.hip) can serve a factorization when the column blocks start on tile boundaries, the
-// workspace allows 16-byte accesses and nothing else wants to follow the schedule from the host (the host entry's progress hook).
-template <typename T>
-static int engine_usable(const Handle* h, const Fact<T>& f, int64_t W)
-{
-    constexpr int64_t VW = 16 / (int64_t)sizeof(T);
-    return W % 128 == 0 && f.roff == 0 && reinterpret_cast<uintptr_t>(f.R) % 16 == 0 && f.ld % VW == 0 &&
-           f.m < (int64_t)1 << 30 && f.n < (int64_t)1 << 30 && (f.n + W - 1) / W <= ENG_MAX_CB && !h->progress && !h->mask_failed &&
-           (!h->tune.schedule_events || h->tune.engine_replay) && h->num_cus == 256 &&
-           (f.m >= f.n || f.m % W == 0);   // (a fat matrix whose last panel ends inside a column block: the columns right of it in that block)
-}
-
 // the engine's state block (device) and the pinned host image of its initial value: both or neither (a half-made pair would
 // have the next call write its image through a null pointer); freed by rflu_destroy
 static int ensure_engine_state(Handle* h)
@@ -923,14 +916,17 @@ static int ensure_engine_state(Handle* h)
 // per-column-block counters instead of being enqueued on S and U; P is unchanged except that its lookahead launch waits for the
 // engine's progress word of the lookahead strip's column block instead of a side-stream gate.  From block column eng_end on the
 // streams take over again (short panels: the XCD-local leaves need CUs the resident engine does not give back).
+// The block width, eng_end and the engine's geometry come from the plan (schedule_plan.hpp).
 template <typename T>
-static int factor_leafwise(Fact<T>& f, int64_t W, int64_t b_begin, hipStream_t U_before, int64_t eng_end = 0)
+static int factor_leafwise(Fact<T>& f, const SchedPlan& plan, int64_t b_begin, hipStream_t U_before)
 {
     Handle* h = f.h;
     const int64_t m = f.m, n = f.n, ld = f.ld, mn = std::min(m, n);
+    const int64_t W = plan.Wb, eng_end = plan.eng_end;
     T* R = f.R;
     const hipStream_t userS = h->stream;
-    struct Restore { Handle* h; hipStream_t s; ~Restore() { h->stream = s; } } restore{h, userS};
+    // (the cap on the XCD-local leaves is the engine's: gone with this schedule, however it ends)
+    struct Restore { Handle* h; hipStream_t s; ~Restore() { h->stream = s; h->local_rows_cap = -1; } } restore{h, userS};
     hipStream_t P = userS;
     const int64_t nblk = (mn + W - 1) / W, nleaf = (mn + NB - 1) / NB;
     // events as in factor_lookahead: block b -> 4b+2 (evU1), 4b+3 (evUend); stream moves of this function from EX on
@@ -1017,21 +1013,18 @@ static int factor_leafwise(Fact<T>& f, int64_t W, int64_t b_begin, hipStream_t U
     EngGeo geo{};
     EngState* est = nullptr;
     hipStream_t E = nullptr;
-    int64_t eng_retire_leaf = -1;   // engine mode: the leaf in front of which the engine's workgroups on the chain's XCD are gone (-1: they stay)
-    struct RestoreLocal { Handle* h; int64_t rows; bool on; ~RestoreLocal() { if (on) h->tune.panel_local_rows = rows; } } restore_local{h, h->tune.panel_local_rows, false};
+    const int64_t eng_retire_leaf = plan.eng_retire_leaf;   // engine mode: the leaf in front of which the engine's workgroups on the chain's XCD are gone
     if (eng_end > 0) {
         if (b_begin != 0) { set_error("factor_leafwise: the engine starts at block column 0"); return RFLU_ERR_ARG; }
-        eng_end = std::min(eng_end, nblk);
         RFLU_TRY(get_ustream(h, 32, &E));
         RFLU_TRY(ensure_engine_state(h));
         est = static_cast<EngState*>(h->eng_state);
         EngState* img = static_cast<EngState*>(h->eng_host);
         geo.m = (int)m; geo.n = (int)n; geo.mn = (int)mn; geo.W = (int)W; geo.nbp = (int)eng_end;
-        geo.Wc = (h->tune.engine_wc >= 128 && h->tune.engine_wc % 128 == 0 && W % h->tune.engine_wc == 0) ? h->tune.engine_wc : (int)W;
+        geo.Wc = plan.eng_wc;
         geo.ncb = (int)((n + geo.Wc - 1) / geo.Wc);
         geo.pivot = f.pivot;
-        geo.ahead = std::max(1, std::min(h->tune.engine_ahead, 4));
-        if (geo.ncb > ENG_MAX_CB) { geo.Wc = (int)W; geo.ncb = (int)((n + W - 1) / W); }
+        geo.ahead = plan.eng_ahead;
         const size_t bytes = offsetof(EngState, cb) + (size_t)geo.ncb * sizeof(EngCB);
         const size_t skip = offsetof(EngState, remaining);   // (the arrival word in front belongs to the feeding stream: getrf_host_engine)
         memset(img, 0, bytes);
@@ -1073,23 +1066,12 @@ static int factor_leafwise(Fact<T>& f, int64_t W, int64_t b_begin, hipStream_t U
         // host entry: whole-block-column operations that lag the chain by this many block columns go first (engine.hip), so that
         // block rows become final -- and leave -- while the factorization runs
         a.host_lag = h->eng_host_mode ? h->tune.engine_host_lag : 0;
-        // Engine to the end: from the first panel of at most `local_rows` rows on the chain wants its XCD-local leaves back (worth 1.2 ms at
-        // N=16384), and the engine has little left to do: its workgroups on the chain's XCD retire two leaves earlier, the first such
-        // leaf waits until they are gone (RFLU_ENGINE_RETIRE=0: they stay, every leaf any-placement)
-        eng_retire_leaf = -1;
+        // Engine to the end: its workgroups on the chain's XCD retire two leaves in front of the plan's retire leaf, which waits until they
+        // are gone and takes the XCD-local leaves back from there on
         a.retire_xcc = -1; a.retire_leaf = 0;
-        {
-            // (RFLU_ENGINE_RETIRE = the panel height from which on: at most what the XCD-local leaf is used for anyway)
-            const int64_t local_max = restore_local.rows >= 0 ? restore_local.rows : (sizeof(T) == 4 ? 8192 : 4096);
-            // (default -1: 4096 rows, 2048 from 16384 rows on, where the end is bound by the engine's throughput and its workgroups are worth
-            // more than the faster leaves for longer: N=16384 75.2-76.5 ms at 4096 / 74.4-75.2 at 2048, N=12288 44.8 / 47.1, N=8192 25.8 / 27.7)
-            const int64_t retire_rows = h->tune.engine_retire >= 0 ? h->tune.engine_retire : (m >= 16384 ? 2048 : 4096);
-            const int64_t local_rows = std::min<int64_t>(local_max, retire_rows);
-            if (retire_rows > 0 && eng_end >= nblk && !h->eng_host_mode && !h->tune.engine_replay && f.pivot && h->panel_local == 2 && !h->coop_launch && local_rows >= 1024 && m > local_rows + 4 * NB) {
-                eng_retire_leaf = (m - local_rows + NB - 1) / NB;   // first leaf whose panel has at most local_rows rows
-                a.retire_xcc = h->panel_xcc;
-                a.retire_leaf = (int)std::max<int64_t>(1, eng_retire_leaf - 2);
-            }
+        if (eng_retire_leaf >= 0) {
+            a.retire_xcc = h->panel_xcc;
+            a.retire_leaf = (int)std::max<int64_t>(1, eng_retire_leaf - 2);
         }
         a.trace = nullptr;
         long long*& eng_trace_buf = h->eng_trace_buf;   // measurement only (RFLU_ENGINE_TRACE=1): stamps of the leaf windows, printed at the next call
@@ -1184,17 +1166,13 @@ static int factor_leafwise(Fact<T>& f, int64_t W, int64_t b_begin, hipStream_t U
         h->eng_active = true;
         // While the engine is resident the only CUs with room are the 4 per XCD its mask leaves out: the any-placement leaves (at most
         // 32 workgroups, one per CU) fit there, the XCD-local ones (all participants on ONE XCD) would wait for CUs it never gives back
-        restore_local.on = true;
-        h->tune.panel_local_rows = 0;
+        h->local_rows_cap = 0;
         Uprev = E;
     }
     for (int64_t b = b_begin; b < nblk; ++b) {
         const bool in_eng = b < eng_end;
         if (in_eng && h->tune.engine_replay) continue;   // (measurement: the engine alone)
-        if (eng_end > 0 && b == eng_end) {   // the streams take over: the leaves are short enough for the XCD-local exchange again
-            h->tune.panel_local_rows = restore_local.rows;
-            restore_local.on = false;
-        }
+        if (eng_end > 0 && b == eng_end) h->local_rows_cap = -1;   // the streams take over: the leaves are short enough for the XCD-local exchange again
         const int64_t j0 = b * W, jb = std::min(W, mn - j0), je = j0 + jb;
         const int64_t bend = std::min(j0 + W, n), wend = std::min(j0 + 2 * W, n);
         const int res = reserve_for(m - j0);
@@ -1221,7 +1199,7 @@ static int factor_leafwise(Fact<T>& f, int64_t W, int64_t b_begin, hipStream_t U
             const int64_t g = g0 + i, c0 = j0 + i * NB, w = std::min<int64_t>(NB, je - c0);
             if (in_eng && g == eng_retire_leaf) {   // the chain's XCD is its own again: XCD-local leaves from here on
                 RFLU_TRY(launch_eng_wait_retired(h, h->panel_xcc));
-                h->tune.panel_local_rows = restore_local.rows;   // (every panel from here on is at most engine_retire rows tall)
+                h->local_rows_cap = -1;   // (every panel from here on is at most engine_retire rows tall)
             }
             RFLU_TRY(launch_panel<T>(h, R, ld, m, c0, c0, w, f.ipiv, f.pivot));
             const int64_t la0 = c0 + w, la1 = std::min(la0 + NB, n);
@@ -1387,105 +1365,38 @@ static int getrf_rm(Handle* h, int64_t m, int64_t n, T* R, int64_t ld, int64_t* 
     if (!pivot && ipiv) RFLU_TRY(launch_iota_ipiv(h, ipiv, 0, mn));  // src/lu.jl:111-113
 
     Fact<T> f{h, R, ld, m, n, ipiv, pivot};
-    bool fat_tail_done = false;
-    const bool default_bs = blocksize == 0;
-    if (blocksize == 0) blocksize = default_blocksize(mn);
-    // column-major entry with the tail of the layout change still in flight (getrf_cm_dev): only factor_lookahead knows where the
-    // first access to those columns is; every other path waits for it here
+    // which schedule (schedule_plan.hpp).  The two-stream schedules ask for their CU-masked streams first: a mask that cannot be had
+    // changes the plan (the leaf-wise / engine schedules hand work between streams through device-side gates: only with real masks)
+    SchedIn in = sched_in(h, m, n, sizeof(T), pivot, blocksize, h->eng_host_mode ? ENTRY_HOST_ENGINE : ENTRY_RM,
+                          reinterpret_cast<uintptr_t>(R) % 16 == 0, ld);
+    SchedPlan p = plan_schedule(in);
+    // column-major entry with the tail of the layout change still in flight (getrf_cm_dev): only factor_lookahead and the engine know
+    // where the first access to those columns is; every other path waits for it here
     hipEvent_t tail = h->tail_event;
     h->tail_event = nullptr;
-    const bool two_stream = !(blocksize < 0 || blocksize >= mn) && !(h->prof || h->prof_one_stream) && h->num_cus == 256;
-    if (tail && !two_stream) {
+    if (p.two_stream) {
+        hipStream_t probe;
+        RFLU_TRY(get_ustream(h, 32, &probe));
+        RFLU_TRY(get_ustream(h, 64, &probe));
+        if (!h->mask_failed) RFLU_TRY(validate_queues(h));
+        in.mask_failed = h->mask_failed;
+        p = plan_schedule(in);
+    }
+    if (h->eng_host_mode && p.path != RFLU_PATH_HIP_ENGINE) {   // (getrf_host asked the same plan: tests/schedule_plan_check.cpp)
+        set_error("getrf: host entry through the engine asked for a schedule the engine cannot serve");
+        return RFLU_ERR_ARG;
+    }
+    if (tail && p.b_switch == 0 && p.eng_end == 0) {
         RFLU_HIP(hipStreamWaitEvent(h->stream, tail, 0));
         tail = nullptr;
     }
-    if (blocksize < 0 || blocksize >= mn) {
-        h->last_path = RFLU_PATH_HIP_RECURSIVE;
+    f.tail = tail;
+    h->last_path = p.path;
+    const auto t_enq0 = std::chrono::steady_clock::now();
+    if (p.path == RFLU_PATH_HIP_RECURSIVE) {
         RFLU_TRY(f.rec(0, mn));
-    } else if (!(h->prof || h->prof_one_stream) && h->num_cus == 256) {   // the CU reservation of the two-stream schedule is laid out for 8 x 32 CUs
-        h->last_path = RFLU_PATH_HIP_LOOKAHEAD;
-        // tall block columns (update-bound): factor_lookahead; from the first panel of at most lw_rows rows on: factor_leafwise.
-        // RFLU_LEAFWISE=0 keeps the lookahead schedule to the end.
-        int leafwise = h->tune.leafwise;
-        // rocprofv3 --pmc runs ONE kernel at a time across all queues: a gate kernel waiting for another stream's kernel would
-        // never see it start (the 2 s gate timeout turns that into RFLU_ERR_TIMEOUT).  A counter-collection run therefore asks
-        // for RFLU_SCHEDULE=events: the lookahead schedule, whose cross-stream edges are hipEvents, to the end (same kernels on
-        // the same shapes for the bulk of the work; scripts/collect_profiles.sh sets it for the --pmc passes only).
-        if (h->tune.schedule_events && !h->tune.engine_replay) leafwise = 0;
-        {   // the leaf-wise / deep schedules hand work between streams through device-side gates: only with real CU-masked streams
-            hipStream_t probe;
-            RFLU_TRY(get_ustream(h, 32, &probe));
-            RFLU_TRY(get_ustream(h, 64, &probe));
-            if (h->mask_failed) leafwise = 0;
-            if (!h->mask_failed) RFLU_TRY(validate_queues(h));
-        }
-        int64_t Wb = round_up(blocksize, NB);
-        // Large matrices with the default block width: WIDE block columns (1024 / 2048: the bulk GEMM at K >= 1024 runs at 0.88-0.91 of
-        // the MFMA peak instead of 0.83) while the update is the bottleneck, i.e. up to the last `narrow_cols` columns; those are
-        // factored the way a matrix of that size is -- 512-wide block columns, leaf-wise from 8192 rows on -- because there the
-        // chain of panels sets the pace and a 2048-column recursion on the critical path is what costs.
-        int64_t W_wide = 0, wide_end = 0;
-        if (default_bs && h->tune.wide_narrow && Wb > 512 && mn >= 20480) {
-            const int64_t narrow_cols = std::max<int64_t>(h->tune.narrow_cols, 2048);
-            W_wide = Wb;
-            Wb = 512;
-            wide_end = std::max<int64_t>(mn - narrow_cols, 0) / W_wide * W_wide;
-        }
-        const auto t_enq0 = std::chrono::steady_clock::now();
-        const int64_t nblk = (mn + Wb - 1) / Wb;
-        int64_t b_switch = nblk;   // first block column of the leaf-wise part
-        // (block columns wider than 512 make the side stream's per-leaf window -- up to 2 W columns at K = 64 -- too much work to
-        //  finish within one leaf: N=32768 at W=2048 is 0.8 % (Float64) / 5 % (Float32) slower leaf-wise, so those stay as they were)
-        if (leafwise && Wb >= 2 * NB && Wb <= 512) {
-            // Float64: panels at most this tall are the bottleneck of their block column (N=16384: 84.8 ms at 7168-8192, 85.4 at
-            // 9216, 88.3 for the whole matrix); Float32's faster GEMM leaves the panel the bottleneck everywhere (61.7 vs 64.5 ms)
-            int64_t lw_rows = sizeof(T) == 8 ? 8192 : 16384;   // 16384 rows = 32 workgroups: the most the 32 reserved CUs take
-            if (h->tune.leafwise_rows >= 0) lw_rows = h->tune.leafwise_rows;
-            lw_rows = std::min<int64_t>(lw_rows, 32 * (int64_t)PANEL_THREADS);
-            b_switch = m <= lw_rows ? 0 : std::min(nblk, (m - lw_rows + Wb - 1) / Wb);
-        }
-        // the block column in front of the leaf-wise part has to be a narrow one (factor_leafwise finds its events by number)
-        if (W_wide > 0 && b_switch < nblk) wide_end = std::min(wide_end, std::max<int64_t>(b_switch - 1, 0) * Wb / W_wide * W_wide);
-        hipStream_t U_last = nullptr;
-        {
-            // the update engine serves the block columns whose panels are taller than engine_rows (the leaf-wise schedule from block
-            // column 0, its side / update streams replaced by the engine); below that the streams and the XCD-local leaves take over
-            int64_t eng_end = 0;
-            // the engine where asked for (RFLU_ENGINE=1, the host entry) or, by default, where it measures faster than the streams: with
-            // pivoting at the default block width of 512, i.e. more than 11264 columns (N=16384 Float64: 71.5 vs 75 ms, Float32 -- round 6 --
-            // 55.3 vs 58.8; N=12288: 41.5 vs 43.5 through the streams at 256, Float32 36.9 vs 38.4; NoPivot at N=16384: 68.9 vs 64.1, the
-            // streams stay; below, at 256-wide block columns, the streams win: N=10240 32.9 vs 33.8, N=8192 24.0 vs 24.9).  A Float32 pivot search may answer another summation order with another (equally valid) pivot sequence from a
-            // near-tie on -- between the stream schedules too: tests hold Float32 to the residual and a floor of equal
-            // leading pivots, not to the bits of another schedule.
-            const bool eng_wanted = h->eng_host_mode || h->tune.engine == 1 || h->tune.engine_replay ||
-                                    (h->tune.engine < 0 && pivot && default_bs && Wb == 512 && mn > 11264 && m >= n);
-            if (eng_wanted && leafwise && Wb >= 2 * NB && Wb <= 512 && W_wide == 0 && m <= 32 * (int64_t)PANEL_THREADS && engine_usable<T>(h, f, Wb)) {
-                const int64_t er = h->eng_host_mode ? 0 : std::max<int64_t>(h->tune.engine_rows, 0);   // (host entry: every block column through the engine)
-                eng_end = m <= er ? 0 : std::min(nblk, (m - er + Wb - 1) / Wb);
-            }
-            if (h->eng_host_mode && eng_end < nblk) {   // the caller feeds the matrix in behind our back: only the engine waits for it
-                set_error("getrf: host entry through the engine asked for a schedule the engine cannot serve");
-                return RFLU_ERR_ARG;
-            }
-            if (tail && b_switch == 0 && eng_end == 0) {
-                RFLU_HIP(hipStreamWaitEvent(h->stream, tail, 0));
-                tail = nullptr;
-            }
-            f.tail = tail;
-            if (eng_end > 0) {
-                h->last_path = RFLU_PATH_HIP_ENGINE;
-                RFLU_TRY(factor_leafwise<T>(f, Wb, 0, nullptr, eng_end));
-                b_switch = nblk;
-            } else if (b_switch > 0) RFLU_TRY(factor_lookahead<T>(f, Wb, b_switch, &U_last, W_wide, wide_end));
-            if (b_switch < nblk) RFLU_TRY(factor_leafwise<T>(f, Wb, b_switch, U_last));
-        }
-        if (h->tune.time_enqueue)
-            fprintf(stderr, "[rflu] host enqueue time %.2f ms\n",
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count());
-        fat_tail_done = true;  // the block-column updates already reached the columns right of the square part
-    } else {
-        h->last_path = RFLU_PATH_HIP_BLOCKED;
-        const int64_t bs = round_up(blocksize, NB);
+    } else if (p.path == RFLU_PATH_HIP_BLOCKED) {
+        const int64_t bs = p.Wb;
         for (int64_t j = 0; j < mn; j += bs) {
             const int64_t jb = std::min(bs, mn - j);
             RFLU_TRY(f.rec(j, j + jb));
@@ -1496,8 +1407,21 @@ static int getrf_rm(Handle* h, int64_t m, int64_t n, T* R, int64_t ld, int64_t* 
                                         R + je * ld + je, ld));
             }
         }
+    } else {
+        hipStream_t U_last = nullptr;
+        if (p.path == RFLU_PATH_HIP_ENGINE) {
+            RFLU_TRY(factor_leafwise<T>(f, p, 0, nullptr));
+        } else {
+            if (p.b_switch > 0) RFLU_TRY(factor_lookahead<T>(f, p.Wb, p.b_switch, &U_last, p.W_wide, p.wide_end));
+            if (p.b_switch < p.nblk) RFLU_TRY(factor_leafwise<T>(f, p, p.b_switch, U_last));
+        }
+        if (h->tune.time_enqueue)
+            fprintf(stderr, "[rflu] host enqueue time %.2f ms\n",
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count());
     }
-    if (m < n && !fat_tail_done)  // fat matrix: AR <- L^-1 AR (src/lu.jl:148-154; interchanges already applied there)
+    // fat matrix: AR <- L^-1 AR (src/lu.jl:148-154; interchanges already applied there) -- the two-stream schedules' block-column
+    // updates have already reached the columns right of the square part
+    if (m < n && !p.two_stream)
         RFLU_TRY(trsm_rec<T>(h, m, n - m, R, ld, R + m, ld, f.linv_at(0)));
 
     if (h->before_sync) RFLU_TRY(h->before_sync());
@@ -1524,11 +1448,9 @@ static int getrf_cm_dev(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int6
     T* R = static_cast<T*>(h->work);
     // Layout change in two pieces: the first block column on the caller's stream, the rest on the CU-masked update stream while
     // the first panel (2.3 ms on 32 CUs at N=16384, nothing else to do) already runs.
-    const int64_t mn = std::min(m, n);
-    int64_t W0 = blocksize == 0 ? default_blocksize(mn) : blocksize;
-    W0 = W0 > 0 ? round_up(W0, NB) : 0;
-    const bool tail_overlap = h->tune.tail_overlap != 0;
-    if (tail_overlap && !(h->prof || h->prof_one_stream) && h->num_cus == 256 && mn >= 12288 && W0 > 0 && W0 < mn && n - W0 >= 4096) {
+    const SchedPlan p = plan_schedule(sched_in(h, m, n, sizeof(T), pivot, blocksize, ENTRY_CM, reinterpret_cast<uintptr_t>(R) % 16 == 0, ldr));
+    const int64_t W0 = p.tail_w0;
+    if (p.tail_overlap) {
         if (!h->tail_event_obj) {
             RFLU_HIP(hipEventCreateWithFlags(&h->tail_event_obj, hipEventDisableTiming));
             RFLU_HIP(hipEventCreateWithFlags(&h->tail_fork_obj, hipEventDisableTiming));
@@ -1575,25 +1497,16 @@ static int getrf_cm_dev(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int6
 // caller) -- copy, layout change, a word that says how many columns are in place -- while the critical-path stream, which waits on the
 // same word, factors what is there; finished block rows leave as before, told by a host-visible word the engine keeps
 // (EngArgs::rows_final) instead of events.  Every block column goes through the engine here (no hand-over to the streams).
-// *handled = false: not a case for this path (the caller falls back to getrf_host's sequence), nothing has been touched.
+// Called where the plan says so (SchedPlan::host_engine).  *handled = false: no CU-masked streams or no pinned memory to be had (the
+// caller falls back to getrf_host's sequence).
 template <typename T>
 static int getrf_host_engine(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv, int pivot, int64_t blocksize,
-                             int64_t* info, bool* handled)
+                             const SchedPlan& plan, int64_t* info, bool* handled)
 {
     *handled = false;
     const int64_t mn = std::min(m, n);
     const int64_t chunk = h->tune.host_early_out;
-    const int64_t W = round_up(blocksize == 0 ? default_blocksize(mn) : blocksize, NB);
-    // With pivoting only (round 6: Float32 too -- its device entry takes the engine at the headline size as well; a Float32 pivot search may
-    // answer the engine's summation order with another, equally valid pivot sequence than a stream schedule's from a near-tie on, which is
-    // why tests hold Float32 to the residual and a floor of equal leading pivots).  An unpivoted factorization shows another summation order
-    // in visibly other digits and measures slower through the engine (N=16384: 68.9 vs 64.1 ms): it keeps the stream path, whose host entry
-    // is bit-identical to the device entry
-    if (!pivot) return RFLU_OK;
-    if (!h->tune.engine_host || h->prof || h->prof_one_stream || h->num_cus != 256 || !h->tune.leafwise || h->tune.schedule_events ||
-        chunk < 64 || mn < 8192 || m > 32 * (int64_t)PANEL_THREADS || m < n || W < 2 * NB || W > 512 || W % 128 != 0 || W >= mn ||
-        (blocksize == 0 && mn >= 20480))
-        return RFLU_OK;
+    const int64_t W = plan.Wb;
     const int64_t ldr = workspace_ld(h, n);
     hipStream_t E, IN, OUT;
     RFLU_TRY(get_ustream(h, 32, &E));
@@ -1784,9 +1697,10 @@ static int getrf_host(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_
     *info = 0;
     const int64_t mn = std::min(m, n);
     if (mn == 0) return RFLU_OK;
-    {   // the way in overlapped with the factorization (the update engine's dataflow waits for columns; the stream schedules cannot)
+    const SchedPlan p = plan_schedule(sched_in(h, m, n, sizeof(T), pivot, blocksize, ENTRY_HOST, true, workspace_ld(h, n)));   // (workspace: hipMalloc)
+    if (p.host_engine) {   // the way in overlapped with the factorization (the update engine's dataflow waits for columns; the stream schedules cannot)
         bool handled = false;
-        const int rc = getrf_host_engine<T>(h, m, n, A, lda, ipiv, pivot, blocksize, info, &handled);
+        const int rc = getrf_host_engine<T>(h, m, n, A, lda, ipiv, pivot, blocksize, p, info, &handled);
         if (handled || rc != RFLU_OK) return rc;
     }
     RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)m * (size_t)n * sizeof(T)));
@@ -1818,8 +1732,7 @@ static int getrf_host(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_
     // single long kernel does not wait: scripts/probes/d2h_block.hip), so the runtime's staging is of no use here.
     // RFLU_HOST_EARLY_OUT=0: the round-2 sequence (everything after the factorization).
     const int64_t chunk = h->tune.host_early_out;
-    const int64_t W0 = blocksize == 0 ? default_blocksize(mn) : blocksize;
-    const bool early = chunk >= 64 && !(h->prof || h->prof_one_stream) && h->num_cus == 256 && mn >= 8192 && W0 > 0 && W0 < mn;
+    const bool early = p.host_early;
     struct Mark { int64_t r1; std::vector<hipEvent_t> ev; };
     std::vector<Mark> marks;
     size_t ev_used = 0;

@@ -520,7 +520,7 @@ int launch_panel(Handle* h, T* R, int64_t ld, int64_t m, int64_t r0, int64_t c0,
 #ifdef RFLU_EXPERIMENTS
     if (pivot && w == NB && panel_use_blocked(h, rows, sizeof(T))) {
         // the sub-panel kernel (panel_blocked.hip); XCD-local records for the short panels as below
-        const int64_t local_rows = h->tune.panel_local_rows >= 0 ? h->tune.panel_local_rows : (sizeof(T) == 4 ? 8192 : 4096);
+        const int64_t local_rows = local_leaf_rows(h->tune, sizeof(T), h->local_rows_cap);
         const bool loc = h->panel_local == 1 || (h->panel_local == 2 && h->num_cus == 256 && rows <= local_rows);
         RFLU_TRY(launch_panel_blocked<T>(h, p, loc ? 1 : 0));
         return RFLU_OK;
@@ -545,7 +545,7 @@ int launch_panel(Handle* h, T* R, int64_t ld, int64_t m, int64_t r0, int64_t c0,
             // N=8192).  RFLU_PANEL_LOCAL_ROWS=0 switches it off, RFLU_PANEL_LOCAL=1 forces it for every panel.
             // Float32: the update is half as heavy, the 32 participants of an 8192-row panel still find their XCD (N=16384 61.9 -> 59.9-60.7 ms,
             // N=8192 22.45 -> 22.18; 12288 rows: 62.1)
-            const int64_t local_rows = h->tune.panel_local_rows >= 0 ? h->tune.panel_local_rows : (sizeof(T) == 4 ? 8192 : 4096);
+            const int64_t local_rows = local_leaf_rows(h->tune, sizeof(T), h->local_rows_cap);
             const bool loc = h->panel_local == 1 || (h->num_cus == 256 && rows <= local_rows && (rows > 512 || tiny_local));
             RFLU_TRY(launch_panel_local<T>(h, p, loc ? 8 : 1, loc ? h->panel_xcc : 0, loc ? h->panel_xcc : -1, loc));
             return RFLU_OK;

@@ -114,7 +114,7 @@ struct Tune {
     int debug_ghost_leaf = -1;         // RFLU_DEBUG_GHOST_LEAF
     // persistent update engine (engine.hip): the default schedule where it measures faster than the streams, and the host entry
     int engine = -1;                   // RFLU_ENGINE: 1 = the side / update streams' work is pulled by the resident engine wherever it can be, 0 = never,
-                                       // -1 (default) = where it measures faster: pivoted, default block width, 12288 < min(m, n), m <= 16384 (N=16384: 72 vs 75 ms, Float32 56.0 vs 58.8)
+                                       // -1 (default) = where it measures faster (schedule_plan.hpp: plan_schedule)
     int engine_policy = 0;             // RFLU_ENGINE_POLICY: 0 = leftmost column block first, 1 = oldest panel piece first
     int engine_wgs = 0;                // RFLU_ENGINE_WGS: resident workgroups (0: two per CU of the update mask)
     int64_t engine_rows = 0;           // RFLU_ENGINE_ROWS: block columns whose panels are taller than this go through the engine, the streams take over below (0: the engine
@@ -214,6 +214,7 @@ struct Handle {
                                  // bit-identical, measured no faster than the default leaves: opt-in)
     int panel_local_maxg = 64;
     int panel_xcc = 0;
+    int64_t local_rows_cap = -1; // set by the schedule: tallest XCD-local leaf while it runs (0 while the update engine is resident; -1: no cap)
     int trsv_max_wgs[2] = {0, 0};    // same for the cooperative solve kernels (asked on first use, per element type: [Float64, Float32])
     int trsm32_per_cu[2] = {0, 0};
     int trsm16_per_cu[2] = {0, 0};   // workgroups of the 16-column block solve a CU holds (trsv.hip: chains side by side)
@@ -243,6 +244,13 @@ struct Handle {
     std::vector<AsyncRec> async_recs;      // pending event pairs of the in-schedule mode
     std::vector<hipEvent_t> async_pool;    // timing events kept for reuse
 };
+
+// tallest panel the XCD-local leaf serves: RFLU_PANEL_LOCAL_ROWS (default 4096 Float64 / 8192 Float32), at most `cap` (Handle::local_rows_cap)
+inline int64_t local_leaf_rows(const Tune& t, size_t esize, int64_t cap = -1)
+{
+    const int64_t rows = t.panel_local_rows >= 0 ? t.panel_local_rows : (esize == 4 ? 8192 : 4096);
+    return cap >= 0 && cap < rows ? cap : rows;
+}
 
 struct ProfScope {
     Handle* h;
