@@ -134,6 +134,31 @@ int rflu_getrs_rm_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const d
 int rflu_getrs_rm_f32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* R_dev, int64_t ld,
                           const int64_t* ipiv_dev, float* B_dev, int64_t ldb);
 
+/* ---- the TRANSPOSED solve: ldiv!(F', B) / ldiv!(transpose(F), B), i.e. B <- P^T L^-T U^-T B = A^-T B ----
+ * LAPACK getrs with trans = 'T' (real element types only, so adjoint and transpose coincide).  Arguments, argument checks, stream
+ * use and the synchronisation before return exactly as the rflu_getrs_* entry of the same shape; ipiv == NULL plays NotIPIV;
+ * a singular U (info != 0) yields Inf/NaN like LAPACK, the host glue checks info first.
+ *   - The column-major entries read F IN PLACE: a column-major F read as a row-major array with ld = lda is F^T (lower triangle
+ *     with the diagonal = U^T, strict upper triangle = L^T), so no n x n layout change happens.  Any lda >= n and any pointer
+ *     aligned to the element size are accepted; with lda * sizeof(T) and the pointer multiples of 16 bytes the blocks arrive as
+ *     16-byte loads, otherwise element by element (same arithmetic, same results).
+ *   - The row-major entries (F as left by rflu_getrf_rm_*) pay one layout change of R into the handle's workspace first: there the
+ *     transposed view is not free.
+ *   - Served by the cooperative chain kernels for ANY nrhs (passes of 8 right-hand sides up to 32, passes of 64 beyond); they cover
+ *     n <= 65536.  A larger n returns RFLU_ERR_ARG with a message: there is no recursive form of this solve and no CPU fallback. */
+int rflu_getrs_trans_f64(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* F_host, int64_t lda,
+                         const int64_t* ipiv_host, double* B_host, int64_t ldb);
+int rflu_getrs_trans_f32(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_host, int64_t lda,
+                         const int64_t* ipiv_host, float* B_host, int64_t ldb);
+int rflu_getrs_trans_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* F_dev, int64_t lda,
+                             const int64_t* ipiv_dev, double* B_dev, int64_t ldb);
+int rflu_getrs_trans_f32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda,
+                             const int64_t* ipiv_dev, float* B_dev, int64_t ldb);
+int rflu_getrs_trans_rm_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* R_dev, int64_t ld,
+                                const int64_t* ipiv_dev, double* B_dev, int64_t ldb);
+int rflu_getrs_trans_rm_f32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* R_dev, int64_t ld,
+                                const int64_t* ipiv_dev, float* B_dev, int64_t ldb);
+
 /* ---- building blocks on the INTERNAL row-major layout: element (i,j) at R[i*ld + j] (device pointers).
  * These are the four kernels of the path plus the bookkeeping the multi-GPU block-column driver and the parity
  * tests need.  Pivot rows are GLOBAL 0-based row positions r0.. of the slab; ipiv entries are 1-based rows.

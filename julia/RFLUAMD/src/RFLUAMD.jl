@@ -138,6 +138,25 @@ function getrs!(F::StridedMatrix{Float32}, ipiv::Ptr{Int64}, B::StridedVecOrMat{
     return B
 end
 
+"`ldiv!(F', B)` / `ldiv!(transpose(F), B)` on the GPU: B <- P^T L^-T U^-T B (LAPACK getrs with trans = 'T'; real types, so one routine)"
+function getrs_trans!(F::StridedMatrix{Float64}, ipiv::Ptr{Int64}, B::StridedVecOrMat{Float64})
+    n = size(F, 1)
+    st = ccall((:rflu_getrs_trans_f64, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Int64),
+               handle(), n, size(B, 2), F, stride(F, 2), ipiv, B, B isa AbstractVector ? n : stride(B, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+function getrs_trans!(F::StridedMatrix{Float32}, ipiv::Ptr{Int64}, B::StridedVecOrMat{Float32})
+    n = size(F, 1)
+    st = ccall((:rflu_getrs_trans_f32, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float32}, Int64),
+               handle(), n, size(B, 2), F, stride(F, 2), ipiv, B, B isa AbstractVector ? n : stride(B, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
 # ---- dispatch: who serves a call (RecursiveFactorization src/lu.jl:92-93, 114-126) -------------------------------------------
 const GPUEltype = Union{Float32, Float64}
 gpu_ok(A::StridedMatrix{<:GPUEltype}, ipiv) =
@@ -200,6 +219,28 @@ function ldiv!(F::LU{T, <:StridedMatrix{T}}, B::StridedVecOrMat{T}) where {T <: 
         return B
     end
     return LinearAlgebra.ldiv!(F, B)
+end
+
+# What `F'` and `transpose(F)` of an LU are: AdjointFactorization / TransposeFactorization from Julia 1.10 on (where the transpose of a
+# real factorization is its adjoint), the array wrappers Adjoint / Transpose in Julia 1.9, the oldest version Project.toml admits.
+@static if isdefined(LinearAlgebra, :AdjointFactorization)
+    const AdjointLU{T} = LinearAlgebra.AdjointFactorization{T, <:LU{T, <:StridedMatrix{T}}}
+    const TransposeLU{T} = LinearAlgebra.TransposeFactorization{T, <:LU{T, <:StridedMatrix{T}}}
+else
+    const AdjointLU{T} = Adjoint{T, <:LU{T, <:StridedMatrix{T}}}
+    const TransposeLU{T} = Transpose{T, <:LU{T, <:StridedMatrix{T}}}
+end
+
+"solve A' x = b / transpose(A) x = b with the factors of A on the GPU (same conditions as `ldiv!(F, B)`), else stdlib `ldiv!`"
+function ldiv!(Ft::Union{AdjointLU{T}, TransposeLU{T}}, B::StridedVecOrMat{T}) where {T <: GPUEltype}
+    F = parent(Ft)
+    lay_ok = stride(F.factors, 1) == 1 && stride(B, 1) == 1 && size(F.factors, 1) == size(F.factors, 2) == size(B, 1)
+    if lay_ok && size(F.factors, 1) >= GPU_MIN_N[] && available() && (F.ipiv isa Vector{Int64} || F.ipiv isa NotIPIV)
+        p = F.ipiv isa NotIPIV ? Ptr{Int64}(C_NULL) : pointer(F.ipiv)
+        GC.@preserve F B getrs_trans!(F.factors, p, B)
+        return B
+    end
+    return LinearAlgebra.ldiv!(Ft, B)
 end
 
 """

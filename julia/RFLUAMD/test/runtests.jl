@@ -29,3 +29,17 @@ end
     F = RFLUAMD.lu!(rand(300, 300) + 10I, ipiv, Val(false), Val(false))
     @test ipiv == 1:300
 end
+@testset "RFLUAMD ldiv! with the adjoint / transposed factorization" begin
+    RFLUAMD.GPU_MIN_N[] = 64
+    for _p in (true, false), T in (Float64, Float32), n in (64, 65, 300, 1000)
+        A = rand(T, n, n) + T(10) * I
+        F = RFLUAMD.lu(A, Val(_p))
+        b = rand(T, n); B = rand(T, n, 3)
+        for Ft in (F', transpose(F))
+            x = RFLUAMD.ldiv!(Ft, copy(b))
+            @test norm(A' * x - b) < 1000n * eps(T)          # the reference's bound for ldiv!, test/runtests.jl:126-128
+            X = RFLUAMD.ldiv!(Ft, copy(B))
+            @test norm(A' * X - B) < 1000n * eps(T)
+        end
+    end
+end

@@ -325,6 +325,106 @@ static int getrs_host(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t ld
     return RFLU_OK;
 }
 
+// ---- ldiv!(F', B): B <- P^T L^-T U^-T B, LAPACK getrs with trans = 'T' (real types: adjoint == transpose) ----------------------------
+// V is the row-major image of F^T, B the row-major n x nrhs block.  The cooperative chain only (trsv.hip): passes of 8 columns up to
+// trsv_max_rhs right-hand sides, passes of 64 on the MFMA units beyond, for any nrhs -- there is no recursive form of this solve.
+template <typename T>
+static int getrs_trans_view(Handle* h, int64_t n, int64_t nrhs, const T* V, int64_t ldv, const int64_t* ipiv, T* B, int64_t ldb)
+{
+    if (n <= 0 || nrhs <= 0) return RFLU_OK;
+    if (n > (int64_t)NB * 256 * 4) {
+        set_error("getrs_trans: n = %lld exceeds the %d rows the cooperative solve covers", (long long)n, NB * 256 * 4);
+        return RFLU_ERR_ARG;
+    }
+    RFLU_TRY(ensure_bookkeeping(h, n));
+    RFLU_HIP(hipMemsetAsync(h->info_dev, 0, 2 * sizeof(int64_t), h->stream));
+    RFLU_TRY(launch_trsv_coop<T>(h, n, nrhs, V, ldv, B, ldb, nrhs > h->tune.trsv_max_rhs, true));
+    if (ipiv) {  // the factorization's interchanges, undone last to first (NULL = NotIPIV: nothing to apply)
+        RFLU_TRY(launch_perm_build(h, ipiv, 0, n, n));
+        RFLU_TRY(launch_laswp_rev<T>(h, B, ldb, nrhs, 0, (n + NB - 1) / NB));
+    }
+    RFLU_HIP(hipMemcpyAsync(h->info_pinned, h->info_dev, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    if (h->info_pinned[1] != 0) {
+        set_error("cooperative solve kernel timed out waiting for a peer workgroup");
+        return RFLU_ERR_TIMEOUT;
+    }
+    return RFLU_OK;
+}
+
+// column-major device entry.  A column-major F read as a row-major array with ld = lda IS F^T: the factors are read in place, whatever
+// lda and the pointer's alignment (the chain kernels fall back to element loads where a 16-byte load would be misaligned); only the
+// right-hand sides change layout.
+template <typename T>
+static int getrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B,
+                              int64_t ldb)
+{
+    if (n < 0 || nrhs < 0 || lda < std::max<int64_t>(n, 1) || ldb < std::max<int64_t>(n, 1)) {
+        set_error("getrs_trans: bad arguments n=%lld nrhs=%lld lda=%lld ldb=%lld", (long long)n, (long long)nrhs,
+                  (long long)lda, (long long)ldb);
+        return RFLU_ERR_ARG;
+    }
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    const int64_t ldx = round_up(nrhs, 16);
+    RFLU_TRY(ensure_buffer(&h->rhs_work, &h->rhs_work_bytes, (size_t)n * (size_t)ldx * sizeof(T)));
+    T* X = static_cast<T*>(h->rhs_work);
+    RFLU_TRY(launch_transpose<T>(h, n, nrhs, B, ldb, X, ldx));
+    RFLU_TRY(getrs_trans_view<T>(h, n, nrhs, F, lda, ipiv, X, ldx));
+    RFLU_TRY(launch_transpose<T>(h, nrhs, n, X, ldx, B, ldb));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+// row-major factors (getrf_rm): here the transposed view is not free -- one layout change of R into the handle's workspace, then the
+// same path
+template <typename T>
+static int getrs_trans_rm(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld, const int64_t* ipiv, T* B, int64_t ldb)
+{
+    if (n < 0 || nrhs < 0 || ld < std::max<int64_t>(n, 1) || ldb < std::max<int64_t>(nrhs, 1)) {
+        set_error("getrs_trans_rm: bad arguments n=%lld nrhs=%lld ld=%lld ldb=%lld", (long long)n, (long long)nrhs,
+                  (long long)ld, (long long)ldb);
+        return RFLU_ERR_ARG;
+    }
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    const int64_t ldv = workspace_ld(h, n);
+    RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldv * sizeof(T)));
+    T* V = static_cast<T*>(h->work);
+    RFLU_TRY(launch_transpose<T>(h, n, n, R, ld, V, ldv));
+    return getrs_trans_view<T>(h, n, nrhs, V, ldv, ipiv, B, ldb);
+}
+
+template <typename T>
+static int getrs_trans_host(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb)
+{
+    if (n < 0 || nrhs < 0 || lda < std::max<int64_t>(n, 1) || ldb < std::max<int64_t>(n, 1) ||
+        (n > 0 && nrhs > 0 && (F == nullptr || B == nullptr))) {
+        set_error("getrs_trans: bad arguments");
+        return RFLU_ERR_ARG;
+    }
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(T)));
+    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * (size_t)nrhs * sizeof(T)));
+    if ((size_t)n > h->ipiv_cap) {
+        if (h->ipiv_dev) RFLU_HIP(hipFree(h->ipiv_dev));
+        h->ipiv_dev = nullptr;
+        h->ipiv_cap = 0;
+        RFLU_HIP(hipMalloc((void**)&h->ipiv_dev, (size_t)n * sizeof(int64_t)));
+        h->ipiv_cap = (size_t)n;
+    }
+    T* dF = static_cast<T*>(h->hostA_dev);
+    T* dB = static_cast<T*>(h->hostB_dev);
+    RFLU_HIP(hipMemcpy2DAsync(dF, (size_t)n * sizeof(T), F, (size_t)lda * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
+                              hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipMemcpy2DAsync(dB, (size_t)n * sizeof(T), B, (size_t)ldb * sizeof(T), (size_t)n * sizeof(T), (size_t)nrhs,
+                              hipMemcpyHostToDevice, h->stream));
+    if (ipiv) RFLU_HIP(hipMemcpyAsync(h->ipiv_dev, ipiv, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    RFLU_TRY(getrs_trans_cm_dev<T>(h, n, nrhs, dF, n, ipiv ? h->ipiv_dev : nullptr, dB, n));
+    RFLU_HIP(hipMemcpy2DAsync(B, (size_t)ldb * sizeof(T), dB, (size_t)n * sizeof(T), (size_t)n * sizeof(T), (size_t)nrhs,
+                              hipMemcpyDeviceToHost, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 // error flags raised by the cooperative kernels (info_dev[1], copied to info_pinned[1] by the caller)
 static int panel_flags_status(Handle* h)
 {
@@ -1945,7 +2045,7 @@ struct DeviceGuard {
 
 extern "C" {
 
-int rflu_version(void) { return 100; }
+int rflu_version(void) { return 101; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -2225,6 +2325,24 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
         RFLU_TRY(getrs_rm<T>(H(handle), n, nrhs, R, ld, ipiv, B, ldb));                                               \
         RFLU_HIP(hipStreamSynchronize(H(handle)->stream));                                                            \
         return RFLU_OK;                                                                                               \
+    }                                                                                                                 \
+    int rflu_getrs_trans_##SFX(rflu_handle_t handle, int64_t n, int64_t nrhs, const T* F, int64_t lda,                \
+                               const int64_t* ipiv, T* B, int64_t ldb)                                                \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getrs_trans_host<T>(H(handle), n, nrhs, F, lda, ipiv, B, ldb);                                         \
+    }                                                                                                                 \
+    int rflu_getrs_trans_##SFX##_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const T* F, int64_t lda,          \
+                                     const int64_t* ipiv, T* B, int64_t ldb)                                          \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getrs_trans_cm_dev<T>(H(handle), n, nrhs, F, lda, ipiv, B, ldb);                                       \
+    }                                                                                                                 \
+    int rflu_getrs_trans_rm_##SFX##_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const T* R, int64_t ld,        \
+                                        const int64_t* ipiv, T* B, int64_t ldb)                                       \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getrs_trans_rm<T>(H(handle), n, nrhs, R, ld, ipiv, B, ldb);                                            \
     }                                                                                                                 \
     int rflu_butterfly_mul_##SFX##_dev(rflu_handle_t handle, int64_t n, T* A, int64_t lda, const T* uv)               \
     {                                                                                                                 \

@@ -285,6 +285,72 @@ template int launch_laswp3<float>(Handle*, float*, int64_t, int64_t, int64_t, in
 template int launch_laswp2<double>(Handle*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, double*, LaswpGate);
 template int launch_laswp2<float>(Handle*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const float*, float*, LaswpGate);
 
+// ---- the interchanges backwards (transposed solve: x = P^T z, LAPACK laswp with incx = -1) -----------------------------------
+// A chunk's move list  new[dst[e]] = old[src[e]]  is a permutation of the rows it names, so its inverse is the same list read the
+// other way round,  new[src[e]] = old[dst[e]],  and the chunks are undone last to first.  Geometry as laswp_strip with one element per
+// lane (the right-hand sides are a narrow block of any alignment): 8 lanes x 8 row slots per wave, a wave owns its 8 columns for the
+// whole launch, all row reads of a chunk before its first write, the next list requested while the rows travel.
+template <typename T>
+__global__ void __launch_bounds__(64 * LW_WAVES) laswp_rev_kernel(T* __restrict__ B, int64_t ldb, int64_t ncols, const int* __restrict__ pm_cnt,
+                                                                  const int* __restrict__ pm_dst, const int* __restrict__ pm_src,
+                                                                  int chunk0, int chunk1)
+{
+    constexpr int LPR = 8, RS = 64 / LPR, NI = (2 * NB) / RS;
+    const int lane = threadIdx.x & 63;
+    const int64_t strip = (int64_t)blockIdx.x * LW_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t col = strip * LPR + (lane & (LPR - 1));
+    const int rsub = lane / LPR;
+    if (strip * LPR >= ncols || chunk1 <= chunk0) return;   // (wave-uniform)
+    const bool active = col < ncols;
+    int t = chunk1 - 1;
+    int cnt = __builtin_amdgcn_readfirstlane(pm_cnt[t]);
+    int s0 = pm_src[(size_t)t * 2 * NB + lane], s1 = pm_src[(size_t)t * 2 * NB + NB + lane];
+    int d0 = pm_dst[(size_t)t * 2 * NB + lane], d1 = pm_dst[(size_t)t * 2 * NB + NB + lane];
+    for (; t >= chunk0; --t) {
+        T v[NI];
+        int to[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int e = i * RS + rsub;   // < 128; the same for the 8 lanes of a row slot
+            const int from = (i * RS < NB) ? __shfl(d0, e & 63) : __shfl(d1, e & 63);
+            to[i] = (i * RS < NB) ? __shfl(s0, e & 63) : __shfl(s1, e & 63);
+            if (i * RS < cnt) {   // wave-uniform
+                if (e < cnt && active) v[i] = B[(int64_t)from * ldb + col];
+            }
+        }
+        const int cur = cnt;
+        if (t > chunk0) {
+            cnt = __builtin_amdgcn_readfirstlane(pm_cnt[t - 1]);
+            s0 = pm_src[(size_t)(t - 1) * 2 * NB + lane];
+            s1 = pm_src[(size_t)(t - 1) * 2 * NB + NB + lane];
+            d0 = pm_dst[(size_t)(t - 1) * 2 * NB + lane];
+            d1 = pm_dst[(size_t)(t - 1) * 2 * NB + NB + lane];
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int e = i * RS + rsub;
+            if (i * RS < cur) {
+                if (e < cur && active) B[(int64_t)to[i] * ldb + col] = v[i];
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (see laswp_strip: a row written here may be read in the next chunk by another lane)
+    }
+}
+
+template <typename T>
+int launch_laswp_rev(Handle* h, T* B, int64_t ldb, int64_t ncols, int64_t chunk0, int64_t chunk1)
+{
+    if (ncols <= 0 || chunk1 <= chunk0) return RFLU_OK;
+    const int64_t strips = (ncols + 7) / 8;
+    ProfScope ps(h, RFLU_K_LASWP, 4.0 * sizeof(T) * (double)NB * (double)ncols * (double)(chunk1 - chunk0));
+    hipLaunchKernelGGL(laswp_rev_kernel<T>, dim3((unsigned)((strips + LW_WAVES - 1) / LW_WAVES)), dim3(64 * LW_WAVES), 0, h->stream, B, ldb,
+                       ncols, h->pm_cnt, h->pm_dst, h->pm_src, (int)chunk0, (int)chunk1);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+template int launch_laswp_rev<double>(Handle*, double*, int64_t, int64_t, int64_t, int64_t);
+template int launch_laswp_rev<float>(Handle*, float*, int64_t, int64_t, int64_t, int64_t);
+
 // ---- tiled transpose: out[r][c] = in[c][r]; "rows_out x cols_out" is the shape of `out` seen as row-major ------------
 // Used for column-major <-> R layout: a column-major m x n matrix (lda) IS a row-major n x m matrix (ld = lda).
 template <typename T>

@@ -323,9 +323,10 @@ template <typename T>
 int launch_diag_inv(Handle* h, int64_t n, const T* L, int64_t ldl, T* Linv);
 template <typename T>
 int launch_trsm_inv64(Handle* h, int64_t n, int64_t nrhs, const T* Linv, T* B, int64_t ldb);   // one block, LDS-free
-// cooperative solve for few right-hand sides (trsv.hip): B <- U^-1 L^-1 B, interchanges already applied
+// cooperative solve for few right-hand sides (trsv.hip): B <- U^-1 L^-1 B, interchanges already applied.  trans: R is the row-major
+// image of F^T (a column-major F read with ld = lda) and B <- L^-T U^-T B; the interchanges come afterwards, backwards (launch_laswp_rev)
 template <typename T>
-int launch_trsv_coop(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld, T* B, int64_t ldb, bool wide = false);
+int launch_trsv_coop(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld, T* B, int64_t ldb, bool wide = false, bool trans = false);
 // stream gates folded into an interchange launch (laswp.hip; used by factor_leafwise): hold the launch until *wait_flag >=
 // wait_val, and let its last workgroup publish signal_val (signal_cnt: a zero-initialised counter that wraps by itself)
 struct LaswpGate {
@@ -353,6 +354,10 @@ template <typename T>
 int launch_leaf_la(Handle* h, T* R, int64_t ld, int64_t la0, int64_t chunk, int64_t c0, const T* inv_L, T* inv_out, LaswpGate gate);
 // fold the interchanges ipiv[k0..k1) (k0 a multiple of NB) into per-chunk row-move lists
 int launch_perm_build(Handle* h, const int64_t* ipiv, int64_t k0, int64_t k1, int64_t m);
+// the interchanges of chunks [chunk0, chunk1) UNDONE on columns [0, ncols) of the row-major block B: last chunk first, every chunk's
+// move list (launch_perm_build) run backwards -- B <- P^T B, the last step of the transposed solve
+template <typename T>
+int launch_laswp_rev(Handle* h, T* B, int64_t ldb, int64_t ncols, int64_t chunk0, int64_t chunk1);
 size_t panel_scratch_bytes();
 int panel_resident_limit(int num_cus);   // min over the cooperative leaf kernels of (resident workgroups per CU) * num_cus
 size_t panel_trace_offset_bytes();

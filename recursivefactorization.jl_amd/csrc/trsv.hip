@@ -58,6 +58,49 @@ __global__ void __launch_bounds__(64) triu_inv_kernel(int n, const T* __restrict
     for (int i = 0; i < NB; ++i) out[i * NB + j] = sX[i * (NB + 1) + j];
 }
 
+// The two triangle kinds of the TRANSPOSED solve (ldiv!(F', B): A^T x = b, LAPACK getrs with trans = 'T').  V is the row-major image
+// of F^T -- for a column-major F simply F's own memory read row-major with ld = lda, no copy -- so its lower triangle, diagonal included,
+// is U^T (LOWER non-unit: UPPER = false, UNIT = false) and its strict upper triangle is L^T (UPPER unit: the stored diagonal belongs to
+// U and is never read).  Output as triu_inv_kernel: block b -> dense row-major 64x64, identity padding outside the matrix; a zero pivot
+// gives Inf / NaN as in LAPACK (the callers check info first).  One wave per block, lane = column of the inverse, substitution through
+// LDS: forward for the lower kind, backward for the upper one.
+template <typename T, bool UPPER, bool UNIT>
+__global__ void __launch_bounds__(64) tri_inv_trans_kernel(int n, const T* __restrict__ V, int64_t ld, T* __restrict__ Vinv)
+{
+    __shared__ T sA[NB * (NB + 1)];
+    __shared__ T sX[NB * (NB + 1)];
+    const int j = threadIdx.x, b = blockIdx.x;
+    const int nbk = min(NB, n - b * NB);
+    const T* Vb = V + (int64_t)b * NB * ld + b * NB;
+    for (int i = 0; i < NB; ++i) {
+        T v = (i == j) ? T(1) : T(0);
+        const bool in_tri = UPPER ? (UNIT ? j > i : j >= i) : (UNIT ? j < i : j <= i);
+        if (i < nbk && j < nbk && in_tri) v = Vb[(int64_t)i * ld + j];
+        sA[i * (NB + 1) + j] = v;
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // column j of the inverse.  Upper: x_j = 1/a_jj, x_i = -(sum_{k=i+1..j} a_ik x_k) / a_ii for i < j, zero below the diagonal;
+    // lower: x_j = 1/a_jj, x_i = -(sum_{k=j..i-1} a_ik x_k) / a_ii for i > j, zero above it.
+#pragma unroll 1
+    for (int t = 0; t < NB; ++t) {
+        const int i = UPPER ? NB - 1 - t : t;
+        T x = T(0);
+        if (i == j) x = UNIT ? T(1) : T(1) / sA[i * (NB + 1) + i];
+        else if (UPPER ? i < j : i > j) {
+            T s = T(0);
+            if (UPPER) { for (int k = i + 1; k <= j; ++k) s += sA[i * (NB + 1) + k] * sX[k * (NB + 1) + j]; }
+            else       { for (int k = j; k < i; ++k) s += sA[i * (NB + 1) + k] * sX[k * (NB + 1) + j]; }
+            x = UNIT ? -s : -s / sA[i * (NB + 1) + i];
+        }
+        sX[i * (NB + 1) + j] = x;
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    T* out = Vinv + (size_t)b * NB * NB;
+    for (int i = 0; i < NB; ++i) out[i * NB + j] = sX[i * (NB + 1) + j];
+}
+
 // A 64x64 block M (row-major, leading dimension ldm) as registers: thread (i = tid & 63, q = tid >> 6) holds row i, columns
 // [16q, 16q+16) -- 16 contiguous elements, four 16-byte loads.  Rows >= rows_ok / columns >= cols_ok read as zero.
 template <typename T>
@@ -824,8 +867,11 @@ static int launch_trsv_pass(Handle* h, unsigned grid, int64_t n, int nr, const T
 
 // B <- U^-1 L^-1 B for nrhs <= TV_NR per pass (row-major factors R, row-major B); interchanges already applied to B.
 // wide: passes of TC_NR = 64 right-hand sides on the MFMA units (trsm_chain_kernel) instead of TV_NR = 8 on the vector units.
+// trans: R is the row-major image of F^T and B <- L^-T U^-T B.  The lower triangle is then U^T (non-unit) and the upper one L^T (unit);
+// the chain kernels and trsv_sub_kernel meet a triangle's nature only through the inverted diagonal blocks, so nothing but the two
+// inverse kernels differs ("Linv" / "Lsub" below stand for the LOWER triangle, "Uinv" / "Usub" for the UPPER one, whatever they hold).
 template <typename T>
-int launch_trsv_coop(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld, T* B, int64_t ldb, bool wide)
+int launch_trsv_coop(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld, T* B, int64_t ldb, bool wide, bool trans)
 {
     if (n <= 0 || nrhs <= 0) return RFLU_OK;
     const int64_t nb = (n + NB - 1) / NB;
@@ -848,10 +894,15 @@ int launch_trsv_coop(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld,
         h->trsv_tag = 0;
         h->trsv_area = xchg;
     }
-    RFLU_TRY(launch_diag_inv<T>(h, n, R, ld, Linv));
+    if (!trans) RFLU_TRY(launch_diag_inv<T>(h, n, R, ld, Linv));
     {
         ProfScope ps(h, RFLU_K_TRSM, (double)n * NB * NB / 3.0 + 4.0 * (double)n * NB * NB);
-        hipLaunchKernelGGL(triu_inv_kernel<T>, dim3((unsigned)nb), dim3(64), 0, h->stream, (int)n, R, ld, Uinv);
+        if (trans) {
+            hipLaunchKernelGGL((tri_inv_trans_kernel<T, false, false>), dim3((unsigned)nb), dim3(64), 0, h->stream, (int)n, R, ld, Linv);
+            hipLaunchKernelGGL((tri_inv_trans_kernel<T, true, true>), dim3((unsigned)nb), dim3(64), 0, h->stream, (int)n, R, ld, Uinv);
+        } else {
+            hipLaunchKernelGGL(triu_inv_kernel<T>, dim3((unsigned)nb), dim3(64), 0, h->stream, (int)n, R, ld, Uinv);
+        }
         hipLaunchKernelGGL((trsv_sub_kernel<T, false>), dim3((unsigned)nb), dim3(256), 0, h->stream, (int)n, R, ld, Linv, Lsub);
         hipLaunchKernelGGL((trsv_sub_kernel<T, true>), dim3((unsigned)nb), dim3(256), 0, h->stream, (int)n, R, ld, Uinv, Usub);
         RFLU_HIP(hipGetLastError());
@@ -980,7 +1031,7 @@ int launch_trsv_coop(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld,
     return RFLU_OK;
 }
 
-template int launch_trsv_coop<double>(Handle*, int64_t, int64_t, const double*, int64_t, double*, int64_t, bool);
-template int launch_trsv_coop<float>(Handle*, int64_t, int64_t, const float*, int64_t, float*, int64_t, bool);
+template int launch_trsv_coop<double>(Handle*, int64_t, int64_t, const double*, int64_t, double*, int64_t, bool, bool);
+template int launch_trsv_coop<float>(Handle*, int64_t, int64_t, const float*, int64_t, float*, int64_t, bool, bool);
 
 }  // namespace rflu

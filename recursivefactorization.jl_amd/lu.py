@@ -9,7 +9,8 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
     LU(A, ipiv, info), checknonsingular(info) -> SingularException                 :128-129 -> ``LU``, ``SingularException``
     ldiv!(F, B) (stdlib for pivoted LU; the package's own for NotIPIV)             :60-64   -> ``ldiv_``
     NoPivot failures carry a NEGATIVE info on Julia >= 1.11                        :25,250,324 -> ``NOPIVOT_NEGATIVE_INFO``
-    Adjoint/Transpose wrappers                                                     :85-87   -> ``Adjoint`` / ``lu(A.T ...)``
+    Adjoint/Transpose wrappers                                                     :85-87   -> ``Adjoint`` / ``lu(A.T ...)``;
+                                                                                             ``ldiv_(Adjoint(F), B)`` solves A' x = b
 
 Same names, argument meaning and error behaviour; Julia's ``!`` is spelled ``_``.  What differs, deliberately:
   * every Float64/Float32 matrix goes to the HIP path, whatever its size -- ``threshold`` (the reference's
@@ -261,9 +262,15 @@ def ldiv_(F: LU, B, *, handle=None):
     factorization -- and the package's own ``ldiv!`` for ``NotIPIV`` factors (/root/reference/src/lu.jl:60-64; tested at
     test/runtests.jl:21-28, 116-128).  Served by ``rflu_getrs_*`` (interchanges, fused unit-lower TRSM, upper solve).
     Raises ``SingularException`` when ``F.info != 0`` (the solve would divide by an exactly zero pivot).
+
+    ``ldiv_(Adjoint(F), B)`` / ``ldiv_(Transpose(F), B)`` overwrite ``B`` with ``A' \\ B`` (stdlib ``ldiv!(::AdjointFactorization{<:Any,<:LU}, B)``,
+    LAPACK getrs with trans = 'T'), served by ``rflu_getrs_trans_*`` under the same layout rules.
     """
+    trans = ""
     if isinstance(F, Adjoint):
-        raise NotImplementedError("solve with the adjoint factorization is not part of the MI355X path")
+        F, trans = F.parent, "trans_"
+        if isinstance(F, Adjoint):
+            raise TypeError("ldiv! of a doubly wrapped factorization: unwrap it first")
     if F.info != 0:
         raise SingularException(abs(F.info))
     A = F.factors
@@ -290,13 +297,13 @@ def ldiv_(F: LU, B, *, handle=None):
             if B.ndim == 2 and not (B.stride(0) == 1 and B.stride(1) >= n):
                 raise ValueError("B must be column-major like the factors")
             ldb = n if B.ndim == 1 else B.stride(1)
-            h.call(f"rflu_getrs_{sfx}_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), A.stride(1), ip,
+            h.call(f"rflu_getrs_{trans}{sfx}_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), A.stride(1), ip,
                    ctypes.c_void_p(B.data_ptr()), ldb)
         else:                 # row-major factors (rflu_getrf_rm) -> row-major right-hand sides
             if B.ndim == 2 and not (B.stride(1) == 1 and B.stride(0) >= nrhs):
                 raise ValueError("B must be row-major like the factors (unit column stride, row stride >= nrhs)")
             ldb = 1 if B.ndim == 1 else B.stride(0)
-            h.call(f"rflu_getrs_rm_{sfx}_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), A.stride(0), ip,
+            h.call(f"rflu_getrs_{trans}rm_{sfx}_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), A.stride(0), ip,
                    ctypes.c_void_p(B.data_ptr()), ldb)
         return B
     if not (isinstance(B, np.ndarray) and B.dtype == A.dtype and (B.ndim == 1 and B.flags.c_contiguous or B.flags.f_contiguous)):
@@ -305,7 +312,7 @@ def ldiv_(F: LU, B, *, handle=None):
     h = handle or _ffi.default_handle(0)
     h.set_stream(None)
     ipiv = None if nopiv else np.ascontiguousarray(F.ipiv, dtype=np.int64)
-    h.call(f"rflu_getrs_{sfx}", n, nrhs, ctypes.c_void_p(A.ctypes.data), max(n, 1),
+    h.call(f"rflu_getrs_{trans}{sfx}", n, nrhs, ctypes.c_void_p(A.ctypes.data), max(n, 1),
            ctypes.c_void_p(0 if ipiv is None else ipiv.ctypes.data), ctypes.c_void_p(B.ctypes.data), max(n, 1))
     return B
 
