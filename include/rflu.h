@@ -47,7 +47,8 @@ enum rflu_path {
     RFLU_PATH_HIP_RECURSIVE = 1, /* pure Toledo recursion on one stream */
     RFLU_PATH_HIP_BLOCKED = 2,   /* right-looking block columns on one stream (profiling modes, devices without 256 CUs) */
     RFLU_PATH_HIP_LOOKAHEAD = 3, /* block-column lookahead / leaf-wise schedules on CU-masked streams */
-    RFLU_PATH_HIP_ENGINE = 4     /* the leaf-wise chain with every trailing update pulled by the persistent update engine (csrc/engine.hip) */
+    RFLU_PATH_HIP_ENGINE = 4,    /* the leaf-wise chain with every trailing update pulled by the persistent update engine (csrc/engine.hip) */
+    RFLU_PATH_HIP_BATCHED = 5    /* rflu_get{rf,rs}_batched_*: one launch of the batched kernels, one group of threads per matrix (csrc/batched.hip) */
 };
 
 /* kernel classes for the built-in per-kernel timers (rflu_profile_*) */
@@ -158,6 +159,35 @@ int rflu_getrs_trans_rm_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, c
                                 const int64_t* ipiv_dev, double* B_dev, int64_t ldb);
 int rflu_getrs_trans_rm_f32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* R_dev, int64_t ld,
                                 const int64_t* ipiv_dev, float* B_dev, int64_t ldb);
+
+/* ---- BATCHED: `batch` independent small systems in one call (getrfBatched / getrsBatched; the sizes the reference was written
+ * for -- recursion threshold 40, src/lu.jl:90 -- where one matrix cannot occupy a GPU).  Strided, not arrays of pointers:
+ *   - matrix b starts at A_dev + b*strideA; row_major = 0: element (i,j) at [i + j*lda] (lda >= m), row_major = 1: at [i*lda + j]
+ *     (lda >= n); the matrices of a batch must not overlap;
+ *   - ipiv of matrix b at ipiv_dev + b*stride_ipiv (stride_ipiv >= min(m,n)), 1-based and sequential as everywhere in this header;
+ *     ipiv_dev == NULL only with pivot == 0 (NotIPIV); a non-NULL ipiv with pivot == 0 is filled with the identity (src/lu.jl:111-113);
+ *   - info_dev: DEVICE array of `batch` entries, required: 0 or the index of the first exactly-zero pivot of that matrix, positive
+ *     convention.  Per matrix the semantics of _generic_lufact! (src/lu.jl:290-338): strict-'>' argmax from 0 with the lowest row on
+ *     ties, reciprocal-multiply scaling, a zero pivot sets info once and the factorization carries on; pivot == 0 is NoPivot;
+ *   - rflu_getrs_batched_*: F / ipiv as the factorization left them, B (n x nrhs per matrix, matrix b at B_dev + b*strideB) in the
+ *     ORIENTATION OF F: row_major = 0: (i,r) at [i + r*ldb], row_major = 1: at [i*ldb + r]; trans != 0 solves A^T x = b (U^T, L^T, then
+ *     the interchanges undone).  Any nrhs.  A singular matrix yields Inf/NaN in its own right-hand sides only;
+ *   - max(m, n) <= 128 (both element types): ONE launch, a group of 64..256 threads per matrix, the matrix in LDS between its one load
+ *     and its one store; rflu_last_path reports RFLU_PATH_HIP_BATCHED.  Larger matrices: a loop over the single-matrix device path on
+ *     the handle's stream -- there so that the interface has no size cliff; it is correct, NOT fast (a launch chain and a
+ *     synchronisation per matrix), and rflu_last_path reports what the last single factorization reports;
+ *   - batch == 0, m == 0 or n == 0 (nrhs == 0): success, nothing launched.  Negative sizes, lda / strides too small, NULL pointers:
+ *     RFLU_ERR_ARG with a message.  Work goes on the handle's stream and is complete on return. */
+int rflu_getrf_batched_f64_dev(rflu_handle_t handle, int64_t batch, int64_t m, int64_t n, double* A_dev, int64_t lda, int64_t strideA,
+                               int row_major, int64_t* ipiv_dev, int64_t stride_ipiv, int pivot, int64_t* info_dev);
+int rflu_getrf_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t m, int64_t n, float* A_dev, int64_t lda, int64_t strideA,
+                               int row_major, int64_t* ipiv_dev, int64_t stride_ipiv, int pivot, int64_t* info_dev);
+int rflu_getrs_batched_f64_dev(rflu_handle_t handle, int64_t batch, int64_t n, int64_t nrhs, const double* F_dev, int64_t lda,
+                               int64_t strideF, int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, double* B_dev, int64_t ldb,
+                               int64_t strideB, int trans);
+int rflu_getrs_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda,
+                               int64_t strideF, int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* B_dev, int64_t ldb,
+                               int64_t strideB, int trans);
 
 /* ---- building blocks on the INTERNAL row-major layout: element (i,j) at R[i*ld + j] (device pointers).
  * These are the four kernels of the path plus the bookkeeping the multi-GPU block-column driver and the parity

@@ -62,7 +62,7 @@ function available()
     end
 end
 
-"which implementation served the last factorization: 1 recursive, 2 blocked (profiling), 3 lookahead (rflu_path)"
+"which implementation served the last factorization: 1 recursive, 2 blocked (profiling), 3 lookahead, 4 engine, 5 batched (rflu_path)"
 last_path() = Int(ccall((:rflu_last_path, librflu), Cint, (Ptr{Cvoid},), handle()))
 
 normalize_pivot(t::Val{T}) where {T} = t                     # RecursiveFactorization src/lu.jl:10-17
@@ -117,6 +117,56 @@ function getrf_dev!(A::Ptr{Float32}, m::Integer, n::Integer, lda::Integer, ipiv:
                handle(), m, n, A, lda, ipiv, Cint(pivot), blocksize, info)
     st == RFLU_OK || error("librflu: ", last_error())
     return BlasInt(info[])
+end
+
+"""
+    getrf_batched_dev!(A, batch, m, n, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info)
+
+`batch` independent `m x n` matrices that live in HBM, factored in one call (`rflu_getrf_batched_*_dev`, include/rflu.h): matrix `b`
+starts `b*strideA` elements after `A`, its pivots `b*stride_ipiv` entries after `ipiv` (`C_NULL` with `pivot = false` plays NotIPIV);
+`info` is a DEVICE pointer to `batch` entries (0 or the first zero pivot, positive convention -- the caller applies
+`NOPIVOT_NEGATIVE_INFO` and `checknonsingular`).  Up to 128 rows and columns one kernel launch serves the whole batch.
+"""
+function getrf_batched_dev!(A::Ptr{Float64}, batch::Integer, m::Integer, n::Integer, lda::Integer, strideA::Integer, row_major::Bool,
+                            ipiv::Ptr{Int64}, stride_ipiv::Integer, pivot::Bool, info::Ptr{Int64})
+    st = ccall((:rflu_getrf_batched_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Int64}, Int64, Cint, Ptr{Int64}),
+               handle(), batch, m, n, A, lda, strideA, Cint(row_major), ipiv, stride_ipiv, Cint(pivot), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function getrf_batched_dev!(A::Ptr{Float32}, batch::Integer, m::Integer, n::Integer, lda::Integer, strideA::Integer, row_major::Bool,
+                            ipiv::Ptr{Int64}, stride_ipiv::Integer, pivot::Bool, info::Ptr{Int64})
+    st = ccall((:rflu_getrf_batched_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Int64}, Int64, Cint, Ptr{Int64}),
+               handle(), batch, m, n, A, lda, strideA, Cint(row_major), ipiv, stride_ipiv, Cint(pivot), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+"""
+    getrs_batched_dev!(F, batch, n, nrhs, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb, strideB, trans)
+
+The solve that follows `getrf_batched_dev!`: `B` (`n x nrhs` per matrix, in the orientation of `F`, device memory) is overwritten with
+`A \\ B`, or with `A' \\ B` when `trans` is set.  A singular matrix leaves Inf/NaN in its own right-hand sides only.
+"""
+function getrs_batched_dev!(F::Ptr{Float64}, batch::Integer, n::Integer, nrhs::Integer, lda::Integer, strideF::Integer, row_major::Bool,
+                            ipiv::Ptr{Int64}, stride_ipiv::Integer, B::Ptr{Float64}, ldb::Integer, strideB::Integer, trans::Bool)
+    st = ccall((:rflu_getrs_batched_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Int64, Cint),
+               handle(), batch, n, nrhs, F, lda, strideF, Cint(row_major), ipiv, stride_ipiv, B, ldb, strideB, Cint(trans))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+function getrs_batched_dev!(F::Ptr{Float32}, batch::Integer, n::Integer, nrhs::Integer, lda::Integer, strideF::Integer, row_major::Bool,
+                            ipiv::Ptr{Int64}, stride_ipiv::Integer, B::Ptr{Float32}, ldb::Integer, strideB::Integer, trans::Bool)
+    st = ccall((:rflu_getrs_batched_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Int64}, Int64, Ptr{Float32}, Int64, Int64, Cint),
+               handle(), batch, n, nrhs, F, lda, strideF, Cint(row_major), ipiv, stride_ipiv, B, ldb, strideB, Cint(trans))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
 end
 
 "`ldiv!(F, B)` on the GPU: B <- U^-1 L^-1 P B (stdlib `ldiv!(::LU, B)`; the package's own for NotIPIV, src/lu.jl:60-64)"

@@ -43,3 +43,28 @@ end
         end
     end
 end
+# The batched entries take DEVICE pointers, so this block needs AMDGPU.jl for the buffers (not a dependency of the package: skipped
+# when it is not installed).  4096 systems of order 32, packed column-major: pivots and info against LAPACK, the reference's solve bound.
+if Base.find_package("AMDGPU") !== nothing
+    @eval using AMDGPU
+    @testset "RFLUAMD batched getrf / getrs ($T)" for T in (Float64, Float32)
+        n, batch = 32, 4096
+        A = rand(T, n, n, batch); A[:, 5, 7] .= 0              # matrix 7 is singular: info 5, alone
+        b = rand(T, n, batch)
+        dA, dB = ROCArray(A), ROCArray(b)
+        dipiv, dinfo = ROCArray(zeros(Int64, n, batch)), ROCArray(fill(Int64(-1), batch))
+        GC.@preserve dA dB dipiv dinfo begin
+            RFLUAMD.getrf_batched_dev!(Ptr{T}(UInt(pointer(dA))), batch, n, n, n, n * n, false, Ptr{Int64}(UInt(pointer(dipiv))), n, true,
+                                       Ptr{Int64}(UInt(pointer(dinfo))))
+            @test RFLUAMD.last_path() == 5
+            RFLUAMD.getrs_batched_dev!(Ptr{T}(UInt(pointer(dA))), batch, n, 1, n, n * n, false, Ptr{Int64}(UInt(pointer(dipiv))), n,
+                                       Ptr{T}(UInt(pointer(dB))), n, n, false)
+        end
+        ipiv, info, x = Array(dipiv), Array(dinfo), Array(dB)
+        @test info[7] == 5 && count(!iszero, info) == 1
+        for k in (1, 2, 1000, batch)
+            @test ipiv[:, k] == baselu(A[:, :, k]).ipiv
+            @test norm(A[:, :, k] * x[:, k] - b[:, k]) < 1000n * eps(T) * norm(A[:, :, k]) * norm(x[:, k])
+        end
+    end
+end

@@ -7,6 +7,7 @@ every call raises.
 from ._ffi import Handle, RfluError, default_handle  # noqa: F401
 from .lu import (  # noqa: F401
     LU,
+    BatchedLU,
     NOPIVOT_NEGATIVE_INFO,
     Adjoint,
     NoPivot,
@@ -17,8 +18,11 @@ from .lu import (  # noqa: F401
     Val,
     last_path,
     ldiv_,
+    ldiv_batched_,
     lu,
     lu_,
+    lu_batched,
+    lu_batched_,
     normalize_pivot,
 )
 
@@ -34,6 +38,6 @@ from . import linsolve  # noqa: F401,E402  (LinearSolve.jl's RFLUFactorization c
 __all__ = [
     "linsolve",
     "ButterflyWorkspace", "butterfly_workspace", "butterfly_solve_", "butterfly_mul_",
-    "lu", "lu_", "ldiv_", "LU", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
+    "lu", "lu_", "ldiv_", "LU", "lu_batched", "lu_batched_", "ldiv_batched_", "BatchedLU", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

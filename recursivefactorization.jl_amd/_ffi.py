@@ -33,6 +33,8 @@ _TYPED = {
     "rflu_getrs_trans_{s}": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64]),
     "rflu_getrs_trans_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64]),
     "rflu_getrs_trans_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64]),
+    "rflu_getrf_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_int, c_p]),
+    "rflu_getrs_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int]),
     "rflu_panel_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_p]),
     "rflu_laswp_rm_{s}_dev": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64]),
     "rflu_trsm_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64]),
@@ -80,6 +82,7 @@ for _k, _v in _TYPED.items():
 K_GEMM, K_TRSM, K_LASWP, K_PANEL, K_TRANSPOSE, K_MISC = range(6)
 KCLASS_NAMES = ["gemm", "trsm", "laswp", "panel", "transpose", "misc", "gemm_small", "laswp_wide"]
 PATH_NONE, PATH_HIP_RECURSIVE, PATH_HIP_BLOCKED, PATH_HIP_LOOKAHEAD = 0, 1, 2, 3
+PATH_HIP_ENGINE, PATH_HIP_BATCHED = 4, 5
 
 _lib = None
 

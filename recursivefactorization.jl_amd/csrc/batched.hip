@@ -1,0 +1,437 @@
+// batched.hip -- LU and solve for a BATCH of small independent matrices (max(m, n) <= BATCHED_MAX_DIM = 128): the sizes the reference
+// was written for (threshold 40, the reference's src/lu.jl:90; tests up to 300 columns), where one matrix cannot fill a GPU.
+//
+// Shape of both kernels: a GROUP of 64 / 128 / 256 threads (max(m, n) <= 32 / 64 / 128) owns one matrix; a 256-thread workgroup holds
+// 4 / 2 / 1 groups.  The matrix is read from HBM once into LDS (column-major, odd leading dimension: a column AND a row are
+// bank-conflict free), worked on there, and written once.  The matrices never talk to each other: no global-memory hand-off, no
+// cooperative launch, nothing a workgroup could wait for -- one workgroup barrier per pivot column is all the synchronisation there is.
+//
+// Factorization, per matrix the semantics of _generic_lufact! (the reference's src/lu.jl:290-338), as panel_single.hip states them:
+// argmax |a_ik| with strict '>' from 0 and the lowest row on ties (:298-305; a NaN never wins), reciprocal-multiply scaling (:317-320),
+// a zero pivot sets info once and the elimination carries on unscaled (:321-334), NoPivot takes row k.
+//   * thread (r, c) of a group owns row r and every CT-th column; rows are never moved in LDS: a row carries its current POSITION
+//     (interchange by renaming, as in the leaf kernels) and goes to that position in the one store at the end;
+//   * every wave of the group finds the pivot of column k redundantly (two rows per lane, one 64-bit DPP max; the low-position
+//     tie-break only when two lanes hold the same maximum), so no wave waits for another one's search;
+//   * l_ik is written back one step late by the row's first thread: nobody reads column k-1 any more then, and the other threads of
+//     the row still read a_ik while step k runs.  One barrier per column.
+// Solve: factors and 8 right-hand sides in LDS; interchanges as one gather through the composed permutation (built in registers by
+// the group's first wave while the factors arrive), then two column-oriented substitutions with one barrier per column; the
+// transposed solve reads the same LDS image by rows (U^T forward, L^T backward) and scatters through the permutation.
+// Roofline: n dependent steps of {barrier, pivot search, LDS rank-1 update}; only for n <= 16 the one load and one store matter.
+#include <algorithm>
+
+#include "rflu_internal.hpp"
+
+namespace rflu {
+
+namespace {
+
+typedef unsigned long long bu64;
+constexpr int BT = 256;                   // threads per workgroup
+constexpr int BNR = 8;                    // right-hand sides per pass of the solve
+constexpr unsigned BPOS_NONE = 0x7fffffffu;
+
+struct BGeo {
+    int tpm;        // threads per matrix (64 | 128 | 256)
+    int tpm_log;
+    int rt_log;     // log2 of RT = rows of the (row, column-slice) thread grid: the smallest power of two >= m
+    int ct_log;     // log2 of the same for the columns (row-major loads and stores: lanes along a row)
+    int ld;         // LDS leading dimension (odd)
+    unsigned group_bytes;
+    unsigned off_x, off_int;   // byte offsets inside a group's LDS: right-hand sides (solve), integer arrays
+};
+
+int blog2_ceil(int64_t v)
+{
+    int l = 0;
+    while (((int64_t)1 << l) < v) ++l;
+    return l;
+}
+
+BGeo batched_geo(int64_t m, int64_t n, size_t esize, bool solve)
+{
+    BGeo g;
+    const int64_t mx = std::max(m, n);
+    g.tpm_log = mx <= 32 ? 6 : (mx <= 64 ? 7 : 8);
+    g.tpm = 1 << g.tpm_log;
+    g.rt_log = blog2_ceil(m);
+    g.ct_log = blog2_ceil(n);
+    g.ld = (int)(m | 1);
+    size_t off = ((size_t)g.ld * (size_t)n * esize + 15) & ~(size_t)15;
+    g.off_x = (unsigned)off;
+    if (solve) off += ((size_t)g.ld * BNR * esize + 15) & ~(size_t)15;
+    g.off_int = (unsigned)off;
+    off += ((size_t)(m + std::min(m, n)) * sizeof(int) + 15) & ~(size_t)15;
+    g.group_bytes = (unsigned)off;
+    return g;
+}
+
+// |v| as an integer that orders like the magnitude; 0 for zeros and NaN (neither ever beats a candidate: `absi > amax`, lu.jl:301)
+__device__ __forceinline__ bu64 bkey(double v)
+{
+    return (__builtin_fabs(v) > 0.0) ? ((bu64)__double_as_longlong(v) & 0x7fffffffffffffffull) : 0ull;
+}
+__device__ __forceinline__ bu64 bkey(float v)
+{
+    return (__builtin_fabsf(v) > 0.0f) ? (bu64)(__float_as_uint(v) & 0x7fffffffu) : 0ull;
+}
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ bu64 bdpp_max(bu64 v)
+{
+    const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+    const int olo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
+    const int ohi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
+    const bu64 o = ((bu64)(unsigned)ohi << 32) | (bu64)(unsigned)olo;
+    return o > v ? o : v;
+}
+// maximum over the 64 lanes of a wave (all of them active), wave-uniform: the DPP ladder of panel_single.hip on 64-bit keys
+__device__ __forceinline__ bu64 bwave_max(bu64 v)
+{
+    v = bdpp_max<0xB1, 0xf>(v);    // quad_perm:[1,0,3,2]
+    v = bdpp_max<0x4E, 0xf>(v);    // quad_perm:[2,3,0,1]
+    v = bdpp_max<0x141, 0xf>(v);   // row_half_mirror
+    v = bdpp_max<0x140, 0xf>(v);   // row_mirror
+    v = bdpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+    v = bdpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds the maximum
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((bu64)hi << 32) | (bu64)lo;
+}
+
+// ---- the one load and the one store ---------------------------------------------------------------------------------------------
+// element (i, j) of the caller's matrix: G[i + j*lda] (column-major) or G[i*lda + j] (row-major); in LDS always s[i + j*ld].
+// Column-major: lanes along a column (thread grid RT x TPM/RT); row-major: lanes along a row (CT x TPM/CT).  A power-of-two grid:
+// no integer division.  `valid` = false (a group beyond the end of the batch): zeros.
+template <typename T>
+__device__ __forceinline__ void bload_matrix(T* s, int ld, const T* G, int64_t lda, int row_major, int m, int n, const BGeo& g,
+                                             int t, bool valid)
+{
+    if (!row_major) {
+        const int r = t & ((1 << g.rt_log) - 1), c0 = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+        if (r < m)
+            for (int j = c0; j < n; j += cs) s[r + j * ld] = valid ? G[r + (int64_t)j * lda] : T(0);
+    } else {
+        const int c = t & ((1 << g.ct_log) - 1), r0 = t >> g.ct_log, rs = g.tpm >> g.ct_log;
+        if (c < n)
+            for (int i = r0; i < m; i += rs) s[i + c * ld] = valid ? G[(int64_t)i * lda + c] : T(0);
+    }
+}
+
+template <typename T>
+struct BFactorArgs {
+    T* A;
+    int64_t* ipiv;
+    int64_t* info;
+    int64_t lda, strideA, stride_ipiv, batch;
+    int m, n, row_major, pivot;
+    BGeo g;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(BT) getrf_batched_kernel(BFactorArgs<T> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char bsmem[];
+    const BGeo g = a.g;
+    const int m = a.m, n = a.n, mn = m < n ? m : n, ld = g.ld;
+    const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1), lane = t & 63;
+    const int64_t b = (int64_t)blockIdx.x * (BT >> g.tpm_log) + grp;
+    const bool valid = b < a.batch;
+    unsigned char* base = bsmem + (size_t)grp * g.group_bytes;
+    T* s = reinterpret_cast<T*>(base);
+    unsigned* spiv = reinterpret_cast<unsigned*>(base + g.off_int);   // [mn] position the pivot of step k came from
+    unsigned* spos = spiv + mn;                                        // [m]  final position of every row
+    T* G = a.A + (valid ? b : 0) * a.strideA;
+
+    bload_matrix<T>(s, ld, G, a.lda, a.row_major, m, n, g, t, valid);
+
+    // the row this thread updates, and the rows this lane looks at in the pivot search (every wave searches all rows)
+    const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+    bool act = r < m;
+    unsigned mypos = act ? (unsigned)r : BPOS_NONE;
+    unsigned pos0 = lane < m ? (unsigned)lane : BPOS_NONE, pos1 = lane + 64 < m ? (unsigned)(lane + 64) : BPOS_NONE;
+    T lprev = T(0);
+    bool updprev = false;
+    int info = 0;
+
+    for (int k = 0; k < mn; ++k) {
+        __syncthreads();   // elimination k-1 is in LDS (k == 0: the matrix)
+        if (updprev && c == 0) s[r + (k - 1) * ld] = lprev;   // nobody reads column k-1 any more
+        int q = k;             // row (as loaded) that becomes the pivot row
+        unsigned gp = (unsigned)k;   // its current position
+        if (a.pivot) {
+            bu64 key = 0;
+            unsigned pos = BPOS_NONE;
+            int phys = 0;
+            if (pos0 != BPOS_NONE) {
+                key = bkey(s[lane + k * ld]);
+                pos = pos0;
+                phys = lane;
+            }
+            if (pos1 != BPOS_NONE) {
+                const bu64 k1 = bkey(s[lane + 64 + k * ld]);
+                if (pos == BPOS_NONE || k1 > key || (k1 == key && pos1 < pos)) {
+                    key = k1;
+                    pos = pos1;
+                    phys = lane + 64;
+                }
+            }
+            const bu64 mx = bwave_max(key);
+            const bool hit = pos != BPOS_NONE && key == mx;
+            bu64 mask = __ballot(hit);
+            if (__popcll(mask) > 1) {   // exact ties (and columns of zeros / NaN): the lowest position
+                const unsigned pm = ~(unsigned)bwave_max(hit ? (bu64)(~pos) : 0ull);
+                mask = __ballot(hit && pos == pm);
+            }
+            // position k is always among the candidates, so mask != 0
+            const int wl = __builtin_amdgcn_readfirstlane(__ffsll((long long)mask) - 1) & 63;
+            gp = (unsigned)__builtin_amdgcn_readlane((int)pos, wl);
+            q = __builtin_amdgcn_readlane(phys, wl);
+            if (pos0 != BPOS_NONE) pos0 = (lane == q) ? BPOS_NONE : (pos0 == (unsigned)k ? gp : pos0);
+            if (pos1 != BPOS_NONE) pos1 = (lane + 64 == q) ? BPOS_NONE : (pos1 == (unsigned)k ? gp : pos1);
+        }
+        const T piv = s[q + k * ld];
+        const T sc = (piv != T(0)) ? T(1) / piv : T(1);
+        if (t == 0) {
+            spiv[k] = gp;
+            if (piv == T(0) && info == 0) info = k + 1;
+        }
+        updprev = false;
+        if (act) {
+            if (r == q) {
+                act = false;
+                mypos = (unsigned)k;
+            } else {
+                if (mypos == (unsigned)k) mypos = gp;
+                const T l = s[r + k * ld] * sc;
+#pragma unroll 4
+                for (int j = k + 1 + c; j < n; j += cs) s[r + j * ld] -= l * s[q + j * ld];
+                lprev = l;
+                updprev = true;
+            }
+        }
+    }
+    __syncthreads();
+    if (updprev && c == 0) s[r + (mn - 1) * ld] = lprev;
+    if (c == 0 && r < m) spos[r] = mypos;
+    __syncthreads();
+
+    if (!valid) return;
+    if (!a.row_major) {
+        if (r < m)
+            for (int j = c; j < n; j += cs) G[(int64_t)mypos + (int64_t)j * a.lda] = s[r + j * ld];
+    } else {
+        const int cc = t & ((1 << g.ct_log) - 1), r0 = t >> g.ct_log, rs = g.tpm >> g.ct_log;
+        if (cc < n)
+            for (int i = r0; i < m; i += rs) G[(int64_t)spos[i] * a.lda + cc] = s[i + cc * ld];
+    }
+    if (a.ipiv) {
+        int64_t* ip = a.ipiv + b * a.stride_ipiv;
+        for (int k = t; k < mn; k += g.tpm) ip[k] = (int64_t)spiv[k] + 1;
+    }
+    if (t == 0) a.info[b] = (int64_t)info;
+}
+
+template <typename T>
+struct BSolveArgs {
+    const T* F;
+    const int64_t* ipiv;
+    T* B;
+    int64_t lda, strideF, stride_ipiv, ldb, strideB, batch, nrhs;
+    int n, row_major, trans;
+    BGeo g;
+};
+
+// F(i, k) of the triangle being solved: the LDS image by columns, or by rows for the transposed solve
+template <typename T, bool TRANS>
+__device__ __forceinline__ T bf(const T* s, int ld, int i, int k)
+{
+    return TRANS ? s[k + i * ld] : s[i + k * ld];
+}
+
+// x <- op(F)^-1 x on the group's pass of right-hand sides: a unit or non-unit LOWER triangle forward, then the other one backward.
+// Column-oriented: after the barrier of step k every thread reads x_k (for the non-unit triangle it divides for itself; the stored
+// x_k stays undivided until the triangle is done, so nobody reads a value that is being replaced), then takes it out of its own row.
+template <typename T, bool TRANS>
+__device__ __forceinline__ void bsubstitute(const T* s, T* x, int ld, int n, int nr, int r, int c, int cs)
+{
+    constexpr bool UNIT_LOWER = !TRANS;   // L (unit) forward and U backward; transposed: U^T forward and L^T (unit) backward
+    for (int k = 0; k < n; ++k) {
+        if (r > k && r < n) {
+            const T f = bf<T, TRANS>(s, ld, r, k);
+            const T d = UNIT_LOWER ? T(1) : bf<T, TRANS>(s, ld, k, k);
+            for (int j = c; j < nr; j += cs) {
+                const T xk = UNIT_LOWER ? x[k + j * ld] : x[k + j * ld] / d;
+                x[r + j * ld] -= f * xk;
+            }
+        }
+        __syncthreads();
+    }
+    if (!UNIT_LOWER) {
+        if (r < n) {
+            const T d = bf<T, TRANS>(s, ld, r, r);
+            for (int j = c; j < nr; j += cs) x[r + j * ld] /= d;
+        }
+        __syncthreads();
+    }
+    for (int k = n - 1; k >= 0; --k) {
+        if (r < k) {
+            const T f = bf<T, TRANS>(s, ld, r, k);
+            const T d = UNIT_LOWER ? bf<T, TRANS>(s, ld, k, k) : T(1);
+            for (int j = c; j < nr; j += cs) {
+                const T xk = UNIT_LOWER ? x[k + j * ld] / d : x[k + j * ld];
+                x[r + j * ld] -= f * xk;
+            }
+        }
+        __syncthreads();
+    }
+    if (UNIT_LOWER) {
+        if (r < n) {
+            const T d = bf<T, TRANS>(s, ld, r, r);
+            for (int j = c; j < nr; j += cs) x[r + j * ld] /= d;
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(BT) getrs_batched_kernel(BSolveArgs<T> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char bsmem[];
+    const BGeo g = a.g;
+    const int n = a.n, ld = g.ld;
+    const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1), lane = t & 63;
+    const int64_t b = (int64_t)blockIdx.x * (BT >> g.tpm_log) + grp;
+    const bool valid = b < a.batch;
+    unsigned char* base = bsmem + (size_t)grp * g.group_bytes;
+    T* s = reinterpret_cast<T*>(base);
+    T* x = reinterpret_cast<T*>(base + g.off_x);
+    int* sperm = reinterpret_cast<int*>(base + g.off_int);   // [n]: row i of P*B is row sperm[i] of B
+    const int64_t bb = valid ? b : 0;
+    const T* F = a.F + bb * a.strideF;
+    T* B = a.B + bb * a.strideB;
+
+    bload_matrix<T>(s, ld, F, a.lda, a.row_major, n, n, g, t, valid);
+    if (t < 64) {
+        // the interchanges k <-> ipiv[k]-1, k = 0 .. n-1, composed into one permutation: two entries per lane, 2 n readlanes
+        int p0 = lane, p1 = lane + 64, i0 = lane, i1 = lane + 64;
+        if (a.ipiv && valid) {
+            const int64_t* ip = a.ipiv + b * a.stride_ipiv;
+            if (lane < n) i0 = (int)(ip[lane] - 1);
+            if (lane + 64 < n) i1 = (int)(ip[lane + 64] - 1);
+        }
+        if (a.ipiv) {
+            for (int k = 0; k < n; ++k) {
+                const int ku = __builtin_amdgcn_readfirstlane(k);
+                int p = ku < 64 ? __builtin_amdgcn_readlane(i0, ku) : __builtin_amdgcn_readlane(i1, ku - 64);
+                if (p <= ku || p >= n) continue;   // nothing to exchange (or not an interchange getrf could have written)
+                const int vk = ku < 64 ? __builtin_amdgcn_readlane(p0, ku) : __builtin_amdgcn_readlane(p1, ku - 64);
+                const int vp = p < 64 ? __builtin_amdgcn_readlane(p0, p) : __builtin_amdgcn_readlane(p1, p - 64);
+                if (lane == (ku & 63)) { if (ku < 64) p0 = vp; else p1 = vp; }
+                if (lane == (p & 63)) { if (p < 64) p0 = vk; else p1 = vk; }
+            }
+        }
+        if (lane < n) sperm[lane] = p0;
+        if (lane + 64 < n) sperm[lane + 64] = p1;
+    }
+    __syncthreads();
+
+    const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+    const int rr = t & (BNR - 1), ri0 = t >> 3, ris = g.tpm >> 3;   // row-major right-hand sides: lanes along a row of B
+    for (int64_t j0 = 0; j0 < a.nrhs; j0 += BNR) {
+        const int nr = (int)(a.nrhs - j0 < BNR ? a.nrhs - j0 : BNR);
+        // row i of the pass: from row perm[i] of B (forward solve: P B), or row i (transposed: the interchanges come last)
+        if (!a.row_major) {
+            if (r < n) {
+                const int src = a.trans ? r : sperm[r];
+                for (int j = c; j < nr; j += cs) x[r + j * ld] = valid ? B[src + (j0 + j) * a.ldb] : T(0);
+            }
+        } else if (rr < nr) {
+            for (int i = ri0; i < n; i += ris) {
+                const int src = a.trans ? i : sperm[i];
+                x[i + rr * ld] = valid ? B[(int64_t)src * a.ldb + j0 + rr] : T(0);
+            }
+        }
+        __syncthreads();
+        if (a.trans) bsubstitute<T, true>(s, x, ld, n, nr, r, c, cs);
+        else bsubstitute<T, false>(s, x, ld, n, nr, r, c, cs);
+        if (valid) {
+            if (!a.row_major) {
+                if (r < n) {
+                    const int dst = a.trans ? sperm[r] : r;
+                    for (int j = c; j < nr; j += cs) B[dst + (j0 + j) * a.ldb] = x[r + j * ld];
+                }
+            } else if (rr < nr) {
+                for (int i = ri0; i < n; i += ris) {
+                    const int dst = a.trans ? sperm[i] : i;
+                    B[(int64_t)dst * a.ldb + j0 + rr] = x[i + rr * ld];
+                }
+            }
+        }
+        __syncthreads();   // the pass has left LDS before the next one arrives
+    }
+}
+
+template <typename K>
+int batched_lds_attr(bool* done, K kernel, size_t lds)
+{
+    if (lds > 64 * 1024 && !*done) {   // above the default limit a kernel has to ask once (160 KiB per CU on gfx950)
+        RFLU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        *done = true;
+    }
+    return RFLU_OK;
+}
+
+}  // namespace
+
+bool batched_fits(int64_t m, int64_t n) { return std::max(m, n) <= BATCHED_MAX_DIM; }
+
+template <typename T>
+int launch_getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, int64_t lda, int64_t strideA, int row_major,
+                         int64_t* ipiv, int64_t stride_ipiv, int pivot, int64_t* info)
+{
+    BFactorArgs<T> a;
+    a.A = A; a.ipiv = ipiv; a.info = info;
+    a.lda = lda; a.strideA = strideA; a.stride_ipiv = stride_ipiv; a.batch = batch;
+    a.m = (int)m; a.n = (int)n; a.row_major = row_major; a.pivot = pivot;
+    a.g = batched_geo(m, n, sizeof(T), false);
+    const int groups = BT / a.g.tpm;
+    const size_t lds = (size_t)groups * a.g.group_bytes;
+    RFLU_TRY(batched_lds_attr(&h->batched_attr_set[0][sizeof(T) == 4], &getrf_batched_kernel<T>, lds));
+    const int64_t wgs = (batch + groups - 1) / groups;
+    ProfScope ps(h, RFLU_K_PANEL, (double)batch * (double)m * (double)n * (double)std::min(m, n),
+                 2.0 * (double)batch * (double)m * (double)n * sizeof(T));
+    hipLaunchKernelGGL((getrf_batched_kernel<T>), dim3((unsigned)wgs), dim3(BT), lds, h->stream, a);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+template <typename T>
+int launch_getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const T* F, int64_t lda, int64_t strideF, int row_major,
+                         const int64_t* ipiv, int64_t stride_ipiv, T* B, int64_t ldb, int64_t strideB, int trans)
+{
+    BSolveArgs<T> a;
+    a.F = F; a.ipiv = ipiv; a.B = B;
+    a.lda = lda; a.strideF = strideF; a.stride_ipiv = stride_ipiv; a.ldb = ldb; a.strideB = strideB; a.batch = batch; a.nrhs = nrhs;
+    a.n = (int)n; a.row_major = row_major; a.trans = trans;
+    a.g = batched_geo(n, n, sizeof(T), true);
+    const int groups = BT / a.g.tpm;
+    const size_t lds = (size_t)groups * a.g.group_bytes;
+    RFLU_TRY(batched_lds_attr(&h->batched_attr_set[1][sizeof(T) == 4], &getrs_batched_kernel<T>, lds));
+    const int64_t wgs = (batch + groups - 1) / groups;
+    ProfScope ps(h, RFLU_K_TRSM, 2.0 * (double)batch * (double)n * (double)n * (double)nrhs,
+                 (double)batch * ((double)n * (double)n + 2.0 * (double)n * (double)nrhs) * sizeof(T));
+    hipLaunchKernelGGL((getrs_batched_kernel<T>), dim3((unsigned)wgs), dim3(BT), lds, h->stream, a);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+template int launch_getrf_batched<double>(Handle*, int64_t, int64_t, int64_t, double*, int64_t, int64_t, int, int64_t*, int64_t, int, int64_t*);
+template int launch_getrf_batched<float>(Handle*, int64_t, int64_t, int64_t, float*, int64_t, int64_t, int, int64_t*, int64_t, int, int64_t*);
+template int launch_getrs_batched<double>(Handle*, int64_t, int64_t, int64_t, const double*, int64_t, int64_t, int, const int64_t*, int64_t,
+                                          double*, int64_t, int64_t, int);
+template int launch_getrs_batched<float>(Handle*, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, int, const int64_t*, int64_t,
+                                         float*, int64_t, int64_t, int);
+
+}  // namespace rflu

@@ -1589,6 +1589,78 @@ static int getrf_cm_dev(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int6
     return RFLU_OK;
 }
 
+// ---- batched entries (include/rflu.h): `batch` independent matrices, strided.  max(m, n) <= BATCHED_MAX_DIM: one launch of the
+// batched kernels (batched.hip); larger: a loop over the single-matrix device path on the same stream -- correct, not fast, no size cliff.
+template <typename T>
+static int getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, int64_t lda, int64_t strideA, int row_major,
+                         int64_t* ipiv, int64_t stride_ipiv, int pivot, int64_t* info_dev)
+{
+    if (batch < 0 || m < 0 || n < 0) {
+        set_error("getrf_batched: negative size batch=%lld m=%lld n=%lld", (long long)batch, (long long)m, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0 || m == 0 || n == 0) return RFLU_OK;
+    const int64_t mn = std::min(m, n), rows = row_major ? n : m, cols = row_major ? m : n;   // rows = the contiguous dimension
+    if (A == nullptr || info_dev == nullptr) { set_error("getrf_batched: null matrix or info pointer"); return RFLU_ERR_ARG; }
+    if (pivot && ipiv == nullptr) { set_error("getrf_batched: pivot != 0 needs an ipiv buffer"); return RFLU_ERR_ARG; }
+    if (lda < rows || (batch > 1 && strideA < (cols - 1) * lda + rows)) {
+        set_error("getrf_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", (long long)lda, (long long)strideA, (long long)m,
+                  (long long)n, row_major ? "row-major" : "column-major");
+        return RFLU_ERR_ARG;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < mn) { set_error("getrf_batched: stride_ipiv=%lld < min(m, n)", (long long)stride_ipiv); return RFLU_ERR_ARG; }
+    if (batched_fits(m, n)) {
+        RFLU_TRY(launch_getrf_batched<T>(h, batch, m, n, A, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info_dev));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        h->last_path = RFLU_PATH_HIP_BATCHED;
+        return RFLU_OK;
+    }
+    std::vector<int64_t> infos((size_t)batch, 0);
+    for (int64_t b = 0; b < batch; ++b) {
+        T* Ab = A + b * strideA;
+        int64_t* ip = ipiv ? ipiv + b * stride_ipiv : nullptr;
+        if (row_major) RFLU_TRY(getrf_rm<T>(h, m, n, Ab, lda, ip, pivot, 0, &infos[(size_t)b]));
+        else RFLU_TRY(getrf_cm_dev<T>(h, m, n, Ab, lda, ip, pivot, 0, &infos[(size_t)b]));
+    }
+    RFLU_HIP(hipMemcpyAsync(info_dev, infos.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+template <typename T>
+static int getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const T* F, int64_t lda, int64_t strideF, int row_major,
+                         const int64_t* ipiv, int64_t stride_ipiv, T* B, int64_t ldb, int64_t strideB, int trans)
+{
+    if (batch < 0 || n < 0 || nrhs < 0) {
+        set_error("getrs_batched: negative size batch=%lld n=%lld nrhs=%lld", (long long)batch, (long long)n, (long long)nrhs);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0 || n == 0 || nrhs == 0) return RFLU_OK;
+    if (F == nullptr || B == nullptr) { set_error("getrs_batched: null pointer"); return RFLU_ERR_ARG; }
+    const int64_t brows = row_major ? nrhs : n, bcols = row_major ? n : nrhs;   // brows = the contiguous dimension of B
+    if (lda < n || ldb < brows || (batch > 1 && (strideF < (n - 1) * lda + n || strideB < (bcols - 1) * ldb + brows))) {
+        set_error("getrs_batched: lda=%lld strideF=%lld ldb=%lld strideB=%lld too small for n=%lld nrhs=%lld (%s)", (long long)lda,
+                  (long long)strideF, (long long)ldb, (long long)strideB, (long long)n, (long long)nrhs, row_major ? "row-major" : "column-major");
+        return RFLU_ERR_ARG;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("getrs_batched: stride_ipiv=%lld < n", (long long)stride_ipiv); return RFLU_ERR_ARG; }
+    if (batched_fits(n, n)) {
+        RFLU_TRY(launch_getrs_batched<T>(h, batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb, strideB, trans ? 1 : 0));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        h->last_path = RFLU_PATH_HIP_BATCHED;
+        return RFLU_OK;
+    }
+    for (int64_t b = 0; b < batch; ++b) {
+        const T* Fb = F + b * strideF;
+        const int64_t* ip = ipiv ? ipiv + b * stride_ipiv : nullptr;
+        T* Bb = B + b * strideB;
+        if (row_major) RFLU_TRY(trans ? getrs_trans_rm<T>(h, n, nrhs, Fb, lda, ip, Bb, ldb) : getrs_rm<T>(h, n, nrhs, Fb, lda, ip, Bb, ldb));
+        else RFLU_TRY(trans ? getrs_trans_cm_dev<T>(h, n, nrhs, Fb, lda, ip, Bb, ldb) : getrs_cm_dev<T>(h, n, nrhs, Fb, lda, ip, Bb, ldb));
+    }
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 // ---- host entry through the update engine: the way in overlaps the factorization (round 5) -----------------------------------------
 // The reference's boundary is a host array (src/lu.jl:116-121).  Round 3 overlapped the way BACK with the factorization; the way in
 // (38 ms of PCIe for a 16384^2 Float64 matrix) still preceded everything, because the stream schedules' first update touches every
@@ -2045,7 +2117,7 @@ struct DeviceGuard {
 
 extern "C" {
 
-int rflu_version(void) { return 101; }
+int rflu_version(void) { return 102; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -2356,6 +2428,21 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
         CHECK_HANDLE(handle);                                                                                         \
         if (n > 0 && nrhs > 0 && (X == nullptr || uv == nullptr)) { set_error("butterfly: null pointer"); return RFLU_ERR_ARG; } \
         return launch_butterfly_vec<T>(H(handle), n, nrhs, X, ldx, uv, transpose_u ? 0 : 1);                          \
+    }                                                                                                                 \
+    int rflu_getrf_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t m, int64_t n, T* A, int64_t lda,  \
+                                       int64_t strideA, int row_major, int64_t* ipiv, int64_t stride_ipiv, int pivot,  \
+                                       int64_t* info_dev)                                                              \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getrf_batched<T>(H(handle), batch, m, n, A, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info_dev); \
+    }                                                                                                                 \
+    int rflu_getrs_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, int64_t nrhs, const T* F,      \
+                                       int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,              \
+                                       int64_t stride_ipiv, T* B, int64_t ldb, int64_t strideB, int trans)            \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getrs_batched<T>(H(handle), batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb,     \
+                                strideB, trans);                                                                      \
     }                                                                                                                 \
     int rflu_fill_uniform_##SFX##_dev(rflu_handle_t handle, T* A, int64_t m, int64_t n, int64_t ld, int row_major,    \
                                       uint64_t seed, int64_t M_global, int64_t i0, int64_t j0, double diag_add)       \

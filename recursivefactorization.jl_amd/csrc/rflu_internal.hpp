@@ -223,6 +223,7 @@ struct Handle {
     bool la_attr_set[2] = {false, false};     // dynamic-LDS opt-in of leaf_la_kernel (f64, f32)
     bool gemm_attr_set[2] = {false, false};   // dynamic-LDS opt-in of the GEMM kernels done on this handle's device (f64, f32)
     bool eng_attr_set[2] = {false, false};    // same for the persistent update engine (engine.hip)
+    bool batched_attr_set[2][2] = {};         // same for the batched kernels (batched.hip): [factorization|solve][Float64|Float32]
     void* eng_state = nullptr;                // device: EngState (engine.hpp)
     void* eng_host = nullptr;                 // pinned host image of its initial value
     long long* eng_trace_buf = nullptr;       // device: RFLU_ENGINE_TRACE stamps + workgroup-time accounting (measurement only)
@@ -386,5 +387,16 @@ template <typename T>
 int launch_butterfly_mul(Handle* h, int64_t n, T* A, int64_t lda, const T* uv);
 template <typename T>
 int launch_butterfly_vec(Handle* h, int64_t n, int64_t nrhs, T* X, int64_t ldx, const T* uv, int mode);
+// batched.hip: `batch` independent matrices of max(m, n) <= BATCHED_MAX_DIM, one group of threads each, everything between the one
+// load and the one store in LDS.  Matrix b at A + b*strideA, element (i, j) at [i + j*lda] or (row_major) [i*lda + j]; info: DEVICE
+// array of `batch` entries.  The solve: B in the orientation of F, any nrhs in passes of 8, trans = B <- A^-T B.
+constexpr int64_t BATCHED_MAX_DIM = 128;
+bool batched_fits(int64_t m, int64_t n);
+template <typename T>
+int launch_getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, int64_t lda, int64_t strideA, int row_major,
+                         int64_t* ipiv, int64_t stride_ipiv, int pivot, int64_t* info);
+template <typename T>
+int launch_getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const T* F, int64_t lda, int64_t strideF, int row_major,
+                         const int64_t* ipiv, int64_t stride_ipiv, T* B, int64_t ldb, int64_t strideB, int trans);
 
 }  // namespace rflu

@@ -8,6 +8,8 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
     NotIPIV (lazy identity pivots for NoPivot)                                     :27-40   -> ``NotIPIV``
     LU(A, ipiv, info), checknonsingular(info) -> SingularException                 :128-129 -> ``LU``, ``SingularException``
     ldiv!(F, B) (stdlib for pivoted LU; the package's own for NotIPIV)             :60-64   -> ``ldiv_``
+    (no counterpart: many small systems at once, getrfBatched / getrsBatched)               -> ``lu_batched_`` / ``lu_batched`` /
+                                                                                             ``ldiv_batched_`` / ``BatchedLU``
     NoPivot failures carry a NEGATIVE info on Julia >= 1.11                        :25,250,324 -> ``NOPIVOT_NEGATIVE_INFO``
     Adjoint/Transpose wrappers                                                     :85-87   -> ``Adjoint`` / ``lu(A.T ...)``;
                                                                                              ``ldiv_(Adjoint(F), B)`` solves A' x = b
@@ -40,9 +42,11 @@ NOPIVOT_NEGATIVE_INFO = True  # the convention of Julia >= 1.11 (src/lu.jl:25)
 class SingularException(ArithmeticError):
     """LinearAlgebra.SingularException(info): raised by ``check`` when a pivot is exactly zero (src/lu.jl:128)."""
 
-    def __init__(self, info: int):
-        super().__init__(f"matrix is singular to working precision (info = {info})")
+    def __init__(self, info: int, batch_index: int | None = None):
+        where = "" if batch_index is None else f", matrix {batch_index} of the batch"
+        super().__init__(f"matrix is singular to working precision (info = {info}{where})")
         self.info = info
+        self.batch_index = batch_index   # lu_batched_ / ldiv_batched_: 0-based index of the first failing matrix; None elsewhere
 
 
 class RowMaximum:
@@ -317,7 +321,146 @@ def ldiv_(F: LU, B, *, handle=None):
     return B
 
 
+@dataclass
+class BatchedLU:
+    """``batch`` factorizations in one object: ``factors`` (batch, m, n) aliasing the caller's tensor, ``ipiv`` (batch, min(m, n))
+    int64 on the device, 1-based (``NotIPIV`` for NoPivot without a pivot buffer), ``info`` int64 CUDA tensor of length ``batch``
+    (0 or the first zero pivot of that matrix; negative for NoPivot under ``NOPIVOT_NEGATIVE_INFO``, as ``lu_`` reports it)."""
+
+    factors: object
+    ipiv: object
+    info: object
+
+    def issuccess(self) -> bool:
+        return not bool((self.info != 0).any().item())
+
+
+def _batched_layout(A, what: str):
+    """(row_major, ld, batch stride) of a (batch, r, c) tensor whose matrices are dense column-major or row-major and do not overlap."""
+    b, r, c = (int(x) for x in A.shape)
+    s0, s1, s2 = (int(x) for x in A.stride())
+    if s1 == 1 and (s2 >= max(r, 1) or c <= 1):
+        row_major, ld, span = 0, (s2 if c > 1 else max(r, 1)), (c - 1) * (s2 if c > 1 else 0) + r
+    elif s2 == 1 and (s1 >= max(c, 1) or r <= 1):
+        row_major, ld, span = 1, (s1 if r > 1 else max(c, 1)), (r - 1) * (s1 if r > 1 else 0) + c
+    else:
+        raise ValueError(f"{what}: every matrix must be dense column-major (stride(1) == 1) or row-major (stride(2) == 1)")
+    if b > 1 and r > 0 and c > 0 and s0 < span:
+        raise ValueError(f"{what}: the matrices of the batch overlap (batch stride {s0} < {span})")
+    return row_major, ld, (s0 if b > 1 else max(span, 1))
+
+
+def _check_batched_info(info_t, piv: bool):
+    bad = (info_t != 0).nonzero()
+    if bad.numel():
+        i = int(bad[0, 0].item())
+        raise SingularException(abs(int(info_t[i].item())), i)
+
+
+def lu_batched_(A, ipiv=None, pivot=True, *, check=True, handle=None) -> BatchedLU:
+    """``lu!`` on every matrix of a batch at once: ``A`` is a 3-D CUDA tensor (batch, m, n) whose matrices are dense column-major
+    (``stride(1) == 1``, e.g. a C-contiguous (batch, n, m) tensor seen through ``.transpose(1, 2)``) or row-major (``stride(2) == 1``),
+    at any batch stride that keeps them apart; factored in place by ``rflu_getrf_batched_*_dev``.  Up to 128 rows and columns the whole
+    batch is ONE kernel launch (``last_path() == "hip-batched"``); larger matrices are looped over the single-matrix path.
+
+    ``ipiv``: None -> allocated, (batch, min(m, n)) int64 (``NotIPIV`` for NoPivot); or a CUDA int64 tensor of that shape with unit
+    stride along a row -- with NoPivot it comes back filled with the identity (src/lu.jl:111-113).  ``check=True`` copies ``info``
+    back and raises ``SingularException`` with the first failing matrix's ``info`` and its index in ``batch_index``."""
+    piv = normalize_pivot(pivot)
+    if not _is_torch(A):
+        raise TypeError("lu_batched_ works on CUDA torch tensors (the batch lives in HBM)")
+    if A.ndim != 3:
+        raise ValueError("lu_batched_ needs a 3-D tensor (batch, m, n)")
+    import torch
+
+    if not A.is_cuda:
+        raise TypeError("lu_batched_: the batch must live on the MI355X (device='cuda')")
+    sfx = _sfx(A.dtype)
+    batch, m, n = (int(x) for x in A.shape)
+    mn = min(m, n)
+    row_major, ld, stride_a = _batched_layout(A, "lu_batched_")
+    if ipiv is None:
+        ipiv_t = torch.empty((batch, mn), dtype=torch.int64, device=A.device) if piv else None
+    else:
+        ipiv_t = ipiv
+        if not (_is_torch(ipiv_t) and ipiv_t.is_cuda and ipiv_t.dtype == torch.int64):
+            raise TypeError("ipiv for a batch must be an int64 CUDA tensor")
+        if ipiv_t.ndim != 2 or ipiv_t.shape[0] != batch or ipiv_t.shape[1] != mn:
+            raise ValueError(f"ipiv must have shape (batch, min(m, n)) = ({batch}, {mn})")
+        if mn > 1 and ipiv_t.stride(1) != 1 or batch > 1 and ipiv_t.stride(0) < mn:
+            raise ValueError("ipiv: unit stride along a row and a batch stride of at least min(m, n)")
+    stride_ip = 0 if ipiv_t is None else (int(ipiv_t.stride(0)) if batch > 1 else max(mn, 1))
+    info_t = torch.zeros(batch, dtype=torch.int64, device=A.device)
+    if batch > 0 and m > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        h.call(f"rflu_getrf_batched_{sfx}_dev", batch, m, n, ctypes.c_void_p(A.data_ptr()), ld, stride_a, row_major,
+               ctypes.c_void_p(ipiv_t.data_ptr() if ipiv_t is not None else 0), stride_ip, int(piv), ctypes.c_void_p(info_t.data_ptr()))
+    if not piv and NOPIVOT_NEGATIVE_INFO:
+        info_t = -info_t
+    if _as_bool(check):
+        _check_batched_info(info_t, piv)
+    return BatchedLU(A, ipiv_t if ipiv_t is not None else NotIPIV(mn), info_t)
+
+
+def lu_batched(A, pivot=True, **kwargs) -> BatchedLU:
+    """``lu`` on every matrix of a batch: ``lu_batched_`` on a copy that keeps the layout of ``A``'s matrices."""
+    if not _is_torch(A) or A.ndim != 3:
+        raise ValueError("lu_batched needs a 3-D CUDA tensor (batch, m, n)")
+    C = A.transpose(1, 2).contiguous().transpose(1, 2) if (A.stride(1) == 1 and A.shape[2] > 1) else A.contiguous()
+    if C.data_ptr() == A.data_ptr():
+        C = C.clone()
+    return lu_batched_(C, None, pivot, **kwargs)
+
+
+def ldiv_batched_(F, B, *, trans=False, check=True, handle=None):
+    """``ldiv!`` on every system of a batch: overwrite ``B`` -- (batch, n) or (batch, n, nrhs), in the orientation of the factors --
+    with ``A_b \\ B_b``, or with ``A_b' \\ B_b`` for ``trans=True`` / ``Adjoint(F)``.  Served by ``rflu_getrs_batched_*_dev`` (one launch
+    up to n = 128).  ``check=True`` raises ``SingularException`` (with ``batch_index``) when some ``F.info`` is non-zero; with
+    ``check=False`` the solve runs and only the singular matrices' own right-hand sides come back non-finite."""
+    if isinstance(F, Adjoint):
+        F, trans = F.parent, not trans
+        if isinstance(F, Adjoint):
+            raise TypeError("ldiv! of a doubly wrapped factorization: unwrap it first")
+    if not isinstance(F, BatchedLU):
+        raise TypeError("ldiv_batched_ needs the BatchedLU that lu_batched_ returned")
+    A = F.factors
+    import torch
+
+    batch, m, n = (int(x) for x in A.shape)
+    if m != n:
+        raise ValueError("ldiv! needs square factorizations")
+    if not (_is_torch(B) and B.is_cuda and B.dtype == A.dtype):
+        raise TypeError("B must be a CUDA tensor of the factorization's dtype")
+    if B.ndim not in (2, 3) or B.shape[0] != batch or B.shape[1] != n:
+        raise ValueError(f"B must have shape (batch, n) or (batch, n, nrhs) with batch = {batch}, n = {n}")
+    row_major, ld, stride_f = _batched_layout(A, "ldiv_batched_")
+    nrhs = 1 if B.ndim == 2 else int(B.shape[2])
+    if B.ndim == 2:
+        if n > 1 and B.stride(1) != 1 or batch > 1 and B.stride(0) < n:
+            raise ValueError("a batch of vectors must have unit stride along a vector and a batch stride of at least n")
+        ldb, stride_b = (n if not row_major else 1), (int(B.stride(0)) if batch > 1 else max(n, 1))
+    else:
+        b_rm, ldb, stride_b = _batched_layout(B, "ldiv_batched_ (B)")
+        if b_rm != row_major and n > 1 and nrhs > 1:
+            raise ValueError("B must have the orientation of the factors (column-major with column-major, row-major with row-major)")
+        if b_rm != row_major:   # a single row or column fits both readings: take the factors'
+            ldb = max(nrhs, 1) if row_major else max(n, 1)
+    if _as_bool(check):
+        _check_batched_info(F.info, True)
+    if batch > 0 and n > 0 and nrhs > 0:
+        sfx = _sfx(A.dtype)
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        nopiv = isinstance(F.ipiv, NotIPIV)
+        stride_ip = 0 if nopiv else (int(F.ipiv.stride(0)) if batch > 1 else max(n, 1))
+        h.call(f"rflu_getrs_batched_{sfx}_dev", batch, n, nrhs, ctypes.c_void_p(A.data_ptr()), ld, stride_f, row_major,
+               ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), stride_ip, ctypes.c_void_p(B.data_ptr()), ldb, stride_b, int(bool(trans)))
+    return B
+
+
 def last_path(device: int = 0) -> str:
     """Which implementation served the last factorization on ``device`` (``enum rflu_path`` of include/rflu.h: "hip-recursive" /
-    "hip-blocked" / "hip-lookahead" / "hip-engine" / "none")."""
-    return {0: "none", 1: "hip-recursive", 2: "hip-blocked", 3: "hip-lookahead", 4: "hip-engine"}[_ffi.default_handle(device).last_path()]
+    "hip-blocked" / "hip-lookahead" / "hip-engine" / "hip-batched" / "none")."""
+    return {0: "none", 1: "hip-recursive", 2: "hip-blocked", 3: "hip-lookahead", 4: "hip-engine",
+            5: "hip-batched"}[_ffi.default_handle(device).last_path()]
