@@ -189,6 +189,29 @@ int rflu_getrs_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, i
                                int64_t strideF, int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* B_dev, int64_t ldb,
                                int64_t strideB, int trans);
 
+/* ---- MIXED PRECISION: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme) ----
+ * The Float32 factorization is the faster one; refinement with Float64 residuals r = b - A x brings the solution to Float64 backward
+ * error when A is not too ill-conditioned for its Float32 factors (kappa well below 1 / eps32), and says so when it does not.
+ * Float32 factors of a Float64 matrix.  A (column-major, lda >= n) is only read.  F32_dev: caller-owned n x n ROW-MAJOR
+ * (ldf >= n, the layout and rules of rflu_getrf_rm_f32_dev), receives L\U.  ipiv / pivot / blocksize / info as in
+ * rflu_getrf_rm_f32_dev (info = first exactly-zero pivot OF THE FLOAT32 FACTORIZATION).  *anorm_out (host, required) = ||A||_inf,
+ * bit-identical from run to run. */
+int rflu_mixed_getrf_f64_dev(rflu_handle_t handle, int64_t n, const double* A_dev, int64_t lda, float* F32_dev, int64_t ldf,
+                             int64_t* ipiv_dev, int pivot, int64_t blocksize, double* anorm_out, int64_t* info);
+/* X <- A^-1 B to Float64 backward error by iterative refinement.  A, B are only read; X (n x nrhs, ldx) is written.
+ * Converged when for every column k  ||r_k||_inf <= ||x_k||_inf * anorm * eps64 * sqrt(n)  (a NaN or Inf anywhere is NOT convergence).
+ * *iters (host, required): >= 0 = refinement steps taken, converged; < 0 = -(steps taken + 1), NOT converged within max_iter
+ * (<= 0 means 30), X is then the last iterate and must not be used.  Return value is RFLU_OK in both cases: the library has no
+ * Float64 fallback inside, the host glue decides.  n == 0 or nrhs == 0: success, *iters = 0, nothing launched.  The Float32 factors
+ * are used as they lie (no n x n layout change per solve); the residual of up to RFLU_MIXED_GEMV_MAX_RHS right-hand sides streams A
+ * once per 8 of them, more go through the Float64 GEMM.  Work goes on the handle's stream and is complete on return. */
+int rflu_mixed_getrs_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const float* F32_dev,
+                             int64_t ldf, const int64_t* ipiv_dev, double anorm, const double* B_dev, int64_t ldb, double* X_dev,
+                             int64_t ldx, int max_iter, int* iters);
+/* building block: R <- B - A X, all column-major Float64, A n x n (R must not overlap A, X or B).  Bit-identical from run to run. */
+int rflu_residual_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const double* X_dev,
+                          int64_t ldx, const double* B_dev, int64_t ldb, double* R_dev, int64_t ldr);
+
 /* ---- building blocks on the INTERNAL row-major layout: element (i,j) at R[i*ld + j] (device pointers).
  * These are the four kernels of the path plus the bookkeeping the multi-GPU block-column driver and the parity
  * tests need.  Pivot rows are GLOBAL 0-based row positions r0.. of the slab; ipiv entries are 1-based rows.

@@ -23,7 +23,7 @@ using LinearAlgebra
 using LinearAlgebra: BlasInt, LU, RowMaximum, NoPivot, checknonsingular
 using Libdl
 
-export RFLUAMDFactorization
+export RFLUAMDFactorization, RF32MixedLUAMDFactorization
 
 const librflu = get(ENV, "RFLU_LIB", "librflu.so")
 const HANDLE = Ref{Ptr{Cvoid}}(C_NULL)
@@ -305,5 +305,110 @@ struct RFLUAMDFactorization{P}
     RFLUAMDFactorization(::Val{P}, blocksize::Integer = 0) where {P} = new{P}(Int(blocksize))
 end
 RFLUAMDFactorization(; pivot = Val(true), blocksize::Integer = 0) = RFLUAMDFactorization(normalize_pivot(pivot), blocksize)
+
+# ---- mixed precision: Float32 factors of a Float64 matrix + Float64 iterative refinement (rflu_mixed_*_f64_dev, include/rflu.h) ----
+# Device pointers, like the batched entries: the matrix stays in HBM (the buffer of an AMDGPU.jl ROCArray) and is only read.
+"raw entry: Float32 row-major factors of the column-major Float64 `A` into `F32` (ldf >= n); returns `(info, anorm)`"
+function mixed_getrf_dev!(A::Ptr{Float64}, n::Integer, lda::Integer, F32::Ptr{Float32}, ldf::Integer, ipiv::Ptr{Int64}, pivot::Bool,
+                          blocksize::Integer)
+    info = Ref{Int64}(0)
+    anorm = Ref{Float64}(0.0)
+    st = GC.@preserve anorm ccall((:rflu_mixed_getrf_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Cint, Int64, Ptr{Float64}, Ref{Int64}),
+               handle(), n, A, lda, F32, ldf, ipiv, Cint(pivot), blocksize, Base.unsafe_convert(Ptr{Float64}, anorm), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return BlasInt(info[]), anorm[]
+end
+
+"raw entry: `X <- A \\ B` by refinement; returns `iters` (>= 0 converged after that many steps, < 0 not converged: do not use `X`)"
+function mixed_getrs_dev!(A::Ptr{Float64}, n::Integer, nrhs::Integer, lda::Integer, F32::Ptr{Float32}, ldf::Integer, ipiv::Ptr{Int64},
+                          anorm::Float64, B::Ptr{Float64}, ldb::Integer, X::Ptr{Float64}, ldx::Integer, max_iter::Integer)
+    iters = Ref{Cint}(0)
+    st = GC.@preserve iters ccall((:rflu_mixed_getrs_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Cdouble, Ptr{Float64}, Int64, Ptr{Float64},
+                Int64, Cint, Ptr{Cint}),
+               handle(), n, nrhs, A, lda, F32, ldf, ipiv, anorm, B, ldb, X, ldx, Cint(max_iter), Base.unsafe_convert(Ptr{Cint}, iters))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return Int(iters[])
+end
+
+"raw entry: `R <- B - A X` in Float64, everything column-major in HBM"
+function residual_dev!(R::Ptr{Float64}, ldr::Integer, A::Ptr{Float64}, n::Integer, nrhs::Integer, lda::Integer, X::Ptr{Float64},
+                       ldx::Integer, B::Ptr{Float64}, ldb::Integer)
+    st = ccall((:rflu_residual_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+               handle(), n, nrhs, A, lda, X, ldx, B, ldb, R, ldr)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return R
+end
+
+"""
+    MixedLU
+
+What `lu_mixed` returns: the untouched Float64 matrix `A` (device pointer, `n`, `lda`), its Float32 factors `F32` (row-major, `ldf`),
+`ipiv` (`C_NULL` = NotIPIV), `info` of the Float32 factorization, `anorm = ||A||_inf` and the `iters` of the last `ldiv_mixed!`.
+The caller owns every buffer and keeps it alive.
+"""
+mutable struct MixedLU
+    A::Ptr{Float64}
+    n::Int
+    lda::Int
+    F32::Ptr{Float32}
+    ldf::Int
+    ipiv::Ptr{Int64}
+    info::BlasInt
+    anorm::Float64
+    iters::Int
+end
+
+"""
+    lu_mixed(A, n, lda, F32, ldf, ipiv, pivot = Val(true); blocksize = 0) -> MixedLU
+
+Factor a Float32 copy of the `n x n` column-major Float64 matrix at the device pointer `A` into the caller's `F32` (`n x ldf` Float32,
+row-major) and `ipiv` (`n` Int64; `C_NULL` with `Val(false)`).  `A` is not modified.  A zero pivot of the Float32 factorization is
+reported in `info` (negative for NoPivot under `NOPIVOT_NEGATIVE_INFO`), never thrown: the caller falls back to `lu!` in Float64.
+"""
+function lu_mixed(A::Ptr{Float64}, n::Integer, lda::Integer, F32::Ptr{Float32}, ldf::Integer, ipiv::Ptr{Int64}, pivot = Val(true);
+                  blocksize::Integer = 0)
+    pivot = normalize_pivot(pivot)
+    info, anorm = mixed_getrf_dev!(A, n, lda, F32, ldf, ipiv, pivot === Val(true), blocksize)
+    (pivot === Val(false) && NOPIVOT_NEGATIVE_INFO) && (info = -info)
+    return MixedLU(A, Int(n), Int(lda), F32, Int(ldf), ipiv, info, anorm, 0)
+end
+
+"""
+    ldiv_mixed!(X, ldx, F::MixedLU, B, ldb, nrhs; max_iter = 30) -> Bool
+
+`X <- A \\ B` (device pointers, column-major) by Float32 solves and Float64 residuals.  `true`: converged, `F.iters` steps were taken.
+`false`: the Float32 factorization hit a zero pivot or the refinement did not converge within `max_iter` steps (`F.iters < 0`);
+`X` must not be used and the caller solves with the Float64 factorization instead (the LinearSolve extension does).
+"""
+function ldiv_mixed!(X::Ptr{Float64}, ldx::Integer, F::MixedLU, B::Ptr{Float64}, ldb::Integer, nrhs::Integer; max_iter::Integer = 30)
+    F.info == 0 || return false
+    F.iters = mixed_getrs_dev!(F.A, F.n, nrhs, F.lda, F.F32, F.ldf, F.ipiv, F.anorm, B, ldb, X, ldx, max_iter)
+    return F.iters >= 0
+end
+
+"""
+    device_pointer(x) -> Ptr
+
+The HBM address of a device array.  RFLUAMD does not depend on a GPU array package: the package that owns the array type adds the
+method (for AMDGPU.jl: `RFLUAMD.device_pointer(x::ROCArray{T}) where {T} = Ptr{T}(UInt(pointer(x)))`).
+"""
+function device_pointer end
+
+"""
+    RF32MixedLUAMDFactorization(; pivot = Val(true), blocksize = 0, max_iter = 30)
+
+LinearSolve.jl algorithm in the place of `RF32MixedLUFactorization`: Float32 factors, Float64 refinement, `cache.A` is NOT overwritten.
+Serves device arrays (see `device_pointer`).  `ReturnCode.Failure` only when the Float64 fallback is singular as well.
+"""
+struct RF32MixedLUAMDFactorization{P}
+    blocksize::Int
+    max_iter::Int
+    RF32MixedLUAMDFactorization(::Val{P}, blocksize::Integer = 0, max_iter::Integer = 30) where {P} = new{P}(Int(blocksize), Int(max_iter))
+end
+RF32MixedLUAMDFactorization(; pivot = Val(true), blocksize::Integer = 0, max_iter::Integer = 30) =
+    RF32MixedLUAMDFactorization(normalize_pivot(pivot), blocksize, max_iter)
 
 end # module

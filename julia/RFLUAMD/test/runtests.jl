@@ -67,4 +67,24 @@ if Base.find_package("AMDGPU") !== nothing
             @test norm(A[:, :, k] * x[:, k] - b[:, k]) < 1000n * eps(T) * norm(A[:, :, k]) * norm(x[:, k])
         end
     end
+    # mixed precision: Float32 factors, Float64 refinement; A and b untouched, dsgesv's rule met, the residual kernel alone
+    @testset "RFLUAMD mixed-precision solve" begin
+        n, nrhs = 1000, 9
+        A, B = rand(n, n), rand(n, nrhs)
+        dA, dB, dX, dR = ROCArray(A), ROCArray(B), ROCArray(zeros(n, nrhs)), ROCArray(zeros(n, nrhs))
+        dF, dipiv = ROCArray(zeros(Float32, n, n)), ROCArray(zeros(Int64, n))
+        p(x::ROCArray{T}) where {T} = Ptr{T}(UInt(pointer(x)))
+        GC.@preserve dA dB dX dR dF dipiv begin
+            F = RFLUAMD.lu_mixed(p(dA), n, n, p(dF), n, p(dipiv))
+            @test F.info == 0 && F.anorm == maximum(sum(abs, A; dims = 2))
+            @test RFLUAMD.ldiv_mixed!(p(dX), n, F, p(dB), n, nrhs) && 1 <= F.iters <= 10
+            RFLUAMD.residual_dev!(p(dR), n, p(dA), n, nrhs, n, p(dX), n, p(dB), n)
+        end
+        X, R = Array(dX), Array(dR)
+        @test Array(dA) == A && Array(dB) == B
+        for k in 1:nrhs
+            @test norm(B[:, k] - A * X[:, k], Inf) <= norm(X[:, k], Inf) * opnorm(A, Inf) * eps() * sqrt(n)
+        end
+        @test maximum(abs, R - (B - A * X)) <= (n + 2) * eps() * maximum(abs.(A) * abs.(X) + abs.(B))
+    end
 end

@@ -8,6 +8,8 @@ from ._ffi import Handle, RfluError, default_handle  # noqa: F401
 from .lu import (  # noqa: F401
     LU,
     BatchedLU,
+    MixedLU,
+    NotConvergedError,
     NOPIVOT_NEGATIVE_INFO,
     Adjoint,
     NoPivot,
@@ -19,10 +21,12 @@ from .lu import (  # noqa: F401
     last_path,
     ldiv_,
     ldiv_batched_,
+    ldiv_mixed,
     lu,
     lu_,
     lu_batched,
     lu_batched_,
+    lu_mixed,
     normalize_pivot,
 )
 
@@ -38,6 +42,6 @@ from . import linsolve  # noqa: F401,E402  (LinearSolve.jl's RFLUFactorization c
 __all__ = [
     "linsolve",
     "ButterflyWorkspace", "butterfly_workspace", "butterfly_solve_", "butterfly_mul_",
-    "lu", "lu_", "ldiv_", "LU", "lu_batched", "lu_batched_", "ldiv_batched_", "BatchedLU", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
+    "lu", "lu_", "ldiv_", "LU", "lu_batched", "lu_batched_", "ldiv_batched_", "BatchedLU", "lu_mixed", "ldiv_mixed", "MixedLU", "NotConvergedError", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

@@ -69,6 +69,10 @@ _PLAIN = {
     "rflu_getrf_f32_mgpu": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_int, c_i64, c_i64, c_p]),
     "rflu_mgpu_fill_uniform_f64": (c_int, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_u64, c_dbl]),
     "rflu_mgpu_fill_uniform_f32": (c_int, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_u64, c_dbl]),
+    # mixed precision (Float32 factors of a Float64 matrix, Float64 refinement): Float64 only, so not in _TYPED
+    "rflu_mixed_getrf_f64_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_i64, c_p, c_p]),
+    "rflu_mixed_getrs_f64_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_dbl, c_p, c_i64, c_p, c_i64, c_int, c_p]),
+    "rflu_residual_f64_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64]),
     "rflu_profile_enable": (c_int, [c_p, c_int]),
     "rflu_profile_get": (c_int, [c_p, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64), ctypes.POINTER(c_dbl)]),
     "rflu_profile_get_bytes": (c_int, [c_p, c_int, ctypes.POINTER(c_dbl)]),

@@ -18,6 +18,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <new>
 
 #include "rflu_internal.hpp"
@@ -58,6 +60,7 @@ void Tune::load_env()
     env_get("RFLU_GEMM_MASKED", gemm_masked);
     env_get("RFLU_TRSV_MAX_RHS", trsv_max_rhs);
     env_get("RFLU_TRSM_CHAIN_MAX_RHS", trsm_chain_max_rhs);
+    env_get("RFLU_MIXED_GEMV_MAX_RHS", mixed_gemv_max_rhs);
     env_get("RFLU_QUEUE_CHECK", queue_check);
     env_flag("RFLU_QUEUE_TRACE", queue_trace);
     env_flag("RFLU_SPLIT_ALL", split_all);
@@ -1661,6 +1664,124 @@ static int getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, cons
     return RFLU_OK;
 }
 
+// ---- mixed precision: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme; kernels: mixed.hip) ----
+// The Float32 factors stay in the row-major layout getrf_rm<float> leaves them in and every solve of the loop is getrs_rm<float> on
+// them: no n x n layout change after the first (getrs_cm_dev would pay one per solve).
+static int ensure_mixed_norms(Handle* h, int64_t count)
+{
+    const size_t need = (size_t)std::max<int64_t>(count, 2) * sizeof(double);
+    RFLU_TRY(ensure_buffer(&h->mixed_norms, &h->mixed_norms_bytes, need));
+    if (h->mixed_norms_host_bytes < need) {
+        if (h->mixed_norms_host) RFLU_HIP(hipHostFree(h->mixed_norms_host));
+        h->mixed_norms_host = nullptr;
+        h->mixed_norms_host_bytes = 0;
+        RFLU_HIP(hipHostMalloc(&h->mixed_norms_host, need));
+        h->mixed_norms_host_bytes = need;
+    }
+    return RFLU_OK;
+}
+
+static int mixed_getrf(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, int64_t* ipiv, int pivot,
+                       int64_t blocksize, double* anorm_out, int64_t* info)
+{
+    if (n < 0 || n > INT32_MAX || lda < std::max<int64_t>(n, 1) || ldf < std::max<int64_t>(n, 1)) {
+        set_error("mixed_getrf: bad arguments n=%lld lda=%lld ldf=%lld", (long long)n, (long long)lda, (long long)ldf);
+        return RFLU_ERR_ARG;
+    }
+    if (anorm_out == nullptr || info == nullptr) { set_error("mixed_getrf: null anorm_out or info pointer"); return RFLU_ERR_ARG; }
+    if (n > 0 && (A == nullptr || F == nullptr)) { set_error("mixed_getrf: null matrix pointer"); return RFLU_ERR_ARG; }
+    if (pivot && ipiv == nullptr && n > 0) { set_error("mixed_getrf: pivot != 0 needs an ipiv buffer"); return RFLU_ERR_ARG; }
+    *anorm_out = 0.0;
+    *info = 0;
+    if (n == 0) return RFLU_OK;
+    RFLU_TRY(ensure_mixed_norms(h, 2));
+    RFLU_TRY(launch_demote_relayout(h, n, A, lda, F, ldf, static_cast<double*>(h->mixed_norms)));
+    RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, h->mixed_norms, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RFLU_TRY(getrf_rm<float>(h, n, n, F, ldf, ipiv, pivot, blocksize, info));   // waits for the stream: the norm has arrived
+    *anorm_out = static_cast<const double*>(h->mixed_norms_host)[0];
+    return RFLU_OK;
+}
+
+// R <- B - A X.  Few right-hand sides: residual_few in passes of RESIDUAL_PASS (A streamed once per pass).  Many: read as row-major, a
+// column-major matrix is its transpose, so after R <- B the row-major GEMM C -= A B with C = R^T (nrhs x n), A = X^T, B = A^T is
+// R^T -= X^T A^T, in place on the column-major buffers.
+static int mixed_residual(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
+                          int64_t ldb, double* R, int64_t ldr)
+{
+    if (n <= 0 || nrhs <= 0) return RFLU_OK;
+    if (nrhs <= h->tune.mixed_gemv_max_rhs) {
+        for (int64_t k0 = 0; k0 < nrhs; k0 += RESIDUAL_PASS)
+            RFLU_TRY(launch_residual_few(h, n, std::min<int64_t>(RESIDUAL_PASS, nrhs - k0), A, lda, X + k0 * ldx, ldx, B + k0 * ldb, ldb,
+                                         R + k0 * ldr, ldr));
+        return RFLU_OK;
+    }
+    RFLU_HIP(hipMemcpy2DAsync(R, (size_t)ldr * sizeof(double), B, (size_t)ldb * sizeof(double), (size_t)n * sizeof(double), (size_t)nrhs,
+                              hipMemcpyDeviceToDevice, h->stream));
+    return gemm_public<double>(h, nrhs, n, n, X, ldx, A, lda, R, ldr);
+}
+
+static int residual_public(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
+                           int64_t ldb, double* R, int64_t ldr)
+{
+    const int64_t n1 = std::max<int64_t>(n, 1);
+    if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldx < n1 || ldb < n1 || ldr < n1) {
+        set_error("residual: bad arguments n=%lld nrhs=%lld lda=%lld ldx=%lld ldb=%lld ldr=%lld", (long long)n, (long long)nrhs, (long long)lda,
+                  (long long)ldx, (long long)ldb, (long long)ldr);
+        return RFLU_ERR_ARG;
+    }
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    if (A == nullptr || X == nullptr || B == nullptr || R == nullptr) { set_error("residual: null pointer"); return RFLU_ERR_ARG; }
+    RFLU_TRY(mixed_residual(h, n, nrhs, A, lda, X, ldx, B, ldb, R, ldr));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+// X <- A^-1 B: x_0 = F32^-1 demote(B); then r = B - A x in Float64, the norms, the decision (dsgesv's rule: converged when for every
+// column ||r_k||_inf <= ||x_k||_inf * anorm * eps * sqrt(n); written so that a NaN or Inf anywhere is NOT convergence), and while it is
+// not met x += F32^-1 demote(r).  One host read per step: the 2 nrhs norms.
+static int mixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const float* F, int64_t ldf, const int64_t* ipiv,
+                       double anorm, const double* B, int64_t ldb, double* X, int64_t ldx, int max_iter, int* iters)
+{
+    const int64_t n1 = std::max<int64_t>(n, 1);
+    if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldf < n1 || ldb < n1 || ldx < n1) {
+        set_error("mixed_getrs: bad arguments n=%lld nrhs=%lld lda=%lld ldf=%lld ldb=%lld ldx=%lld", (long long)n, (long long)nrhs,
+                  (long long)lda, (long long)ldf, (long long)ldb, (long long)ldx);
+        return RFLU_ERR_ARG;
+    }
+    if (iters == nullptr) { set_error("mixed_getrs: null iters pointer"); return RFLU_ERR_ARG; }
+    *iters = 0;
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    if (A == nullptr || F == nullptr || B == nullptr || X == nullptr) { set_error("mixed_getrs: null pointer"); return RFLU_ERR_ARG; }
+    if (max_iter <= 0) max_iter = 30;
+    const int64_t ldw = round_up(nrhs, 16);
+    RFLU_TRY(ensure_buffer(&h->mixed_rhs, &h->mixed_rhs_bytes, (size_t)n * (size_t)ldw * sizeof(float)));
+    RFLU_TRY(ensure_buffer(&h->mixed_r, &h->mixed_r_bytes, (size_t)n * (size_t)nrhs * sizeof(double)));
+    RFLU_TRY(ensure_mixed_norms(h, 2 * nrhs));
+    float* W = static_cast<float*>(h->mixed_rhs);
+    double* R = static_cast<double*>(h->mixed_r);
+    double* norms_dev = static_cast<double*>(h->mixed_norms);
+    const double* norms = static_cast<const double*>(h->mixed_norms_host);
+    const double scale = anorm * DBL_EPSILON * std::sqrt((double)n);
+
+    RFLU_TRY((launch_convert_transpose<double, float>(h, n, nrhs, B, ldb, W, ldw, false)));
+    RFLU_TRY(getrs_rm<float>(h, n, nrhs, F, ldf, ipiv, W, ldw));
+    RFLU_TRY((launch_convert_transpose<float, double>(h, nrhs, n, W, ldw, X, ldx, false)));
+    for (int step = 0;; ++step) {
+        RFLU_TRY(mixed_residual(h, n, nrhs, A, lda, X, ldx, B, ldb, R, n));
+        RFLU_TRY(launch_colnorms(h, n, nrhs, R, n, X, ldx, norms_dev));
+        RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, norms_dev, (size_t)(2 * nrhs) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        bool converged = true;
+        for (int64_t k = 0; k < nrhs && converged; ++k)
+            if (!(norms[2 * k] <= norms[2 * k + 1] * scale)) converged = false;
+        if (converged) { *iters = step; return RFLU_OK; }
+        if (step >= max_iter) { *iters = -(step + 1); return RFLU_OK; }
+        RFLU_TRY((launch_convert_transpose<double, float>(h, n, nrhs, R, n, W, ldw, false)));
+        RFLU_TRY(getrs_rm<float>(h, n, nrhs, F, ldf, ipiv, W, ldw));
+        RFLU_TRY((launch_convert_transpose<float, double>(h, nrhs, n, W, ldw, X, ldx, true)));
+    }
+}
+
 // ---- host entry through the update engine: the way in overlaps the factorization (round 5) -----------------------------------------
 // The reference's boundary is a host array (src/lu.jl:116-121).  Round 3 overlapped the way BACK with the factorization; the way in
 // (38 ms of PCIe for a 16384^2 Float64 matrix) still preceded everything, because the stream schedules' first update touches every
@@ -2117,7 +2238,7 @@ struct DeviceGuard {
 
 extern "C" {
 
-int rflu_version(void) { return 102; }
+int rflu_version(void) { return 103; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -2198,6 +2319,11 @@ int rflu_destroy(rflu_handle_t handle)
     if (h->out_stage) (void)hipFree(h->out_stage);
     if (h->rhs_work) (void)hipFree(h->rhs_work);
     if (h->hostB_dev) (void)hipFree(h->hostB_dev);
+    if (h->mixed_rhs) (void)hipFree(h->mixed_rhs);
+    if (h->mixed_r) (void)hipFree(h->mixed_r);
+    if (h->mixed_part) (void)hipFree(h->mixed_part);
+    if (h->mixed_norms) (void)hipFree(h->mixed_norms);
+    if (h->mixed_norms_host) (void)hipHostFree(h->mixed_norms_host);
     if (h->pm_cnt) (void)hipFree(h->pm_cnt);
     if (h->pm_dst) (void)hipFree(h->pm_dst);
     if (h->pm_src) (void)hipFree(h->pm_src);
@@ -2453,6 +2579,28 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
 
 DEFINE_TYPED(f64, double)
 DEFINE_TYPED(f32, float)
+
+int rflu_mixed_getrf_f64_dev(rflu_handle_t handle, int64_t n, const double* A_dev, int64_t lda, float* F32_dev, int64_t ldf,
+                             int64_t* ipiv_dev, int pivot, int64_t blocksize, double* anorm_out, int64_t* info)
+{
+    CHECK_HANDLE(handle);
+    return mixed_getrf(H(handle), n, A_dev, lda, F32_dev, ldf, ipiv_dev, pivot, blocksize, anorm_out, info);
+}
+
+int rflu_mixed_getrs_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const float* F32_dev,
+                             int64_t ldf, const int64_t* ipiv_dev, double anorm, const double* B_dev, int64_t ldb, double* X_dev,
+                             int64_t ldx, int max_iter, int* iters)
+{
+    CHECK_HANDLE(handle);
+    return mixed_getrs(H(handle), n, nrhs, A_dev, lda, F32_dev, ldf, ipiv_dev, anorm, B_dev, ldb, X_dev, ldx, max_iter, iters);
+}
+
+int rflu_residual_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const double* X_dev,
+                          int64_t ldx, const double* B_dev, int64_t ldb, double* R_dev, int64_t ldr)
+{
+    CHECK_HANDLE(handle);
+    return residual_public(H(handle), n, nrhs, A_dev, lda, X_dev, ldx, B_dev, ldb, R_dev, ldr);
+}
 
 /* experiment hook (not in rflu.h): a stream restricted to an arbitrary CU mask (8 x 32 bits); the caller owns it */
 int rflu_debug_masked_stream(rflu_handle_t handle, const unsigned* mask8, void** stream_out)

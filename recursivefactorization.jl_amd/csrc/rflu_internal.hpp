@@ -71,6 +71,8 @@ struct Tune {
     int gemm_masked = -1;              // RFLU_GEMM_MASKED: stand-alone rflu_gemm_* calls on the CU-masked stream leaving this many CUs free
     int64_t ld_pad = 0;                // RFLU_LD_PAD
     int64_t trsv_max_rhs = 32;         // RFLU_TRSV_MAX_RHS
+    int64_t mixed_gemv_max_rhs = 16;   // RFLU_MIXED_GEMV_MAX_RHS: mixed-precision refinement: residuals of up to this many right-hand sides by residual_few
+                                       // (mixed.hip, passes of 8), of more by the Float64 GEMM on the transposed views
     int64_t trsm_chain_max_rhs = 320;  // RFLU_TRSM_CHAIN_MAX_RHS: up to this many right-hand sides the cooperative solve in passes of 64 (MFMA)
     int trsm_chain_cached = 1;         // RFLU_TRSM_CHAIN_CACHED=0: every workgroup fetches x_d with cache-bypassing loads (trsv.hip)
     int trsm_chain_split = 2;          // RFLU_TRSM_CHAIN_SPLIT: a pass of 64 right-hand sides as 0 = one chain of 64 columns, 1 = four of 16 in runs of two blocks,
@@ -187,6 +189,17 @@ struct Handle {
     size_t rhs_work_bytes = 0;
     void* hostB_dev = nullptr;   // device copy of host right-hand sides (getrs host entry)
     size_t hostB_bytes = 0;
+    // mixed-precision solve (mixed.hip, driver.cpp: mixed_getrf / mixed_getrs)
+    void* mixed_rhs = nullptr;   // Float32 row-major right-hand sides / corrections
+    size_t mixed_rhs_bytes = 0;
+    void* mixed_r = nullptr;     // Float64 residual, column-major n x nrhs
+    size_t mixed_r_bytes = 0;
+    void* mixed_part = nullptr;  // partial sums: row sums of |A| per tile column, the column slices' shares of A X
+    size_t mixed_part_bytes = 0;
+    void* mixed_norms = nullptr; // device: ||A||_inf, or per column {||r_k||_inf, ||x_k||_inf} ...
+    size_t mixed_norms_bytes = 0;
+    void* mixed_norms_host = nullptr;   // ... and their pinned host image: the one host read of a refinement step
+    size_t mixed_norms_host_bytes = 0;
 
     // pivot bookkeeping: for every chunk of NB pivots the list of (dst,src) row moves equivalent to its interchanges
     int* pm_cnt = nullptr;
@@ -398,5 +411,18 @@ int launch_getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, i
 template <typename T>
 int launch_getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const T* F, int64_t lda, int64_t strideF, int row_major,
                          const int64_t* ipiv, int64_t stride_ipiv, T* B, int64_t ldb, int64_t strideB, int trans);
+
+// mixed.hip: the kernels of the mixed-precision solve.  A, X, B, R column-major Float64; F row-major Float32.
+constexpr int RESIDUAL_PASS = 8;   // right-hand sides per launch of residual_few
+// F <- Float32(A) in row-major, *anorm_dev (device) <- ||A||_inf; partial sums in Handle::mixed_part
+int launch_demote_relayout(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, double* anorm_dev);
+// R <- B - A X for nrhs <= RESIDUAL_PASS; A is read once
+int launch_residual_few(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
+                        int64_t ldb, double* R, int64_t ldr);
+// out[r][c] = (TO) in[c][r], or += with add: element type and layout of the right-hand sides in one pass
+template <typename TI, typename TO>
+int launch_convert_transpose(Handle* h, int64_t rows_out, int64_t cols_out, const TI* in, int64_t ld_in, TO* out, int64_t ld_out, bool add);
+// norms[2k] = ||r_k||_inf, norms[2k + 1] = ||x_k||_inf (a NaN anywhere in a column is kept)
+int launch_colnorms(Handle* h, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* X, int64_t ldx, double* norms);
 
 }  // namespace rflu

@@ -18,6 +18,10 @@ src/lu.jl:97-130 with ``check = false``] does, in order:
 same state machine in the language the tests here can run, over the same entry points (``lu_`` -> ``rflu_getrf_*``,
 ``ldiv_`` -> ``rflu_getrs_*``): fresh -> factor INTO the cached ``ipiv``, not fresh -> reuse the factors without touching
 the GPU factorization again, singular -> ``ReturnCode.Failure``.
+
+``RF32MixedLUFactorization`` (LinearSolve's Float32-inside algorithm next to ``RFLUFactorization``) runs the same state machine over
+``lu_mixed`` / ``ldiv_mixed``: Float32 factors, Float64 iterative refinement, ``cache.A`` NOT overwritten, and ``ReturnCode.Failure``
+only when the Float64 fallback is singular as well.
 """
 from __future__ import annotations
 
@@ -26,7 +30,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .lu import LU, NotIPIV, _is_torch, ldiv_, lu_, normalize_pivot
+from .lu import LU, NotIPIV, SingularException, _is_torch, ldiv_, ldiv_mixed, lu_, lu_mixed, normalize_pivot
 
 
 class ReturnCode(enum.Enum):
@@ -43,6 +47,21 @@ class RFLUFactorization:
     pivot: object = True
     thread: object = True
     blocksize: int = 0
+
+    @property
+    def P(self) -> bool:
+        return normalize_pivot(self.pivot)
+
+
+@dataclass
+class RF32MixedLUFactorization:
+    """``RF32MixedLUFactorization(; pivot = Val(true))``: factor a Float32 copy of ``A``, solve, refine with Float64 residuals.
+    ``cacheval`` is the ``MixedLU`` (with it the Float64 fallback factorization once one was needed)."""
+
+    pivot: object = True
+    thread: object = True
+    blocksize: int = 0
+    max_iter: int = 30
 
     @property
     def P(self) -> bool:
@@ -94,6 +113,8 @@ class LinearCache:
 def init_cacheval(alg: RFLUFactorization, A, b, u):
     """``init_cacheval(::RFLUFactorization, A, b, u, ...)`` -> ``(fact, ipiv)``: a placeholder factorization of the right type and
     the pivot vector that every later ``lu!`` writes into (LinearSolve allocates it once: ``Vector{BlasInt}(undef, min(size(A)...))``)."""
+    if isinstance(alg, RF32MixedLUFactorization):
+        return None   # lu_mixed allocates the Float32 factors and the pivots with the first factorization
     ipiv = _new_ipiv(A, min(int(A.shape[0]), int(A.shape[1])))
     return (LU(A[:0, :0], ipiv[:0], 0), ipiv)
 
@@ -112,6 +133,8 @@ def init(A, b, alg: RFLUFactorization = None, u=None) -> LinearCache:
 def solve_(cache: LinearCache) -> LinearSolution:
     """``solve!(cache)`` for ``RFLUFactorization`` (see the module docstring)."""
     alg = cache.alg
+    if isinstance(alg, RF32MixedLUFactorization):
+        return _solve_mixed(cache)
     A = cache.A
     fact, ipiv = cache.cacheval
     if cache.isfresh:
@@ -134,6 +157,26 @@ def solve_(cache: LinearCache) -> LinearSolution:
     return LinearSolution(y, ReturnCode.Success, alg)
 
 
+def _solve_mixed(cache: LinearCache) -> LinearSolution:
+    """``solve!(cache)`` for ``RF32MixedLUFactorization``: fresh -> ``lu_mixed(cache.A)`` (``A`` is only read), then ``ldiv_mixed`` with
+    the Float64 fallback; a zero pivot of the Float32 factorization is no failure, a singular Float64 fallback is."""
+    alg = cache.alg
+    if cache.isfresh:
+        cache.cacheval = lu_mixed(cache.A, alg.pivot, blocksize=alg.blocksize or None)
+        cache.nfactor += 1
+        cache.isfresh = False
+    try:
+        x = ldiv_mixed(cache.cacheval, cache.b, max_iter=alg.max_iter, fallback=True)
+    except SingularException:
+        cache.isfresh = True
+        return LinearSolution(cache.u, ReturnCode.Failure, alg)
+    if _is_torch(cache.u):   # x has the kind of cache.b (ldiv_mixed), u the kind init gave it: the same
+        cache.u.copy_(x)
+    else:
+        np.copyto(cache.u, x)
+    return LinearSolution(cache.u, ReturnCode.Success, alg)
+
+
 def solve(A, b, alg: RFLUFactorization = None) -> LinearSolution:
     """``solve(LinearProblem(A, b), alg)``: out of place (A and b are copied, as LinearSolve does without aliasing)."""
     if _is_torch(A):
@@ -145,4 +188,4 @@ def solve(A, b, alg: RFLUFactorization = None) -> LinearSolution:
     return solve_(init(A2, b, alg))
 
 
-__all__ = ["RFLUFactorization", "LinearCache", "LinearSolution", "ReturnCode", "init", "init_cacheval", "solve", "solve_"]
+__all__ = ["RFLUFactorization", "RF32MixedLUFactorization", "LinearCache", "LinearSolution", "ReturnCode", "init", "init_cacheval", "solve", "solve_"]

@@ -11,6 +11,8 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
     (no counterpart: many small systems at once, getrfBatched / getrsBatched)               -> ``lu_batched_`` / ``lu_batched`` /
                                                                                              ``ldiv_batched_`` / ``BatchedLU``
     NoPivot failures carry a NEGATIVE info on Julia >= 1.11                        :25,250,324 -> ``NOPIVOT_NEGATIVE_INFO``
+    (no counterpart here; LinearSolve.jl's RF32MixedLUFactorization: Float32 factors,      -> ``lu_mixed`` / ``ldiv_mixed`` / ``MixedLU``
+     Float64 iterative refinement)
     Adjoint/Transpose wrappers                                                     :85-87   -> ``Adjoint`` / ``lu(A.T ...)``;
                                                                                              ``ldiv_(Adjoint(F), B)`` solves A' x = b
 
@@ -319,6 +321,147 @@ def ldiv_(F: LU, B, *, handle=None):
     h.call(f"rflu_getrs_{trans}{sfx}", n, nrhs, ctypes.c_void_p(A.ctypes.data), max(n, 1),
            ctypes.c_void_p(0 if ipiv is None else ipiv.ctypes.data), ctypes.c_void_p(B.ctypes.data), max(n, 1))
     return B
+
+
+class NotConvergedError(ArithmeticError):
+    """``ldiv_mixed(..., fallback=False)``: the refinement did not reach Float64 backward error within ``max_iter`` steps."""
+
+    def __init__(self, iters: int):
+        super().__init__(f"mixed-precision refinement did not converge ({-iters - 1} steps taken); the matrix is too ill-conditioned for "
+                         "Float32 factors -- use lu / ldiv_ in Float64")
+        self.iters = iters
+
+
+@dataclass
+class MixedLU:
+    """Float32 factors of a Float64 matrix, for ``ldiv_mixed``: ``A`` (the caller's matrix, untouched -- the residuals need it),
+    ``F32`` (n x n Float32, row-major, packed L\\U), ``ipiv`` (int64 CUDA tensor, 1-based; ``NotIPIV`` for NoPivot), ``info`` of the
+    FLOAT32 factorization, ``anorm`` = ||A||_inf, and from the last ``ldiv_mixed``: ``iters`` (>= 0 refinement steps, converged; < 0 not
+    converged) and ``fell_back`` (the Float64 factorization served it)."""
+
+    A: object
+    F32: object
+    ipiv: object
+    info: int
+    anorm: float
+    iters: int = 0
+    fell_back: bool = False
+    _f64: object = None   # the Float64 factorization of a copy of A, once a fallback needed it
+
+    def issuccess(self) -> bool:
+        return self.info == 0
+
+
+def _check_mixed_matrix(A):
+    """Shape, element type and layout of ``lu_mixed``'s matrix -- before anything touches the library."""
+    if getattr(A, "ndim", None) != 2:
+        raise ValueError("lu_mixed needs a matrix")
+    if str(A.dtype).replace("torch.", "") != "float64":
+        raise TypeError(f"lu_mixed factors a Float64 matrix in Float32 and refines in Float64 (got {A.dtype}); "
+                        "a Float32 matrix goes to lu / lu_ directly")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("lu_mixed needs a square matrix")
+
+
+def lu_mixed(A, pivot=True, *, blocksize=None, handle=None) -> MixedLU:
+    """Factor a Float32 copy of the Float64 matrix ``A`` (``rflu_mixed_getrf_f64_dev``): one pass demotes ``A`` into the library's
+    row-major layout and yields ||A||_inf, the Float32 factorization runs in place there.  ``A`` is NOT modified and is kept by
+    reference.  ``A``: a CUDA Float64 tensor, column-major (``stride(0) == 1``) like the other device entries; a NumPy array is staged
+    through a torch tensor.  A zero pivot of the Float32 factorization is reported in ``info``, never raised: ``ldiv_mixed`` decides."""
+    piv = normalize_pivot(pivot)
+    _check_mixed_matrix(A)
+    import torch
+
+    if not _is_torch(A):
+        if not isinstance(A, np.ndarray):
+            raise TypeError("A must be a numpy.ndarray or a CUDA torch.Tensor")
+        A = torch.from_numpy(np.ascontiguousarray(A.T)).to("cuda:0").T   # column-major on the device
+    elif not A.is_cuda:
+        raise _ffi.RfluError("torch input must live on the MI355X (device='cuda'); host data goes in as NumPy")
+    n = int(A.shape[0])
+    if n > 1 and not (A.stride(0) == 1 and A.stride(1) >= n):
+        raise ValueError("lu_mixed: the matrix must be dense column-major (stride(0) == 1, stride(1) >= n)")
+    lda = int(A.stride(1)) if n > 1 else max(n, 1)
+    ldf = (max(n, 1) + 15) // 16 * 16
+    F32 = torch.empty((n, ldf), dtype=torch.float32, device=A.device)[:, :n]
+    ipiv_t = torch.empty(n, dtype=torch.int64, device=A.device) if piv else None
+    info, anorm = ctypes.c_int64(0), ctypes.c_double(0.0)
+    if n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        h.call("rflu_mixed_getrf_f64_dev", n, ctypes.c_void_p(A.data_ptr()), lda, ctypes.c_void_p(F32.data_ptr()), ldf,
+               ctypes.c_void_p(ipiv_t.data_ptr() if ipiv_t is not None else 0), int(piv), int(blocksize or 0), ctypes.byref(anorm),
+               ctypes.byref(info))
+    inf = int(info.value)
+    if not piv and NOPIVOT_NEGATIVE_INFO:
+        inf = -inf
+    return MixedLU(A, F32, ipiv_t if ipiv_t is not None else NotIPIV(n), inf, float(anorm.value))
+
+
+def ldiv_mixed(F: MixedLU, B, *, max_iter=30, fallback=True, handle=None):
+    """``A \\ B`` to Float64 backward error with the Float32 factors ``F`` (``rflu_mixed_getrs_f64_dev``): solve, Float64 residual, and
+    while some column misses ``||r||_inf <= ||x||_inf ||A||_inf eps sqrt(n)`` another Float32 solve of the residual.  Returns a NEW ``X``
+    (``B`` is only read; a NumPy ``B`` gives a NumPy ``X``).  ``F.iters`` records the steps.
+
+    When the Float32 factorization hit a zero pivot (``F.info != 0``) or the refinement does not converge within ``max_iter`` steps:
+    ``fallback=True`` solves with the Float64 ``lu`` / ``ldiv_`` of a copy of ``A`` (kept in ``F`` for later calls) and sets
+    ``F.fell_back``; a matrix that is singular in Float64 too raises ``SingularException`` as ``lu`` does.  ``fallback=False`` raises
+    ``SingularException`` / ``NotConvergedError`` instead.  The library itself never falls back."""
+    if not isinstance(F, MixedLU):
+        raise TypeError("ldiv_mixed needs the MixedLU that lu_mixed returned")
+    A = F.A
+    n = int(A.shape[0])
+    if getattr(B, "ndim", 0) not in (1, 2):
+        raise ValueError("B must be a vector or a matrix")
+    if B.shape[0] != n:
+        raise ValueError("right-hand side has the wrong number of rows")
+    if str(B.dtype).replace("torch.", "") != "float64":
+        raise TypeError("B must be Float64 like A")
+    import torch
+
+    host = not _is_torch(B)
+    if host:
+        if not isinstance(B, np.ndarray):
+            raise TypeError("B must be a numpy.ndarray or a CUDA torch.Tensor")
+        Bd = torch.from_numpy(np.ascontiguousarray(B.T)).to(A.device).T if B.ndim == 2 else torch.from_numpy(np.ascontiguousarray(B)).to(A.device)
+    else:
+        if not B.is_cuda:
+            raise TypeError("B must be a CUDA tensor (or a NumPy array, which is staged)")
+        Bd = B
+    nrhs = 1 if Bd.ndim == 1 else int(Bd.shape[1])
+    if Bd.ndim == 1:
+        if n > 1 and Bd.stride(0) != 1:
+            raise ValueError("a vector right-hand side must be contiguous (stride 1); copy the view first")
+        ldb = max(n, 1)
+    else:
+        if n > 1 and not (Bd.stride(0) == 1 and (nrhs <= 1 or Bd.stride(1) >= n)):
+            raise ValueError("B must be column-major like A")
+        ldb = int(Bd.stride(1)) if (nrhs > 1 and n > 1) else max(n, 1)
+    X = torch.empty(n, dtype=torch.float64, device=A.device) if Bd.ndim == 1 else torch.empty((nrhs, n), dtype=torch.float64, device=A.device).T
+    F.fell_back = False
+    F.iters = 0
+    ok = F.info == 0
+    if ok and n > 0 and nrhs > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        iters = ctypes.c_int(0)
+        h.call("rflu_mixed_getrs_f64_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), int(A.stride(1)) if n > 1 else 1,
+               ctypes.c_void_p(F.F32.data_ptr()), int(F.F32.stride(0)) if n > 1 else 1,
+               ctypes.c_void_p(0 if isinstance(F.ipiv, NotIPIV) else F.ipiv.data_ptr()), float(F.anorm), ctypes.c_void_p(Bd.data_ptr()), ldb,
+               ctypes.c_void_p(X.data_ptr()), max(n, 1), int(max_iter), ctypes.byref(iters))
+        F.iters = int(iters.value)
+        ok = F.iters >= 0
+    if not ok:
+        if not fallback:
+            if F.info != 0:
+                raise SingularException(abs(F.info))
+            raise NotConvergedError(F.iters)
+        if F._f64 is None:
+            F._f64 = lu(A, not isinstance(F.ipiv, NotIPIV), handle=handle)   # check=True: SingularException when Float64 is singular too
+        X.copy_(Bd)
+        ldiv_(F._f64, X, handle=handle)
+        F.fell_back = True
+    return X.cpu().numpy() if host else X
 
 
 @dataclass
