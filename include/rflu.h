@@ -189,6 +189,61 @@ int rflu_getrs_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, i
                                int64_t strideF, int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* B_dev, int64_t ldb,
                                int64_t strideB, int trans);
 
+/* ---- INVERSE, DETERMINANT: what LinearAlgebra offers on the object lu! returns besides the solve (inv / inv!, det, logabsdet,
+ * logdet on an LU), from the packed factors alone.  Kernels and the two sweeps: csrc/inverse.hip, DESIGN.md section 4.4.
+ * Everything is an in-order launch on the handle's stream -- no kernel of these entries waits for another workgroup -- and no sum is
+ * formed by read-modify-write on shared words: results are bit-identical from run to run.  Work is complete on return.
+ *
+ * (log|det A|, sign det A) from the factors.  The diagonal sits at F[i*(ld+1)] in BOTH layouts, so one entry serves column- and
+ * row-major factors.  ipiv NULL = NotIPIV.  *logabs_out, *sign_out: host, required.  Julia's logabsdet(::LU): sum of log|u_ii|;
+ * sign = product of sign(u_ii) times (-1)^#{k : ipiv[k] != k+1}.  Float64 arithmetic for both element types; chunks of 1024 diagonal
+ * entries are summed by a fixed tree, the chunk sums in index order.  A zero u_ii gives (-Inf, 0); a NaN u_ii gives (NaN, NaN).
+ * n == 0: (0, 1).  The host entry copies the diagonal and ipiv only. */
+int rflu_logabsdet_f64_dev(rflu_handle_t handle, int64_t n, const double* F_dev, int64_t ld, const int64_t* ipiv_dev,
+                           double* logabs_out, double* sign_out);
+int rflu_logabsdet_f32_dev(rflu_handle_t handle, int64_t n, const float* F_dev, int64_t ld, const int64_t* ipiv_dev,
+                           double* logabs_out, double* sign_out);
+int rflu_logabsdet_f64(rflu_handle_t handle, int64_t n, const double* F_host, int64_t ld, const int64_t* ipiv_host,
+                       double* logabs_out, double* sign_out);
+int rflu_logabsdet_f32(rflu_handle_t handle, int64_t n, const float* F_host, int64_t ld, const int64_t* ipiv_host,
+                       double* logabs_out, double* sign_out);
+/* the same for every matrix of a batch (matrix b at F_dev + b*strideF, ipiv at ipiv_dev + b*stride_ipiv as in the BATCHED entries
+ * below); logabs_dev / sign_dev: DEVICE arrays of `batch` doubles.  One launch, one workgroup per matrix, any n (only diagonals are
+ * read: no size cliff); bit-identical to the single-matrix entry on the same factors. */
+int rflu_logabsdet_batched_f64_dev(rflu_handle_t handle, int64_t batch, int64_t n, const double* F_dev, int64_t lda, int64_t strideF,
+                                   const int64_t* ipiv_dev, int64_t stride_ipiv, double* logabs_dev, double* sign_dev);
+int rflu_logabsdet_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, const float* F_dev, int64_t lda, int64_t strideF,
+                                   const int64_t* ipiv_dev, int64_t stride_ipiv, double* logabs_dev, double* sign_dev);
+/* LAPACK getri: F (packed L\U exactly as rflu_getrf_* left it) is overwritten by A^-1 -- the factors are gone afterwards.  ipiv NULL =
+ * NotIPIV.  *info (host, required): 0, or the 1-based index of the first exactly-zero u_ii -- then F is left UNTOUCHED and the return
+ * value is still RFLU_OK (a numerical condition, like everywhere in this header).  n == 0: success, nothing launched.
+ *   - About 4n^3/3 flops (n^3/3 for U^-1 in place, n^3 for the sweep with L), all of it through the MFMA GEMM; against 2n^3 and four
+ *     n x n arrays for rflu_getrs_* on an explicit identity.  Workspace beyond F, owned by the handle: one buffer of 512 x n elements
+ *     and the 64x64 diagonal inverses of both triangles (2 * ceil(n/64) * 4096 elements); nothing of size n x n.
+ *   - The column-major entries work IN PLACE on F read as a row-major array with ld = lda (that is F^T, and A^-1 column-major is
+ *     A^-T row-major): no layout change.  Any lda >= n and any pointer aligned to the element size are accepted; where lda *
+ *     sizeof(T) or the pointer is no multiple of 16 bytes the GEMM loads element by element (slower, same arithmetic; h->work is
+ *     not used).  Entries of F beyond the n x n matrix (rows n .. lda-1 of a column) are never written.
+ *   - The row-major entry pays one layout change of R into the handle's workspace and one back (the trade of rflu_getrs_trans_rm_*).
+ *   - The host entry: H2D, the device entry, D2H (not at all when info != 0). */
+int rflu_getri_f64_dev(rflu_handle_t handle, int64_t n, double* F_dev, int64_t lda, const int64_t* ipiv_dev, int64_t* info);
+int rflu_getri_f32_dev(rflu_handle_t handle, int64_t n, float* F_dev, int64_t lda, const int64_t* ipiv_dev, int64_t* info);
+int rflu_getri_rm_f64_dev(rflu_handle_t handle, int64_t n, double* R_dev, int64_t ld, const int64_t* ipiv_dev, int64_t* info);
+int rflu_getri_rm_f32_dev(rflu_handle_t handle, int64_t n, float* R_dev, int64_t ld, const int64_t* ipiv_dev, int64_t* info);
+int rflu_getri_f64(rflu_handle_t handle, int64_t n, double* F_host, int64_t lda, const int64_t* ipiv_host, int64_t* info);
+int rflu_getri_f32(rflu_handle_t handle, int64_t n, float* F_host, int64_t lda, const int64_t* ipiv_host, int64_t* info);
+/* Ainv_b <- A_b^-1 from batched factors (getriBatched); out of place (Ainv must not overlap F), Ainv in the ORIENTATION OF F with its
+ * own ldi / strideI.  info_dev (device, batch entries, required): 0 or the first zero u_ii of that matrix, whose output is then
+ * Inf/NaN in its own matrix only.  n <= 128: ONE launch, the factors in LDS once, the identity right-hand sides made in LDS.  Larger
+ * matrices: a loop over a device copy and the single-matrix getri -- correct, NOT fast, no size cliff.  Argument rules and the
+ * batch == 0 / n == 0 cases as rflu_getrs_batched_*. */
+int rflu_getri_batched_f64_dev(rflu_handle_t handle, int64_t batch, int64_t n, const double* F_dev, int64_t lda, int64_t strideF,
+                               int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, double* Ainv_dev, int64_t ldi,
+                               int64_t strideI, int64_t* info_dev);
+int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, const float* F_dev, int64_t lda, int64_t strideF,
+                               int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* Ainv_dev, int64_t ldi,
+                               int64_t strideI, int64_t* info_dev);
+
 /* ---- MIXED PRECISION: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme) ----
  * The Float32 factorization is the faster one; refinement with Float64 residuals r = b - A x brings the solution to Float64 backward
  * error when A is not too ill-conditioned for its Float32 factors (kappa well below 1 / eps32), and says so when it does not.

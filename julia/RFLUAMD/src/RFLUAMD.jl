@@ -207,6 +207,146 @@ function getrs_trans!(F::StridedMatrix{Float32}, ipiv::Ptr{Int64}, B::StridedVec
     return B
 end
 
+"""
+    getri!(F, ipiv) -> info
+
+LAPACK getri on HOST factors (`rflu_getri_*`, include/rflu.h): the packed `L\\U` in `F` (column-major, as `getrf!` left it) is
+overwritten by `inv(A)`; about 4n^3/3 flops and no n x n workspace on the device.  Returns 0, or the index of the first exactly
+zero `u_ii` -- `F` is then untouched.  `ipiv = C_NULL` plays NotIPIV.
+"""
+function getri!(F::StridedMatrix{Float64}, ipiv::Ptr{Int64})
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getri_f64, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), size(F, 1), F, stride(F, 2), ipiv, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return info[]
+end
+
+function getri!(F::StridedMatrix{Float32}, ipiv::Ptr{Int64})
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getri_f32, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), size(F, 1), F, stride(F, 2), ipiv, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return info[]
+end
+
+"""
+    getri_dev!(F, n, ld, ipiv; row_major = false) -> info
+
+The same on factors that live in HBM: column-major (`rflu_getri_*_dev`, in place, no layout change) or row-major
+(`rflu_getri_rm_*_dev`, one layout change each way through the handle's workspace).
+"""
+function getri_dev!(F::Ptr{Float64}, n::Integer, ld::Integer, ipiv::Ptr{Int64}; row_major::Bool = false)
+    info = Ref{Int64}(0)
+    st = row_major ?
+         ccall((:rflu_getri_rm_f64_dev, librflu), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), n, F, ld, ipiv, info) :
+         ccall((:rflu_getri_f64_dev, librflu), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), n, F, ld, ipiv, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return info[]
+end
+
+function getri_dev!(F::Ptr{Float32}, n::Integer, ld::Integer, ipiv::Ptr{Int64}; row_major::Bool = false)
+    info = Ref{Int64}(0)
+    st = row_major ?
+         ccall((:rflu_getri_rm_f32_dev, librflu), Cint, (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), n, F, ld, ipiv, info) :
+         ccall((:rflu_getri_f32_dev, librflu), Cint, (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), n, F, ld, ipiv, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return info[]
+end
+
+"""
+    logabsdet_dev(F, n, ld, ipiv) -> (logabs, sign)
+    logabsdet_host(F, ipiv) -> (logabs, sign)
+
+`logabsdet(::LU)` from the diagonal of the factors and the parity of `ipiv` (`rflu_logabsdet_*`): Float64 arithmetic for both element
+types, bit-identical from run to run.  The diagonal is at `F[i*(ld+1)]` in both layouts.  The host form copies the diagonal and
+`ipiv` only.
+"""
+function logabsdet_dev(F::Ptr{Float64}, n::Integer, ld::Integer, ipiv::Ptr{Int64})
+    out = zeros(Float64, 2)
+    st = GC.@preserve out ccall((:rflu_logabsdet_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+               handle(), n, F, ld, ipiv, pointer(out, 1), pointer(out, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1], out[2]
+end
+
+function logabsdet_dev(F::Ptr{Float32}, n::Integer, ld::Integer, ipiv::Ptr{Int64})
+    out = zeros(Float64, 2)
+    st = GC.@preserve out ccall((:rflu_logabsdet_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+               handle(), n, F, ld, ipiv, pointer(out, 1), pointer(out, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1], out[2]
+end
+
+function logabsdet_host(F::StridedMatrix{Float64}, ipiv::Ptr{Int64})
+    out = zeros(Float64, 2)
+    st = GC.@preserve out ccall((:rflu_logabsdet_f64, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+               handle(), size(F, 1), F, stride(F, 2), ipiv, pointer(out, 1), pointer(out, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1], out[2]
+end
+
+function logabsdet_host(F::StridedMatrix{Float32}, ipiv::Ptr{Int64})
+    out = zeros(Float64, 2)
+    st = GC.@preserve out ccall((:rflu_logabsdet_f32, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+               handle(), size(F, 1), F, stride(F, 2), ipiv, pointer(out, 1), pointer(out, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1], out[2]
+end
+
+"""
+    getri_batched_dev!(Ainv, ldi, strideI, F, batch, n, lda, strideF, row_major, ipiv, stride_ipiv, info)
+    logabsdet_batched_dev!(logabs, sign, F, batch, n, lda, strideF, ipiv, stride_ipiv)
+
+The batched forms on device memory (`rflu_getri_batched_*_dev`, `rflu_logabsdet_batched_*_dev`): `Ainv` out of place in the orientation
+of `F`, `info` a DEVICE pointer to `batch` entries; `logabs` / `sign` DEVICE pointers to `batch` Float64 values.
+"""
+function getri_batched_dev!(Ainv::Ptr{Float64}, ldi::Integer, strideI::Integer, F::Ptr{Float64}, batch::Integer, n::Integer, lda::Integer,
+                            strideF::Integer, row_major::Bool, ipiv::Ptr{Int64}, stride_ipiv::Integer, info::Ptr{Int64})
+    st = ccall((:rflu_getri_batched_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Int64, Ptr{Int64}),
+               handle(), batch, n, F, lda, strideF, Cint(row_major), ipiv, stride_ipiv, Ainv, ldi, strideI, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return Ainv
+end
+
+function getri_batched_dev!(Ainv::Ptr{Float32}, ldi::Integer, strideI::Integer, F::Ptr{Float32}, batch::Integer, n::Integer, lda::Integer,
+                            strideF::Integer, row_major::Bool, ipiv::Ptr{Int64}, stride_ipiv::Integer, info::Ptr{Int64})
+    st = ccall((:rflu_getri_batched_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Int64}, Int64, Ptr{Float32}, Int64, Int64, Ptr{Int64}),
+               handle(), batch, n, F, lda, strideF, Cint(row_major), ipiv, stride_ipiv, Ainv, ldi, strideI, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return Ainv
+end
+
+function logabsdet_batched_dev!(logabs::Ptr{Float64}, sign::Ptr{Float64}, F::Ptr{Float64}, batch::Integer, n::Integer, lda::Integer,
+                                strideF::Integer, ipiv::Ptr{Int64}, stride_ipiv::Integer)
+    st = ccall((:rflu_logabsdet_batched_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}),
+               handle(), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs, sign)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function logabsdet_batched_dev!(logabs::Ptr{Float64}, sign::Ptr{Float64}, F::Ptr{Float32}, batch::Integer, n::Integer, lda::Integer,
+                                strideF::Integer, ipiv::Ptr{Int64}, stride_ipiv::Integer)
+    st = ccall((:rflu_logabsdet_batched_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}),
+               handle(), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs, sign)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
 # ---- dispatch: who serves a call (RecursiveFactorization src/lu.jl:92-93, 114-126) -------------------------------------------
 const GPUEltype = Union{Float32, Float64}
 gpu_ok(A::StridedMatrix{<:GPUEltype}, ipiv) =
@@ -269,6 +409,35 @@ function ldiv!(F::LU{T, <:StridedMatrix{T}}, B::StridedVecOrMat{T}) where {T <: 
         return B
     end
     return LinearAlgebra.ldiv!(F, B)
+end
+
+# ---- inv! / det / logabsdet on the LU object: the GPU under the conditions of `ldiv!(F, B)`, else the stdlib ------------------------------
+lu_on_gpu(F::LU) = stride(F.factors, 1) == 1 && size(F.factors, 1) == size(F.factors, 2) && size(F.factors, 1) >= GPU_MIN_N[] &&
+                   available() && (F.ipiv isa Vector{Int64} || F.ipiv isa NotIPIV)
+
+"`inv!(F)`: the factors are overwritten by `inv(A)` (LAPACK getri on the GPU) -- `F` is invalid afterwards; SingularException as the stdlib"
+function inv!(F::LU{T, <:StridedMatrix{T}}) where {T <: GPUEltype}
+    lu_on_gpu(F) || return LinearAlgebra.inv!(F)
+    checknonsingular(F.info)
+    p = F.ipiv isa NotIPIV ? Ptr{Int64}(C_NULL) : pointer(F.ipiv)
+    info = GC.@preserve F getri!(F.factors, p)
+    checknonsingular(info)
+    return F.factors
+end
+
+"`logabsdet(F)`: (log|det A|, sign) with the element type of `F`, summed in Float64 on the GPU; only the diagonal and ipiv travel"
+function logabsdet(F::LU{T, <:StridedMatrix{T}}) where {T <: GPUEltype}
+    lu_on_gpu(F) || return LinearAlgebra.logabsdet(F)
+    p = F.ipiv isa NotIPIV ? Ptr{Int64}(C_NULL) : pointer(F.ipiv)
+    la, sg = GC.@preserve F logabsdet_host(F.factors, p)
+    return T(la), T(sg)
+end
+
+"`det(F)` = sign * exp(logabs): equal to the stdlib's running product up to rounding, 0 for a singular `F`"
+function det(F::LU{T, <:StridedMatrix{T}}) where {T <: GPUEltype}
+    lu_on_gpu(F) || return LinearAlgebra.det(F)
+    la, sg = logabsdet(F)
+    return iszero(sg) ? zero(T) : sg * exp(la)
 end
 
 # What `F'` and `transpose(F)` of an LU are: AdjointFactorization / TransposeFactorization from Julia 1.10 on (where the transpose of a

@@ -18,10 +18,18 @@ from .lu import (  # noqa: F401
     SingularException,
     Transpose,
     Val,
+    det,
+    det_batched,
+    inv,
+    inv_,
+    inv_batched,
     last_path,
     ldiv_,
     ldiv_batched_,
     ldiv_mixed,
+    logabsdet,
+    logabsdet_batched,
+    logdet,
     lu,
     lu_,
     lu_batched,
@@ -43,5 +51,6 @@ __all__ = [
     "linsolve",
     "ButterflyWorkspace", "butterfly_workspace", "butterfly_solve_", "butterfly_mul_",
     "lu", "lu_", "ldiv_", "LU", "lu_batched", "lu_batched_", "ldiv_batched_", "BatchedLU", "lu_mixed", "ldiv_mixed", "MixedLU", "NotConvergedError", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
+    "inv", "inv_", "det", "logabsdet", "logdet", "inv_batched", "logabsdet_batched", "det_batched",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

@@ -35,6 +35,13 @@ _TYPED = {
     "rflu_getrs_trans_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64]),
     "rflu_getrf_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_int, c_p]),
     "rflu_getrs_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int]),
+    "rflu_logabsdet_{s}_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "rflu_logabsdet_{s}": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "rflu_logabsdet_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
+    "rflu_getri_{s}_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "rflu_getri_rm_{s}_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "rflu_getri_{s}": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "rflu_getri_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_p]),
     "rflu_panel_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_p]),
     "rflu_laswp_rm_{s}_dev": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64]),
     "rflu_trsm_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64]),

@@ -373,6 +373,88 @@ __global__ void __launch_bounds__(BT) getrs_batched_kernel(BSolveArgs<T> a)
     }
 }
 
+template <typename T>
+struct BInvArgs {
+    const T* F;
+    const int64_t* ipiv;
+    T* Ainv;
+    int64_t* info;
+    int64_t lda, strideF, stride_ipiv, ldi, strideI, batch;
+    int n, row_major;
+    BGeo g;
+};
+
+// the batched inverse: getrs_batched_kernel's forward solve (bsubstitute<T, false>, unchanged) on the columns of P * I, which are made
+// in LDS -- row i of a pass is 1 in column sperm[i] -- and never read from HBM; info from the diagonal held in LDS
+template <typename T>
+__global__ void __launch_bounds__(BT) getri_batched_kernel(BInvArgs<T> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char bsmem[];
+    const BGeo g = a.g;
+    const int n = a.n, ld = g.ld;
+    const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1), lane = t & 63;
+    const int64_t b = (int64_t)blockIdx.x * (BT >> g.tpm_log) + grp;
+    const bool valid = b < a.batch;
+    unsigned char* base = bsmem + (size_t)grp * g.group_bytes;
+    T* s = reinterpret_cast<T*>(base);
+    T* x = reinterpret_cast<T*>(base + g.off_x);
+    int* sperm = reinterpret_cast<int*>(base + g.off_int);   // [n]: row i of P*I is row sperm[i] of I
+    const int64_t bb = valid ? b : 0;
+    const T* F = a.F + bb * a.strideF;
+    T* X = a.Ainv + bb * a.strideI;
+
+    bload_matrix<T>(s, ld, F, a.lda, a.row_major, n, n, g, t, valid);
+    if (t < 64) {
+        // the interchanges composed into one permutation, as in getrs_batched_kernel
+        int p0 = lane, p1 = lane + 64, i0 = lane, i1 = lane + 64;
+        if (a.ipiv && valid) {
+            const int64_t* ip = a.ipiv + b * a.stride_ipiv;
+            if (lane < n) i0 = (int)(ip[lane] - 1);
+            if (lane + 64 < n) i1 = (int)(ip[lane + 64] - 1);
+        }
+        if (a.ipiv) {
+            for (int k = 0; k < n; ++k) {
+                const int ku = __builtin_amdgcn_readfirstlane(k);
+                int p = ku < 64 ? __builtin_amdgcn_readlane(i0, ku) : __builtin_amdgcn_readlane(i1, ku - 64);
+                if (p <= ku || p >= n) continue;
+                const int vk = ku < 64 ? __builtin_amdgcn_readlane(p0, ku) : __builtin_amdgcn_readlane(p1, ku - 64);
+                const int vp = p < 64 ? __builtin_amdgcn_readlane(p0, p) : __builtin_amdgcn_readlane(p1, p - 64);
+                if (lane == (ku & 63)) { if (ku < 64) p0 = vp; else p1 = vp; }
+                if (lane == (p & 63)) { if (p < 64) p0 = vk; else p1 = vk; }
+            }
+        }
+        if (lane < n) sperm[lane] = p0;
+        if (lane + 64 < n) sperm[lane + 64] = p1;
+    }
+    __syncthreads();
+    if (t < 64 && valid) {   // first exactly-zero u_ii of this matrix
+        const bool z0 = lane < n && s[lane + lane * ld] == T(0), z1 = lane + 64 < n && s[lane + 64 + (lane + 64) * ld] == T(0);
+        const bu64 m0 = __ballot(z0), m1 = __ballot(z1);
+        if (lane == 0) a.info[b] = m0 ? (int64_t)__ffsll((long long)m0) : (m1 ? (int64_t)(64 + __ffsll((long long)m1)) : (int64_t)0);
+    }
+
+    const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+    const int rr = t & (BNR - 1), ri0 = t >> 3, ris = g.tpm >> 3;   // row-major output: lanes along a row
+    for (int j0 = 0; j0 < n; j0 += BNR) {
+        const int nr = n - j0 < BNR ? n - j0 : BNR;
+        if (r < n) {
+            const int one = sperm[r] - j0;
+            for (int j = c; j < nr; j += cs) x[r + j * ld] = (j == one) ? T(1) : T(0);
+        }
+        __syncthreads();
+        bsubstitute<T, false>(s, x, ld, n, nr, r, c, cs);
+        if (valid) {
+            if (!a.row_major) {
+                if (r < n)
+                    for (int j = c; j < nr; j += cs) X[r + (int64_t)(j0 + j) * a.ldi] = x[r + j * ld];
+            } else if (rr < nr) {
+                for (int i = ri0; i < n; i += ris) X[(int64_t)i * a.ldi + j0 + rr] = x[i + rr * ld];
+            }
+        }
+        __syncthreads();   // the pass has left LDS before the next one is made
+    }
+}
+
 template <typename K>
 int batched_lds_attr(bool* done, K kernel, size_t lds)
 {
@@ -426,6 +508,30 @@ int launch_getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, cons
     RFLU_HIP(hipGetLastError());
     return RFLU_OK;
 }
+
+template <typename T>
+int launch_getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,
+                         int64_t stride_ipiv, T* Ainv, int64_t ldi, int64_t strideI, int64_t* info)
+{
+    BInvArgs<T> a;
+    a.F = F; a.ipiv = ipiv; a.Ainv = Ainv; a.info = info;
+    a.lda = lda; a.strideF = strideF; a.stride_ipiv = stride_ipiv; a.ldi = ldi; a.strideI = strideI; a.batch = batch;
+    a.n = (int)n; a.row_major = row_major;
+    a.g = batched_geo(n, n, sizeof(T), true);
+    const int groups = BT / a.g.tpm;
+    const size_t lds = (size_t)groups * a.g.group_bytes;
+    RFLU_TRY(batched_lds_attr(&h->batched_inv_attr_set[sizeof(T) == 4], &getri_batched_kernel<T>, lds));
+    const int64_t wgs = (batch + groups - 1) / groups;
+    ProfScope ps(h, RFLU_K_TRSM, 2.0 * (double)batch * (double)n * (double)n * (double)n, 2.0 * (double)batch * (double)n * (double)n * sizeof(T));
+    hipLaunchKernelGGL((getri_batched_kernel<T>), dim3((unsigned)wgs), dim3(BT), lds, h->stream, a);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+template int launch_getri_batched<double>(Handle*, int64_t, int64_t, const double*, int64_t, int64_t, int, const int64_t*, int64_t, double*,
+                                          int64_t, int64_t, int64_t*);
+template int launch_getri_batched<float>(Handle*, int64_t, int64_t, const float*, int64_t, int64_t, int, const int64_t*, int64_t, float*,
+                                         int64_t, int64_t, int64_t*);
 
 template int launch_getrf_batched<double>(Handle*, int64_t, int64_t, int64_t, double*, int64_t, int64_t, int, int64_t*, int64_t, int, int64_t*);
 template int launch_getrf_batched<float>(Handle*, int64_t, int64_t, int64_t, float*, int64_t, int64_t, int, int64_t*, int64_t, int, int64_t*);

@@ -1664,6 +1664,177 @@ static int getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, cons
     return RFLU_OK;
 }
 
+// ---- inv / det / logabsdet from the factors (include/rflu.h; kernels and the two sweeps: inverse.hip) ----------
+static int ensure_ipiv_dev(Handle* h, int64_t n)
+{
+    if ((size_t)n > h->ipiv_cap) {
+        if (h->ipiv_dev) RFLU_HIP(hipFree(h->ipiv_dev));
+        h->ipiv_dev = nullptr;
+        h->ipiv_cap = 0;
+        RFLU_HIP(hipMalloc((void**)&h->ipiv_dev, (size_t)n * sizeof(int64_t)));
+        h->ipiv_cap = (size_t)n;
+    }
+    return RFLU_OK;
+}
+
+template <typename T>
+static int logabsdet_dev(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign)
+{
+    if (n < 0 || ld < std::max<int64_t>(n, 1) || logabs == nullptr || sign == nullptr || (n > 0 && F == nullptr)) {
+        set_error("logabsdet: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
+        return RFLU_ERR_ARG;
+    }
+    *logabs = 0.0;
+    *sign = 1.0;
+    if (n == 0) return RFLU_OK;
+    return launch_logabsdet<T>(h, n, F, ld + 1, ipiv, logabs, sign, nullptr);
+}
+
+// host entry: only the diagonal and ipiv travel
+template <typename T>
+static int logabsdet_host(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign)
+{
+    if (n < 0 || ld < std::max<int64_t>(n, 1) || logabs == nullptr || sign == nullptr || (n > 0 && F == nullptr)) {
+        set_error("logabsdet: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
+        return RFLU_ERR_ARG;
+    }
+    *logabs = 0.0;
+    *sign = 1.0;
+    if (n == 0) return RFLU_OK;
+    std::vector<T> diag((size_t)n);
+    for (int64_t i = 0; i < n; ++i) diag[(size_t)i] = F[i * (ld + 1)];
+    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * sizeof(T)));
+    RFLU_TRY(ensure_ipiv_dev(h, n));
+    RFLU_HIP(hipMemcpyAsync(h->hostB_dev, diag.data(), (size_t)n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    if (ipiv) RFLU_HIP(hipMemcpyAsync(h->ipiv_dev, ipiv, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));   // `diag` is pageable and leaves scope
+    return launch_logabsdet<T>(h, n, static_cast<const T*>(h->hostB_dev), 1, ipiv ? h->ipiv_dev : nullptr, logabs, sign, nullptr);
+}
+
+template <typename T>
+static int logabsdet_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, const int64_t* ipiv,
+                             int64_t stride_ipiv, double* logabs_dev, double* sign_dev)
+{
+    if (batch < 0 || n < 0) {
+        set_error("logabsdet_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0) return RFLU_OK;
+    if (logabs_dev == nullptr || sign_dev == nullptr || (n > 0 && F == nullptr)) { set_error("logabsdet_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (n > 0 && (lda < n || (batch > 1 && strideF < (n - 1) * lda + n))) {
+        set_error("logabsdet_batched: lda=%lld strideF=%lld too small for n=%lld", (long long)lda, (long long)strideF, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("logabsdet_batched: stride_ipiv=%lld < n", (long long)stride_ipiv); return RFLU_ERR_ARG; }
+    if (n == 0) {   // the empty product: (0, 1) for every matrix
+        std::vector<double> z((size_t)batch, 0.0), o((size_t)batch, 1.0);
+        RFLU_HIP(hipMemcpyAsync(logabs_dev, z.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        RFLU_HIP(hipMemcpyAsync(sign_dev, o.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        return RFLU_OK;
+    }
+    RFLU_TRY(launch_logabsdet_batched<T>(h, batch, n, F, lda + 1, strideF, ipiv, stride_ipiv, logabs_dev, sign_dev));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+// column-major device entry: F read as a row-major array with ld = lda IS the transposed view, and A^-1 column-major IS A^-T row-major:
+// no layout change, whatever lda and the pointer's alignment (misaligned: the GEMM's element-wise loads, same arithmetic)
+template <typename T>
+static int getri_cm_dev(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)
+{
+    if (n < 0 || lda < std::max<int64_t>(n, 1) || info == nullptr || (n > 0 && F == nullptr)) {
+        set_error("getri: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    *info = 0;
+    if (n == 0) return RFLU_OK;
+    return getri_view<T>(h, n, F, lda, ipiv, info);
+}
+
+// row-major factors: one layout change into the handle's workspace, the sweeps there, one layout change back
+template <typename T>
+static int getri_rm(Handle* h, int64_t n, T* R, int64_t ld, const int64_t* ipiv, int64_t* info)
+{
+    if (n < 0 || ld < std::max<int64_t>(n, 1) || info == nullptr || (n > 0 && R == nullptr)) {
+        set_error("getri_rm: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
+        return RFLU_ERR_ARG;
+    }
+    *info = 0;
+    if (n == 0) return RFLU_OK;
+    const int64_t ldv = workspace_ld(h, n);
+    RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldv * sizeof(T)));
+    T* V = static_cast<T*>(h->work);
+    RFLU_TRY(launch_transpose<T>(h, n, n, R, ld, V, ldv));
+    RFLU_TRY(getri_view<T>(h, n, V, ldv, ipiv, info));
+    if (*info != 0) return RFLU_OK;
+    RFLU_TRY(launch_transpose<T>(h, n, n, V, ldv, R, ld));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+template <typename T>
+static int getri_host(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)
+{
+    if (n < 0 || lda < std::max<int64_t>(n, 1) || info == nullptr || (n > 0 && F == nullptr)) {
+        set_error("getri: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    *info = 0;
+    if (n == 0) return RFLU_OK;
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(T)));
+    RFLU_TRY(ensure_ipiv_dev(h, n));
+    T* dF = static_cast<T*>(h->hostA_dev);
+    RFLU_HIP(hipMemcpy2DAsync(dF, (size_t)n * sizeof(T), F, (size_t)lda * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
+                              hipMemcpyHostToDevice, h->stream));
+    if (ipiv) RFLU_HIP(hipMemcpyAsync(h->ipiv_dev, ipiv, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    RFLU_TRY(getri_cm_dev<T>(h, n, dF, n, ipiv ? h->ipiv_dev : nullptr, info));
+    if (*info != 0) return RFLU_OK;   // F stays as it is
+    RFLU_HIP(hipMemcpy2DAsync(F, (size_t)lda * sizeof(T), dF, (size_t)n * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
+                              hipMemcpyDeviceToHost, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+template <typename T>
+static int getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,
+                         int64_t stride_ipiv, T* Ainv, int64_t ldi, int64_t strideI, int64_t* info_dev)
+{
+    if (batch < 0 || n < 0) {
+        set_error("getri_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0 || n == 0) return RFLU_OK;
+    if (F == nullptr || Ainv == nullptr || info_dev == nullptr) { set_error("getri_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (lda < n || ldi < n || (batch > 1 && (strideF < (n - 1) * lda + n || strideI < (n - 1) * ldi + n))) {
+        set_error("getri_batched: lda=%lld strideF=%lld ldi=%lld strideI=%lld too small for n=%lld", (long long)lda, (long long)strideF,
+                  (long long)ldi, (long long)strideI, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("getri_batched: stride_ipiv=%lld < n", (long long)stride_ipiv); return RFLU_ERR_ARG; }
+    if (batched_fits(n, n)) {
+        RFLU_TRY(launch_getri_batched<T>(h, batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi, strideI, info_dev));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        h->last_path = RFLU_PATH_HIP_BATCHED;
+        return RFLU_OK;
+    }
+    std::vector<int64_t> infos((size_t)batch, 0);
+    for (int64_t b = 0; b < batch; ++b) {
+        const T* Fb = F + b * strideF;
+        const int64_t* ip = ipiv ? ipiv + b * stride_ipiv : nullptr;
+        T* Xb = Ainv + b * strideI;
+        RFLU_HIP(hipMemcpy2DAsync(Xb, (size_t)ldi * sizeof(T), Fb, (size_t)lda * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
+                                  hipMemcpyDeviceToDevice, h->stream));
+        if (row_major) RFLU_TRY(getri_rm<T>(h, n, Xb, ldi, ip, &infos[(size_t)b]));
+        else RFLU_TRY(getri_cm_dev<T>(h, n, Xb, ldi, ip, &infos[(size_t)b]));
+        if (infos[(size_t)b] != 0)   // a singular matrix: its output is NaN, as the one-launch path's division by zero leaves it non-finite
+            RFLU_HIP(hipMemset2DAsync(Xb, (size_t)ldi * sizeof(T), 0xff, (size_t)n * sizeof(T), (size_t)n, h->stream));
+    }
+    RFLU_HIP(hipMemcpyAsync(info_dev, infos.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 // ---- mixed precision: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme; kernels: mixed.hip) ----
 // The Float32 factors stay in the row-major layout getrf_rm<float> leaves them in and every solve of the loop is getrs_rm<float> on
 // them: no n x n layout change after the first (getrs_cm_dev would pay one per solve).
@@ -2238,7 +2409,7 @@ struct DeviceGuard {
 
 extern "C" {
 
-int rflu_version(void) { return 103; }
+int rflu_version(void) { return 104; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -2324,6 +2495,8 @@ int rflu_destroy(rflu_handle_t handle)
     if (h->mixed_part) (void)hipFree(h->mixed_part);
     if (h->mixed_norms) (void)hipFree(h->mixed_norms);
     if (h->mixed_norms_host) (void)hipHostFree(h->mixed_norms_host);
+    if (h->inv_work) (void)hipFree(h->inv_work);
+    if (h->inv_part) (void)hipFree(h->inv_part);
     if (h->pm_cnt) (void)hipFree(h->pm_cnt);
     if (h->pm_dst) (void)hipFree(h->pm_dst);
     if (h->pm_src) (void)hipFree(h->pm_src);
@@ -2569,6 +2742,49 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
         CHECK_HANDLE(handle);                                                                                         \
         return getrs_batched<T>(H(handle), batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb,     \
                                 strideB, trans);                                                                      \
+    }                                                                                                                 \
+    int rflu_logabsdet_##SFX##_dev(rflu_handle_t handle, int64_t n, const T* F, int64_t ld, const int64_t* ipiv,       \
+                                   double* logabs_out, double* sign_out)                                              \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return logabsdet_dev<T>(H(handle), n, F, ld, ipiv, logabs_out, sign_out);                                     \
+    }                                                                                                                 \
+    int rflu_logabsdet_##SFX(rflu_handle_t handle, int64_t n, const T* F, int64_t ld, const int64_t* ipiv,             \
+                             double* logabs_out, double* sign_out)                                                    \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return logabsdet_host<T>(H(handle), n, F, ld, ipiv, logabs_out, sign_out);                                    \
+    }                                                                                                                 \
+    int rflu_logabsdet_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, const T* F, int64_t lda,   \
+                                           int64_t strideF, const int64_t* ipiv, int64_t stride_ipiv,                 \
+                                           double* logabs_dev, double* sign_dev)                                      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return logabsdet_batched<T>(H(handle), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs_dev, sign_dev);   \
+    }                                                                                                                 \
+    int rflu_getri_##SFX##_dev(rflu_handle_t handle, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info) \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getri_cm_dev<T>(H(handle), n, F, lda, ipiv, info);                                                     \
+    }                                                                                                                 \
+    int rflu_getri_rm_##SFX##_dev(rflu_handle_t handle, int64_t n, T* R, int64_t ld, const int64_t* ipiv,             \
+                                  int64_t* info)                                                                      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getri_rm<T>(H(handle), n, R, ld, ipiv, info);                                                          \
+    }                                                                                                                 \
+    int rflu_getri_##SFX(rflu_handle_t handle, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getri_host<T>(H(handle), n, F, lda, ipiv, info);                                                       \
+    }                                                                                                                 \
+    int rflu_getri_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, const T* F, int64_t lda,       \
+                                       int64_t strideF, int row_major, const int64_t* ipiv, int64_t stride_ipiv,      \
+                                       T* Ainv, int64_t ldi, int64_t strideI, int64_t* info_dev)                      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return getri_batched<T>(H(handle), batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi,        \
+                                strideI, info_dev);                                                                   \
     }                                                                                                                 \
     int rflu_fill_uniform_##SFX##_dev(rflu_handle_t handle, T* A, int64_t m, int64_t n, int64_t ld, int row_major,    \
                                       uint64_t seed, int64_t M_global, int64_t i0, int64_t j0, double diag_add)       \

@@ -200,6 +200,11 @@ struct Handle {
     size_t mixed_norms_bytes = 0;
     void* mixed_norms_host = nullptr;   // ... and their pinned host image: the one host read of a refinement step
     size_t mixed_norms_host_bytes = 0;
+    // inverse / logabsdet (inverse.hip)
+    void* inv_work = nullptr;    // getri: W x n elements -- the negated diagonal block and Q of the G sweep, then the saved block row of H
+    size_t inv_work_bytes = 0;
+    void* inv_part = nullptr;    // logabsdet: per-chunk partial sums, then {logabs, sign, first zero}
+    size_t inv_part_bytes = 0;
 
     // pivot bookkeeping: for every chunk of NB pivots the list of (dst,src) row moves equivalent to its interchanges
     int* pm_cnt = nullptr;
@@ -237,6 +242,7 @@ struct Handle {
     bool gemm_attr_set[2] = {false, false};   // dynamic-LDS opt-in of the GEMM kernels done on this handle's device (f64, f32)
     bool eng_attr_set[2] = {false, false};    // same for the persistent update engine (engine.hip)
     bool batched_attr_set[2][2] = {};         // same for the batched kernels (batched.hip): [factorization|solve][Float64|Float32]
+    bool batched_inv_attr_set[2] = {};        // ... and the batched inverse: [Float64|Float32]
     void* eng_state = nullptr;                // device: EngState (engine.hpp)
     void* eng_host = nullptr;                 // pinned host image of its initial value
     long long* eng_trace_buf = nullptr;       // device: RFLU_ENGINE_TRACE stamps + workgroup-time accounting (measurement only)
@@ -411,6 +417,29 @@ int launch_getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, i
 template <typename T>
 int launch_getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const T* F, int64_t lda, int64_t strideF, int row_major,
                          const int64_t* ipiv, int64_t stride_ipiv, T* B, int64_t ldb, int64_t strideB, int trans);
+
+// the batched inverse: Ainv_b <- A_b^-1 from the factors, out of place, Ainv in the orientation of F; info[b] = first zero u_ii or 0
+template <typename T>
+int launch_getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,
+                         int64_t stride_ipiv, T* Ainv, int64_t ldi, int64_t strideI, int64_t* info);
+
+// trsv.hip: the 64x64 diagonal inverses of both triangles of the transposed view V (lower non-unit -> Ginv, unit upper -> Hinv; block b
+// dense row-major at [b * 64 * 64], identity padding beyond the matrix)
+template <typename T>
+int launch_tri_inv_trans(Handle* h, int64_t n, const T* V, int64_t ld, T* Ginv, T* Hinv);
+
+// inverse.hip.  The diagonal entry i is F[i * dstride] (dstride = ld + 1 in both layouts); results on the HOST,
+// the stream is synchronised.  zero1: 1-based index of the first exactly-zero entry, 0 = none.
+constexpr int64_t GETRI_W = 512;   // block-column / block-row width of getri's two sweeps
+int64_t getri_width(int64_t n);    // ... for an n x n matrix (smaller matrices: n rounded up to 64)
+template <typename T>
+int launch_logabsdet(Handle* h, int64_t n, const T* F, int64_t dstride, const int64_t* ipiv, double* logabs, double* sign, int64_t* zero1);
+template <typename T>
+int launch_logabsdet_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_t dstride, int64_t strideF, const int64_t* ipiv,
+                             int64_t stride_ipiv, double* logabs, double* sign);
+// V: row-major n x n image of F^T, overwritten by A^-T; *info (host): first exactly-zero u_ii, V then untouched.  Complete on return.
+template <typename T>
+int getri_view(Handle* h, int64_t n, T* V, int64_t ld, const int64_t* ipiv, int64_t* info);
 
 // mixed.hip: the kernels of the mixed-precision solve.  A, X, B, R column-major Float64; F row-major Float32.
 constexpr int RESIDUAL_PASS = 8;   // right-hand sides per launch of residual_few

@@ -1031,6 +1031,20 @@ int launch_trsv_coop(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld,
     return RFLU_OK;
 }
 
+template <typename T>
+int launch_tri_inv_trans(Handle* h, int64_t n, const T* V, int64_t ld, T* Ginv, T* Hinv)
+{
+    if (n <= 0) return RFLU_OK;
+    const int64_t nb = (n + NB - 1) / NB;
+    ProfScope ps(h, RFLU_K_TRSM, 2.0 * (double)n * NB * NB / 3.0, 3.0 * sizeof(T) * (double)n * NB);
+    hipLaunchKernelGGL((tri_inv_trans_kernel<T, false, false>), dim3((unsigned)nb), dim3(64), 0, h->stream, (int)n, V, ld, Ginv);
+    hipLaunchKernelGGL((tri_inv_trans_kernel<T, true, true>), dim3((unsigned)nb), dim3(64), 0, h->stream, (int)n, V, ld, Hinv);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+template int launch_tri_inv_trans<double>(Handle*, int64_t, const double*, int64_t, double*, double*);
+template int launch_tri_inv_trans<float>(Handle*, int64_t, const float*, int64_t, float*, float*);
+
 template int launch_trsv_coop<double>(Handle*, int64_t, int64_t, const double*, int64_t, double*, int64_t, bool, bool);
 template int launch_trsv_coop<float>(Handle*, int64_t, int64_t, const float*, int64_t, float*, int64_t, bool, bool);
 

@@ -13,6 +13,9 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
     NoPivot failures carry a NEGATIVE info on Julia >= 1.11                        :25,250,324 -> ``NOPIVOT_NEGATIVE_INFO``
     (no counterpart here; LinearSolve.jl's RF32MixedLUFactorization: Float32 factors,      -> ``lu_mixed`` / ``ldiv_mixed`` / ``MixedLU``
      Float64 iterative refinement)
+    inv / inv!, det, logabsdet, logdet on the LU object (stdlib LinearAlgebra)            -> ``inv`` / ``inv_`` / ``det`` / ``logabsdet`` /
+                                                                                             ``logdet``; batched: ``inv_batched`` /
+                                                                                             ``logabsdet_batched`` / ``det_batched``
     Adjoint/Transpose wrappers                                                     :85-87   -> ``Adjoint`` / ``lu(A.T ...)``;
                                                                                              ``ldiv_(Adjoint(F), B)`` solves A' x = b
 
@@ -323,6 +326,135 @@ def ldiv_(F: LU, B, *, handle=None):
     return B
 
 
+def _unwrap_adjoint(F, what: str):
+    if isinstance(F, Adjoint):
+        F = F.parent
+        if isinstance(F, Adjoint):
+            raise TypeError(f"{what} of a doubly wrapped factorization: unwrap it first")
+        return F, True
+    return F, False
+
+
+def _square_factors(F, what: str):
+    """Shape, element type and layout of the factors of ``inv`` / ``det`` / ``logabsdet`` -- before anything touches the library.
+    Returns (A, n, sfx, kind, ld) with kind in "cm" / "rm" (CUDA tensors) / "host" (column-major NumPy)."""
+    if not isinstance(F, LU):
+        raise TypeError(f"{what} needs the LU that lu / lu_ returned")
+    A = F.factors
+    if A is None:
+        raise ValueError(f"{what}: this factorization is no longer valid (inv_ overwrote its factors with the inverse)")
+    if getattr(A, "ndim", None) != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError(f"{what} needs a square factorization")
+    sfx = _sfx(A.dtype)
+    n = int(A.shape[0])
+    if _is_torch(A):
+        if not A.is_cuda:
+            raise _ffi.RfluError("torch factors must live on the MI355X (device='cuda'); host data goes in as NumPy")
+        if not isinstance(F.ipiv, NotIPIV) and not (_is_torch(F.ipiv) and F.ipiv.is_cuda and str(F.ipiv.dtype) == "torch.int64"
+                                                      and F.ipiv.numel() >= n and (n <= 1 or F.ipiv.stride(0) == 1)):
+            raise TypeError("ipiv of GPU factors must be a contiguous int64 CUDA tensor of length n (or NotIPIV)")
+        if n <= 1 or (A.stride(0) == 1 and A.stride(1) >= n):
+            return A, n, sfx, "cm", (int(A.stride(1)) if n > 1 else 1)
+        if A.stride(1) == 1 and A.stride(0) >= n:
+            return A, n, sfx, "rm", int(A.stride(0))
+        raise ValueError(f"{what}: the factors must be dense column-major or row-major (unit stride in one dimension)")
+    if not isinstance(A, np.ndarray):
+        raise TypeError("factors must be a numpy.ndarray or a CUDA torch.Tensor")
+    if not A.flags.f_contiguous:
+        raise ValueError(f"{what}: host factors must be column-major (Fortran-ordered), as lu_ leaves them")
+    return A, n, sfx, "host", max(n, 1)
+
+
+def _ipiv_arg(F, kind: str):
+    """(keep-alive object, pointer) of the pivots: NULL for NotIPIV."""
+    if isinstance(F.ipiv, NotIPIV):
+        return None, ctypes.c_void_p(0)
+    if kind == "host":
+        ip = np.ascontiguousarray(F.ipiv, dtype=np.int64)
+        return ip, ctypes.c_void_p(ip.ctypes.data)
+    return F.ipiv, ctypes.c_void_p(F.ipiv.data_ptr())
+
+
+def _handle_for(A, kind: str, handle):
+    if kind == "host":
+        h = handle or _ffi.default_handle(0)
+        h.set_stream(None)
+        return h, ctypes.c_void_p(A.ctypes.data)
+    import torch
+
+    h = handle or _ffi.default_handle(A.device.index or 0)
+    h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+    return h, ctypes.c_void_p(A.data_ptr())
+
+
+def inv_(F, *, handle=None):
+    """``LinearAlgebra.inv!(F::LU)``: overwrite the factors with ``inv(A)`` (LAPACK getri, ``rflu_getri_*``) and return the array that
+    held them.  About 4n^3/3 flops and no n x n workspace, against 2n^3 and three more n x n arrays for ``ldiv_(F, I)``.
+
+    ``F`` IS INVALID AFTERWARDS: its storage holds the inverse, so ``F.factors`` is set to ``None`` and any later use of ``F`` raises.
+    Use ``inv(F)`` to keep the factorization.  Layout rules exactly as ``ldiv_``: a column-major or row-major CUDA tensor
+    (``rflu_getri_*_dev`` / ``rflu_getri_rm_*_dev``) or a column-major NumPy array (``rflu_getri_*``).  Raises ``SingularException(info)``
+    when ``F.info != 0`` or the library finds an exactly zero ``u_ii`` -- the factors are then untouched and ``F`` stays valid.
+    ``inv_(Adjoint(F))`` returns the transposed view of ``inv_(F)``: inv(A') = inv(A)'."""
+    F, adj = _unwrap_adjoint(F, "inv!")
+    A, n, sfx, kind, ld = _square_factors(F, "inv!")
+    if F.info != 0:
+        raise SingularException(abs(F.info))
+    if n > 0:
+        keep, ip = _ipiv_arg(F, kind)
+        h, ap = _handle_for(A, kind, handle)
+        info = ctypes.c_int64(0)
+        name = {"cm": f"rflu_getri_{sfx}_dev", "rm": f"rflu_getri_rm_{sfx}_dev", "host": f"rflu_getri_{sfx}"}[kind]
+        h.call(name, n, ap, ld, ip, ctypes.byref(info))
+        del keep
+        if info.value != 0:
+            raise SingularException(int(info.value))
+    F.factors = None
+    return A.T if adj else A
+
+
+def inv(F, *, handle=None):
+    """``inv(F::LU)``: ``inv_`` on a copy of the factors; ``F`` stays intact."""
+    G, adj = _unwrap_adjoint(F, "inv")
+    A = _square_factors(G, "inv")[0]
+    C = A.clone() if _is_torch(A) else np.array(A, order="F", copy=True)
+    X = inv_(LU(C, G.ipiv, G.info), handle=handle)
+    return X.T if adj else X
+
+
+def logabsdet(F, *, handle=None):
+    """``logabsdet(F::LU)`` -> ``(log|det A|, sign det A)`` as Python floats (``rflu_logabsdet_*``): the sum of ``log|u_ii|`` in Float64
+    for both element types, the sign from the diagonal's signs and the parity of the interchanges.  Only the diagonal and ``ipiv`` are
+    read (the host entry copies nothing else).  A zero ``u_ii`` gives ``(-inf, 0.0)``, a NaN ``(nan, nan)``; ``n == 0`` gives ``(0.0, 1.0)``.
+    ``Adjoint(F)``: the same value."""
+    F, _ = _unwrap_adjoint(F, "logabsdet")
+    A, n, sfx, kind, ld = _square_factors(F, "logabsdet")
+    if n == 0:
+        return 0.0, 1.0
+    keep, ip = _ipiv_arg(F, kind)
+    h, ap = _handle_for(A, kind, handle)
+    la, sg = ctypes.c_double(0.0), ctypes.c_double(1.0)
+    h.call(f"rflu_logabsdet_{sfx}" + ("" if kind == "host" else "_dev"), n, ap, ld, ip, ctypes.byref(la), ctypes.byref(sg))
+    del keep
+    return float(la.value), float(sg.value)
+
+
+def det(F, *, handle=None) -> float:
+    """``det(F::LU)`` = ``sign * exp(logabs)`` of ``logabsdet``; 0.0 for a singular ``F`` as in Julia.  It differs from Julia's running
+    product of the diagonal by rounding only (and overflows / underflows only where the determinant itself does)."""
+    la, sg = logabsdet(F, handle=handle)
+    with np.errstate(over="ignore"):
+        return 0.0 if sg == 0.0 else sg * float(np.exp(np.float64(la)))
+
+
+def logdet(F, *, handle=None) -> float:
+    """``logdet(F::LU)``: ``log(det A)``; raises ``ValueError`` (Julia: DomainError) for a negative determinant."""
+    la, sg = logabsdet(F, handle=handle)
+    if sg < 0.0:
+        raise ValueError("logdet: the determinant is negative; use logabsdet")
+    return la
+
+
 class NotConvergedError(ArithmeticError):
     """``ldiv_mixed(..., fallback=False)``: the refinement did not reach Float64 backward error within ``max_iter`` steps."""
 
@@ -600,6 +732,76 @@ def ldiv_batched_(F, B, *, trans=False, check=True, handle=None):
         h.call(f"rflu_getrs_batched_{sfx}_dev", batch, n, nrhs, ctypes.c_void_p(A.data_ptr()), ld, stride_f, row_major,
                ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), stride_ip, ctypes.c_void_p(B.data_ptr()), ldb, stride_b, int(bool(trans)))
     return B
+
+
+def _batched_square(F, what: str):
+    F, adj = _unwrap_adjoint(F, what)
+    if not isinstance(F, BatchedLU):
+        raise TypeError(f"{what} needs the BatchedLU that lu_batched_ returned")
+    A = F.factors
+    if not (_is_torch(A) and A.is_cuda) or A.ndim != 3:
+        raise TypeError(f"{what}: the factors must be a 3-D CUDA tensor")
+    if A.shape[1] != A.shape[2]:
+        raise ValueError(f"{what} needs square factorizations")
+    sfx = _sfx(A.dtype)
+    row_major, ld, stride_f = _batched_layout(A, what)
+    return F, adj, A, sfx, row_major, ld, stride_f
+
+
+def inv_batched(F, *, check=True, handle=None):
+    """``inv`` of every matrix of a batch from its factors (``rflu_getri_batched_*_dev``; one launch up to n = 128, no identity tensor
+    anywhere): returns a NEW (batch, n, n) CUDA tensor in the orientation of the factors; ``F`` stays intact.  ``check=True`` raises
+    ``SingularException`` (with ``batch_index``) when some ``F.info`` is non-zero; with ``check=False`` only the singular matrices' own
+    inverses come back non-finite.  ``Adjoint(F)``: the transposed views."""
+    F, adj, A, sfx, row_major, ld, stride_f = _batched_square(F, "inv_batched")
+    import torch
+
+    batch, n = int(A.shape[0]), int(A.shape[1])
+    if _as_bool(check):
+        _check_batched_info(F.info, True)
+    X = torch.empty((batch, n, n), dtype=A.dtype, device=A.device)
+    if not row_major:
+        X = X.transpose(1, 2)
+    if batch > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        nopiv = isinstance(F.ipiv, NotIPIV)
+        stride_ip = 0 if nopiv else (int(F.ipiv.stride(0)) if batch > 1 else max(n, 1))
+        info_t = torch.zeros(batch, dtype=torch.int64, device=A.device)
+        h.call(f"rflu_getri_batched_{sfx}_dev", batch, n, ctypes.c_void_p(A.data_ptr()), ld, stride_f, row_major,
+               ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), stride_ip, ctypes.c_void_p(X.data_ptr()), n, n * n,
+               ctypes.c_void_p(info_t.data_ptr()))
+        if _as_bool(check):
+            _check_batched_info(info_t, True)
+    return X.transpose(1, 2) if adj else X
+
+
+def logabsdet_batched(F, *, handle=None):
+    """``logabsdet`` of every matrix of a batch (``rflu_logabsdet_batched_*_dev``, one launch): ``(logabs, sign)``, two Float64 CUDA
+    tensors of length ``batch``; entry b is bit-identical to ``logabsdet`` on matrix b's factors."""
+    F, _, A, sfx, row_major, ld, stride_f = _batched_square(F, "logabsdet_batched")
+    import torch
+
+    batch, n = int(A.shape[0]), int(A.shape[1])
+    la = torch.zeros(batch, dtype=torch.float64, device=A.device)
+    sg = torch.ones(batch, dtype=torch.float64, device=A.device)
+    if batch > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        nopiv = isinstance(F.ipiv, NotIPIV)
+        stride_ip = 0 if nopiv else (int(F.ipiv.stride(0)) if batch > 1 else max(n, 1))
+        h.call(f"rflu_logabsdet_batched_{sfx}_dev", batch, n, ctypes.c_void_p(A.data_ptr()), ld, stride_f,
+               ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), stride_ip, ctypes.c_void_p(la.data_ptr()), ctypes.c_void_p(sg.data_ptr()))
+    return la, sg
+
+
+def det_batched(F, *, handle=None):
+    """``det`` of every matrix of a batch: ``sign * exp(logabs)`` of ``logabsdet_batched`` (0.0 for a singular matrix), a Float64 CUDA
+    tensor of length ``batch``."""
+    import torch
+
+    la, sg = logabsdet_batched(F, handle=handle)
+    return torch.where(sg == 0, torch.zeros_like(sg), sg * torch.exp(la))
 
 
 def last_path(device: int = 0) -> str:
