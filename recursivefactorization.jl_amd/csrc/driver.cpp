@@ -1,4 +1,4 @@
-// driver.cpp -- host side of librflu.so: handle, the Toledo recursion, and the C ABI of include/rflu.h.
+// driver.cpp -- host side of librflu.so: handle, the Toledo recursion, and the C ABI of include/rflu.h (host-pointer entries: host_entry.cpp).
 //
 // Host control flow restates /root/reference/src/lu.jl:
 //   lu!(A, ipiv, pivot, thread; ...)  (:97-130)  -> rflu_getrf_* : NoPivot identity fill (:111-113), recursion, info
@@ -22,12 +22,9 @@
 #include <cmath>
 #include <new>
 
-#include "rflu_internal.hpp"
+#include "driver.hpp"
 #include "engine.hpp"
-#include "schedule_plan.hpp"
-#include <atomic>
 #include <chrono>
-#include <thread>
 
 namespace rflu {
 
@@ -156,7 +153,7 @@ static void load_handle_env(Handle* h)
 // RFLU_LD_PAD=<elements> adds a padding when that is a multiple of 512 elements (a power-of-two row pitch): measured on MI355X
 // (round 3, N=16384: 82.7 ms / laswp 3.11 TB/s without, 82.3-82.9 ms / 3.0-3.17 TB/s with 16..272 elements) it changes nothing --
 // the HBM address hash already spreads equal columns of consecutive rows over the channels -- so the default is none.
-static int64_t workspace_ld(const Handle* h, int64_t n)
+int64_t workspace_ld(const Handle* h, int64_t n)
 {
     const int64_t pad = h->tune.ld_pad;
     int64_t ld = round_up(std::max<int64_t>(n, 1), 16);
@@ -274,7 +271,7 @@ static int getrs_rm(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_t ld, 
 
 // column-major device entry: F (n x n, lda) and B (n x nrhs, ldb) as LinearAlgebra.LU / LAPACK getrs hold them
 template <typename T>
-static int getrs_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B,
+int getrs_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B,
                         int64_t ldb)
 {
     if (n < 0 || nrhs < 0 || lda < std::max<int64_t>(n, 1) || ldb < std::max<int64_t>(n, 1)) {
@@ -292,38 +289,6 @@ static int getrs_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t 
     RFLU_TRY(launch_transpose<T>(h, n, nrhs, B, ldb, X, ldx));
     RFLU_TRY(getrs_rm<T>(h, n, nrhs, R, ldr, ipiv, X, ldx));
     RFLU_TRY(launch_transpose<T>(h, nrhs, n, X, ldx, B, ldb));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
-
-template <typename T>
-static int getrs_host(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb)
-{
-    if (n < 0 || nrhs < 0 || lda < std::max<int64_t>(n, 1) || ldb < std::max<int64_t>(n, 1) ||
-        (n > 0 && nrhs > 0 && (F == nullptr || B == nullptr))) {
-        set_error("getrs: bad arguments");
-        return RFLU_ERR_ARG;
-    }
-    if (n == 0 || nrhs == 0) return RFLU_OK;
-    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(T)));
-    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * (size_t)nrhs * sizeof(T)));
-    if ((size_t)n > h->ipiv_cap) {
-        if (h->ipiv_dev) RFLU_HIP(hipFree(h->ipiv_dev));
-        h->ipiv_dev = nullptr;
-        h->ipiv_cap = 0;
-        RFLU_HIP(hipMalloc((void**)&h->ipiv_dev, (size_t)n * sizeof(int64_t)));
-        h->ipiv_cap = (size_t)n;
-    }
-    T* dF = static_cast<T*>(h->hostA_dev);
-    T* dB = static_cast<T*>(h->hostB_dev);
-    RFLU_HIP(hipMemcpy2DAsync(dF, (size_t)n * sizeof(T), F, (size_t)lda * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
-                              hipMemcpyHostToDevice, h->stream));
-    RFLU_HIP(hipMemcpy2DAsync(dB, (size_t)n * sizeof(T), B, (size_t)ldb * sizeof(T), (size_t)n * sizeof(T), (size_t)nrhs,
-                              hipMemcpyHostToDevice, h->stream));
-    if (ipiv) RFLU_HIP(hipMemcpyAsync(h->ipiv_dev, ipiv, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    RFLU_TRY(getrs_cm_dev<T>(h, n, nrhs, dF, n, ipiv ? h->ipiv_dev : nullptr, dB, n));
-    RFLU_HIP(hipMemcpy2DAsync(B, (size_t)ldb * sizeof(T), dB, (size_t)n * sizeof(T), (size_t)n * sizeof(T), (size_t)nrhs,
-                              hipMemcpyDeviceToHost, h->stream));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
@@ -359,7 +324,7 @@ static int getrs_trans_view(Handle* h, int64_t n, int64_t nrhs, const T* V, int6
 // lda and the pointer's alignment (the chain kernels fall back to element loads where a 16-byte load would be misaligned); only the
 // right-hand sides change layout.
 template <typename T>
-static int getrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B,
+int getrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B,
                               int64_t ldb)
 {
     if (n < 0 || nrhs < 0 || lda < std::max<int64_t>(n, 1) || ldb < std::max<int64_t>(n, 1)) {
@@ -396,38 +361,6 @@ static int getrs_trans_rm(Handle* h, int64_t n, int64_t nrhs, const T* R, int64_
     return getrs_trans_view<T>(h, n, nrhs, V, ldv, ipiv, B, ldb);
 }
 
-template <typename T>
-static int getrs_trans_host(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb)
-{
-    if (n < 0 || nrhs < 0 || lda < std::max<int64_t>(n, 1) || ldb < std::max<int64_t>(n, 1) ||
-        (n > 0 && nrhs > 0 && (F == nullptr || B == nullptr))) {
-        set_error("getrs_trans: bad arguments");
-        return RFLU_ERR_ARG;
-    }
-    if (n == 0 || nrhs == 0) return RFLU_OK;
-    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(T)));
-    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * (size_t)nrhs * sizeof(T)));
-    if ((size_t)n > h->ipiv_cap) {
-        if (h->ipiv_dev) RFLU_HIP(hipFree(h->ipiv_dev));
-        h->ipiv_dev = nullptr;
-        h->ipiv_cap = 0;
-        RFLU_HIP(hipMalloc((void**)&h->ipiv_dev, (size_t)n * sizeof(int64_t)));
-        h->ipiv_cap = (size_t)n;
-    }
-    T* dF = static_cast<T*>(h->hostA_dev);
-    T* dB = static_cast<T*>(h->hostB_dev);
-    RFLU_HIP(hipMemcpy2DAsync(dF, (size_t)n * sizeof(T), F, (size_t)lda * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
-                              hipMemcpyHostToDevice, h->stream));
-    RFLU_HIP(hipMemcpy2DAsync(dB, (size_t)n * sizeof(T), B, (size_t)ldb * sizeof(T), (size_t)n * sizeof(T), (size_t)nrhs,
-                              hipMemcpyHostToDevice, h->stream));
-    if (ipiv) RFLU_HIP(hipMemcpyAsync(h->ipiv_dev, ipiv, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    RFLU_TRY(getrs_trans_cm_dev<T>(h, n, nrhs, dF, n, ipiv ? h->ipiv_dev : nullptr, dB, n));
-    RFLU_HIP(hipMemcpy2DAsync(B, (size_t)ldb * sizeof(T), dB, (size_t)n * sizeof(T), (size_t)n * sizeof(T), (size_t)nrhs,
-                              hipMemcpyDeviceToHost, h->stream));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
-
 // error flags raised by the cooperative kernels (info_dev[1], copied to info_pinned[1] by the caller)
 static int panel_flags_status(Handle* h)
 {
@@ -457,7 +390,6 @@ static int panel_flags_status(Handle* h)
 
 // C-ABI GEMM.  RFLU_GEMM_MASKED=<reserve> (measurement only): run it on the CU-masked update stream of the lookahead
 // schedule and wait for it, so that scripts/microbench_gemm_k.py can time the kernel on 256 - reserve CUs.
-int get_ustream(Handle* h, int reserve, hipStream_t* out);
 template <typename T>
 static int gemm_public(Handle* h, int64_t M, int64_t N, int64_t K, const T* A, int64_t lda, const T* B, int64_t ldb, T* C,
                        int64_t ldc)
@@ -475,7 +407,7 @@ static int gemm_public(Handle* h, int64_t M, int64_t N, int64_t K, const T* A, i
 }
 
 // the inputs of plan_schedule (schedule_plan.hpp) as the handle has them now
-static SchedIn sched_in(const Handle* h, int64_t m, int64_t n, size_t esize, int pivot, int64_t blocksize, int entry, bool aligned16, int64_t ld)
+SchedIn sched_in(const Handle* h, int64_t m, int64_t n, size_t esize, int pivot, int64_t blocksize, int entry, bool aligned16, int64_t ld)
 {
     SchedIn in;
     in.m = m; in.n = n; in.esize = esize; in.pivot = pivot; in.blocksize = blocksize; in.entry = entry;
@@ -584,7 +516,7 @@ static int get_masked_stream(Handle* h, hipStream_t* slot, int r)
 // While the factorization is update-bound the critical path has time to spare, and the workgroups of ITS GEMMs that land on
 // shared CUs delay the update (scripts/microbench_gemm_vs_rec.py: -2 % on the masked 15872 x 14848 x 512 GEMM) -- so in that
 // phase the critical path is kept on its own CUs (N=16384: 88.1 -> 86.8 ms).
-static int get_pstream(Handle* h, int reserve, hipStream_t* out)
+int get_pstream(Handle* h, int reserve, hipStream_t* out)
 {
     const int r = reserve / 32;
     if (reserve % 32 != 0 || r < 1 || r > 7) { set_error("CU reservation %d not in 32..224 step 32", reserve); return RFLU_ERR_ARG; }
@@ -611,7 +543,7 @@ static int get_pstream(Handle* h, int reserve, hipStream_t* out)
 // the library's masked streams is probed against the caller's stream and the ones already accepted, and replaced by a new one with
 // the same mask (the next queue index) until it shares a pipe with none of them; the rejected streams stay parked, idle.
 // Re-checked when the caller's stream changes (rflu_set_stream) or a new masked stream appears.  RFLU_QUEUE_CHECK=0 skips it.
-static int validate_queues(Handle* h)
+int validate_queues(Handle* h)
 {
     if (!h->tune.queue_check || h->queue_giveup) return RFLU_OK;
     int created = 0;
@@ -976,7 +908,7 @@ static int factor_lookahead(Fact<T>& f, int64_t W, int64_t b_end, hipStream_t* U
 
 // the engine's state block (device) and the pinned host image of its initial value: both or neither (a half-made pair would
 // have the next call write its image through a null pointer); freed by rflu_destroy
-static int ensure_engine_state(Handle* h)
+int ensure_engine_state(Handle* h)
 {
     if (h->eng_state && h->eng_host) return RFLU_OK;
     if (!h->eng_host) RFLU_HIP(hipHostMalloc(&h->eng_host, sizeof(EngState), hipHostMallocDefault));
@@ -1129,7 +1061,7 @@ static int factor_leafwise(Fact<T>& f, const SchedPlan& plan, int64_t b_begin, h
         geo.pivot = f.pivot;
         geo.ahead = plan.eng_ahead;
         const size_t bytes = offsetof(EngState, cb) + (size_t)geo.ncb * sizeof(EngCB);
-        const size_t skip = offsetof(EngState, remaining);   // (the arrival word in front belongs to the feeding stream: getrf_host_engine)
+        const size_t skip = offsetof(EngState, remaining);   // (the arrival word in front belongs to the feeding stream: host_entry.cpp)
         memset(img, 0, bytes);
         for (int cb = 0; cb < geo.ncb; ++cb) {
             EngCB& c = img->cb[cb];
@@ -1444,7 +1376,7 @@ static int factor_leafwise(Fact<T>& f, const SchedPlan& plan, int64_t b_begin, h
 
 // Factor the row-major m x n matrix R in place (see rflu.h for `blocksize`).
 template <typename T>
-static int getrf_rm(Handle* h, int64_t m, int64_t n, T* R, int64_t ld, int64_t* ipiv, int pivot, int64_t blocksize,
+int getrf_rm(Handle* h, int64_t m, int64_t n, T* R, int64_t ld, int64_t* ipiv, int pivot, int64_t blocksize,
                     int64_t* info)
 {
     if (m < 0 || n < 0 || ld < std::max<int64_t>(n, 1) || (m > 0 && n > 0 && R == nullptr)) {
@@ -1537,7 +1469,7 @@ static int getrf_rm(Handle* h, int64_t m, int64_t n, T* R, int64_t ld, int64_t* 
 
 // column-major device entry: R-layout workspace, transpose in, factor, transpose out
 template <typename T>
-static int getrf_cm_dev(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv, int pivot,
+int getrf_cm_dev(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv, int pivot,
                         int64_t blocksize, int64_t* info)
 {
     if (m < 0 || n < 0 || lda < std::max<int64_t>(m, 1) || info == nullptr) {
@@ -1665,18 +1597,6 @@ static int getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, cons
 }
 
 // ---- inv / det / logabsdet from the factors (include/rflu.h; kernels and the two sweeps: inverse.hip) ----------
-static int ensure_ipiv_dev(Handle* h, int64_t n)
-{
-    if ((size_t)n > h->ipiv_cap) {
-        if (h->ipiv_dev) RFLU_HIP(hipFree(h->ipiv_dev));
-        h->ipiv_dev = nullptr;
-        h->ipiv_cap = 0;
-        RFLU_HIP(hipMalloc((void**)&h->ipiv_dev, (size_t)n * sizeof(int64_t)));
-        h->ipiv_cap = (size_t)n;
-    }
-    return RFLU_OK;
-}
-
 template <typename T>
 static int logabsdet_dev(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign)
 {
@@ -1688,27 +1608,6 @@ static int logabsdet_dev(Handle* h, int64_t n, const T* F, int64_t ld, const int
     *sign = 1.0;
     if (n == 0) return RFLU_OK;
     return launch_logabsdet<T>(h, n, F, ld + 1, ipiv, logabs, sign, nullptr);
-}
-
-// host entry: only the diagonal and ipiv travel
-template <typename T>
-static int logabsdet_host(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign)
-{
-    if (n < 0 || ld < std::max<int64_t>(n, 1) || logabs == nullptr || sign == nullptr || (n > 0 && F == nullptr)) {
-        set_error("logabsdet: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
-        return RFLU_ERR_ARG;
-    }
-    *logabs = 0.0;
-    *sign = 1.0;
-    if (n == 0) return RFLU_OK;
-    std::vector<T> diag((size_t)n);
-    for (int64_t i = 0; i < n; ++i) diag[(size_t)i] = F[i * (ld + 1)];
-    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * sizeof(T)));
-    RFLU_TRY(ensure_ipiv_dev(h, n));
-    RFLU_HIP(hipMemcpyAsync(h->hostB_dev, diag.data(), (size_t)n * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    if (ipiv) RFLU_HIP(hipMemcpyAsync(h->ipiv_dev, ipiv, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    RFLU_HIP(hipStreamSynchronize(h->stream));   // `diag` is pageable and leaves scope
-    return launch_logabsdet<T>(h, n, static_cast<const T*>(h->hostB_dev), 1, ipiv ? h->ipiv_dev : nullptr, logabs, sign, nullptr);
 }
 
 template <typename T>
@@ -1741,7 +1640,7 @@ static int logabsdet_batched(Handle* h, int64_t batch, int64_t n, const T* F, in
 // column-major device entry: F read as a row-major array with ld = lda IS the transposed view, and A^-1 column-major IS A^-T row-major:
 // no layout change, whatever lda and the pointer's alignment (misaligned: the GEMM's element-wise loads, same arithmetic)
 template <typename T>
-static int getri_cm_dev(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)
+int getri_cm_dev(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)
 {
     if (n < 0 || lda < std::max<int64_t>(n, 1) || info == nullptr || (n > 0 && F == nullptr)) {
         set_error("getri: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
@@ -1769,29 +1668,6 @@ static int getri_rm(Handle* h, int64_t n, T* R, int64_t ld, const int64_t* ipiv,
     RFLU_TRY(getri_view<T>(h, n, V, ldv, ipiv, info));
     if (*info != 0) return RFLU_OK;
     RFLU_TRY(launch_transpose<T>(h, n, n, V, ldv, R, ld));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
-
-template <typename T>
-static int getri_host(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)
-{
-    if (n < 0 || lda < std::max<int64_t>(n, 1) || info == nullptr || (n > 0 && F == nullptr)) {
-        set_error("getri: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
-        return RFLU_ERR_ARG;
-    }
-    *info = 0;
-    if (n == 0) return RFLU_OK;
-    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(T)));
-    RFLU_TRY(ensure_ipiv_dev(h, n));
-    T* dF = static_cast<T*>(h->hostA_dev);
-    RFLU_HIP(hipMemcpy2DAsync(dF, (size_t)n * sizeof(T), F, (size_t)lda * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
-                              hipMemcpyHostToDevice, h->stream));
-    if (ipiv) RFLU_HIP(hipMemcpyAsync(h->ipiv_dev, ipiv, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    RFLU_TRY(getri_cm_dev<T>(h, n, dF, n, ipiv ? h->ipiv_dev : nullptr, info));
-    if (*info != 0) return RFLU_OK;   // F stays as it is
-    RFLU_HIP(hipMemcpy2DAsync(F, (size_t)lda * sizeof(T), dF, (size_t)n * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
-                              hipMemcpyDeviceToHost, h->stream));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
@@ -1953,428 +1829,21 @@ static int mixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int6
     }
 }
 
-// ---- host entry through the update engine: the way in overlaps the factorization (round 5) -----------------------------------------
-// The reference's boundary is a host array (src/lu.jl:116-121).  Round 3 overlapped the way BACK with the factorization; the way in
-// (38 ms of PCIe for a 16384^2 Float64 matrix) still preceded everything, because the stream schedules' first update touches every
-// column.  The engine's per-column-block dataflow does not: a column block's operations become eligible when its columns have
-// arrived, so the matrix is fed in block column by block column (a second host thread: copies from pageable memory block their
-// caller) -- copy, layout change, a word that says how many columns are in place -- while the critical-path stream, which waits on the
-// same word, factors what is there; finished block rows leave as before, told by a host-visible word the engine keeps
-// (EngArgs::rows_final) instead of events.  Every block column goes through the engine here (no hand-over to the streams).
-// Called where the plan says so (SchedPlan::host_engine).  *handled = false: no CU-masked streams or no pinned memory to be had (the
-// caller falls back to getrf_host's sequence).
-template <typename T>
-static int getrf_host_engine(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv, int pivot, int64_t blocksize,
-                             const SchedPlan& plan, int64_t* info, bool* handled)
-{
-    *handled = false;
-    const int64_t mn = std::min(m, n);
-    const int64_t chunk = h->tune.host_early_out;
-    const int64_t W = plan.Wb;
-    const int64_t ldr = workspace_ld(h, n);
-    hipStream_t E, IN, OUT;
-    RFLU_TRY(get_ustream(h, 32, &E));
-    RFLU_TRY(get_ustream(h, 64, &E));    // (what getrf_rm creates before it settles the queues: nothing new appears afterwards)
-    RFLU_TRY(get_pstream(h, 32, &IN));   // streams confined to the CUs the resident engine leaves free: anything else would wait for it
-    RFLU_TRY(get_pstream(h, 64, &OUT));
-    if (h->mask_failed) return RFLU_OK;
-    RFLU_TRY(validate_queues(h));
-    RFLU_TRY(get_pstream(h, 32, &IN));
-    RFLU_TRY(get_pstream(h, 64, &OUT));
-    // buffers: device copy of the input (kept intact for a failed call), row-major workspace, staging + pinned bounce buffers of the way back
-    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)m * (size_t)n * sizeof(T)));
-    RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)m * (size_t)ldr * sizeof(T)));
-    if ((size_t)mn > h->ipiv_cap) {
-        if (h->ipiv_dev) RFLU_HIP(hipFree(h->ipiv_dev));
-        h->ipiv_dev = nullptr;
-        h->ipiv_cap = 0;
-        RFLU_HIP(hipMalloc((void**)&h->ipiv_dev, (size_t)mn * sizeof(int64_t)));
-        h->ipiv_cap = (size_t)mn;
-    }
-    const size_t bounce_bytes = (size_t)std::min(chunk, m) * (size_t)n * sizeof(T);
-    RFLU_TRY(ensure_buffer(&h->out_stage, &h->out_stage_bytes, 2 * bounce_bytes));
-    if (h->bounce_bytes < bounce_bytes) {
-        for (int i = 0; i < 2; ++i) {
-            if (h->bounce[i]) RFLU_HIP(hipHostFree(h->bounce[i]));
-            h->bounce[i] = nullptr;
-        }
-        h->bounce_bytes = 0;
-        for (int i = 0; i < 2; ++i)
-            if (hipHostMalloc(&h->bounce[i], bounce_bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int k = 0; k < 2; ++k) { if (h->bounce[k]) (void)hipHostFree(h->bounce[k]); h->bounce[k] = nullptr; }
-                return RFLU_OK;   // no pinned memory to be had: the plain sequence needs none
-            }
-        h->bounce_bytes = bounce_bytes;
-    }
-    RFLU_TRY(ensure_engine_state(h));
-    if (!h->eng_rows_final) {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, 64, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); return RFLU_OK; }
-        h->eng_rows_final = static_cast<unsigned long long*>(p);
-        void* d = nullptr;
-        RFLU_HIP(hipHostGetDevicePointer(&d, p, 0));
-        h->eng_rows_final_dev = static_cast<unsigned long long*>(d);
-    }
-    *handled = true;
-    *info = 0;
-    EngState* est = static_cast<EngState*>(h->eng_state);
-    T* dA = static_cast<T*>(h->hostA_dev);
-    T* R = static_cast<T*>(h->work);
-    const hipStream_t user = h->stream;
-    const bool trace = h->tune.host_trace != 0;
-    const auto t_call = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    __atomic_store_n(h->eng_rows_final, 0ull, __ATOMIC_RELEASE);
-    RFLU_HIP(hipMemsetAsync(&est->arrived, 0, sizeof(unsigned long long), user));
-    RFLU_HIP(hipStreamSynchronize(user));   // (whatever the caller had in flight on this stream is done, the arrival word reads 0)
-    // ---- the way in: a thread of its own (a copy from pageable memory returns when the data has left the host)
-    std::atomic<int> feed_status{RFLU_OK};
-    std::atomic<bool> feed_stop{false};
-    const int device = h->device;
-    const int64_t in_cols = std::max<int64_t>(W, 512);
-    std::thread feeder([&, device]() {
-        if (hipSetDevice(device) != hipSuccess) { feed_status = RFLU_ERR_HIP; return; }
-        for (int64_t c0 = 0; c0 < n && !feed_stop.load(); c0 += in_cols) {
-            const int64_t nc = std::min(in_cols, n - c0);
-            if (hipMemcpy2DAsync(dA + c0 * m, (size_t)m * sizeof(T), A + c0 * lda, (size_t)lda * sizeof(T), (size_t)m * sizeof(T), (size_t)nc,
-                                 hipMemcpyHostToDevice, IN) != hipSuccess ||
-                launch_transpose_on<T>(IN, m, nc, dA + c0 * m, m, R + c0, ldr) != RFLU_OK ||
-                launch_gate_signal_on(IN, &est->arrived, (unsigned long long)(c0 + nc)) != RFLU_OK) {
-                feed_status = RFLU_ERR_HIP;
-                return;
-            }
-        }
-    });
-    struct Join { std::thread& t; std::atomic<bool>& stop; ~Join() { stop = true; if (t.joinable()) t.join(); } } join{feeder, feed_stop};
-    // ---- the way back: runs on this thread once the factorization is enqueued (Handle::before_sync), chunk by chunk as the engine
-    // reports block rows final
-    bool scattered = false;
-    size_t ev_used = 0;
-    auto new_event = [h, &ev_used](hipEvent_t* e) -> int {
-        if (ev_used == h->out_events.size()) {
-            hipEvent_t x;
-            RFLU_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-            h->out_events.push_back(x);
-        }
-        *e = h->out_events[ev_used++];
-        return RFLU_OK;
-    };
-    struct Reset { Handle* h; ~Reset() { h->before_sync = nullptr; h->out_done = false; h->eng_host_mode = false; } } reset{h};
-    h->eng_host_mode = true;
-    h->before_sync = [&]() -> int {
-        hipEvent_t all_done;
-        RFLU_TRY(new_event(&all_done));
-        RFLU_HIP(hipEventRecord(all_done, user));   // the whole factorization (the critical-path stream joins the engine's at its end)
-        if (trace) fprintf(stderr, "[rflu] host entry (engine): enqueue done %.1f ms after the call\n", since(t_call));
-        std::vector<int64_t> ends;
-        for (int64_t r = 0; r < m;) { r = std::min(m, r + chunk); ends.push_back(r); }
-        const size_t nchunks = ends.size();
-        std::vector<hipEvent_t> landed(nchunks);
-        auto start_of = [&](size_t k) { return k == 0 ? (int64_t)0 : ends[k - 1]; };
-        bool everything = false;
-        auto wait_final = [&](int64_t r1) -> int {   // rows [0, r1) final: the engine's word, or the end of everything
-            const auto t0 = std::chrono::steady_clock::now();
-            while (!everything && (int64_t)__atomic_load_n(h->eng_rows_final, __ATOMIC_ACQUIRE) < r1) {
-                const hipError_t q = hipEventQuery(all_done);
-                if (q == hipSuccess) { everything = true; break; }
-                if (q != hipErrorNotReady) { set_error("hipEventQuery failed: %s", hipGetErrorString(q)); return RFLU_ERR_HIP; }
-                if (feed_status.load() != RFLU_OK) { set_error("host entry: feeding the matrix to the device failed"); return RFLU_ERR_HIP; }
-                if (since(t0) > 20000.0) { set_error("host entry: no progress for 20 s"); return RFLU_ERR_TIMEOUT; }
-                std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
-            return RFLU_OK;
-        };
-        auto send = [&](size_t k) -> int {   // chunk k: final -> transpose into a contiguous piece of the staging copy -> bounce buffer
-            const int64_t r0 = start_of(k), rows = ends[k] - r0;
-            RFLU_TRY(wait_final(ends[k]));
-            T* piece = static_cast<T*>(h->out_stage) + (k & 1) * (size_t)std::min(chunk, m) * (size_t)n;
-            RFLU_TRY(launch_transpose_on<T>(OUT, n, rows, R + r0 * ldr, ldr, piece, rows));
-            RFLU_HIP(hipMemcpyAsync(h->bounce[k & 1], piece, (size_t)rows * (size_t)n * sizeof(T), hipMemcpyDeviceToHost, OUT));
-            RFLU_TRY(new_event(&landed[k]));
-            RFLU_HIP(hipEventRecord(landed[k], OUT));
-            return RFLU_OK;
-        };
-        const int nthreads = std::max(1, std::min(h->tune.host_threads, 64));
-        for (size_t k = 0; k < std::min<size_t>(2, nchunks); ++k) RFLU_TRY(send(k));
-        for (size_t k = 0; k < nchunks; ++k) {
-            RFLU_HIP(hipEventSynchronize(landed[k]));
-            const int64_t r0 = start_of(k), rows = ends[k] - r0;
-            const T* src = static_cast<const T*>(h->bounce[k & 1]);
-            scattered = true;
-            auto scatter = [&](int64_t j0, int64_t j1) {
-                for (int64_t j = j0; j < j1; ++j) memcpy(A + j * lda + r0, src + j * rows, (size_t)rows * sizeof(T));
-            };
-            if (nthreads == 1 || (size_t)rows * (size_t)n * sizeof(T) < ((size_t)8 << 20)) {
-                scatter(0, n);
-            } else {
-                std::vector<std::thread> pool;
-                const int64_t per = (n + nthreads - 1) / nthreads;
-                int64_t done_to = std::min<int64_t>(n, per);
-                try {
-                    for (int t = 1; t < nthreads; ++t) {
-                        pool.emplace_back(scatter, std::min<int64_t>(n, t * per), std::min<int64_t>(n, (t + 1) * per));
-                        done_to = std::min<int64_t>(n, (t + 1) * per);
-                    }
-                } catch (...) {
-                }
-                scatter(0, std::min<int64_t>(n, per));
-                if (done_to < n) scatter(done_to, n);
-                for (std::thread& th : pool) th.join();
-            }
-            if (trace) fprintf(stderr, "[rflu] host entry (engine): rows [%lld, %lld) home at %.1f ms\n", (long long)r0, (long long)ends[k], since(t_call));
-            if (k + 2 < nchunks) RFLU_TRY(send(k + 2));
-        }
-        h->out_done = true;
-        return RFLU_OK;
-    };
-    int rc = getrf_rm<T>(h, m, n, R, ldr, (pivot || ipiv) ? h->ipiv_dev : nullptr, pivot, blocksize, info);
-    feed_stop = true;
-    if (feeder.joinable()) feeder.join();
-    if (rc == RFLU_OK && feed_status.load() != RFLU_OK) { set_error("host entry: feeding the matrix to the device failed"); rc = feed_status.load(); }
-    if (rc != RFLU_OK) {
-        // a failed call leaves the caller's matrix as it was (the device copy of the input is never written by the factorization)
-        (void)hipDeviceSynchronize();
-        if (scattered)
-            (void)hipMemcpy2D(A, (size_t)lda * sizeof(T), dA, (size_t)m * sizeof(T), (size_t)m * sizeof(T), (size_t)n, hipMemcpyDeviceToHost);
-        return rc;
-    }
-    if (!h->out_done) {   // (cannot happen: before_sync either brings everything home or fails)
-        set_error("host entry: the factors did not travel back");
-        return RFLU_ERR_ARG;
-    }
-    if (ipiv) RFLU_HIP(hipMemcpyAsync(ipiv, h->ipiv_dev, (size_t)mn * sizeof(int64_t), hipMemcpyDeviceToHost, user));
-    RFLU_HIP(hipStreamSynchronize(user));
-    RFLU_HIP(hipStreamSynchronize(IN));
-    return RFLU_OK;
-}
-
-// host entry: stage through device buffers owned by the handle
-template <typename T>
-static int getrf_host(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv, int pivot, int64_t blocksize,
-                      int64_t* info)
-{
-    if (m < 0 || n < 0 || lda < std::max<int64_t>(m, 1) || info == nullptr || (m > 0 && n > 0 && A == nullptr)) {
-        set_error("getrf: bad arguments m=%lld n=%lld lda=%lld", (long long)m, (long long)n, (long long)lda);
-        return RFLU_ERR_ARG;
-    }
-    *info = 0;
-    const int64_t mn = std::min(m, n);
-    if (mn == 0) return RFLU_OK;
-    const SchedPlan p = plan_schedule(sched_in(h, m, n, sizeof(T), pivot, blocksize, ENTRY_HOST, true, workspace_ld(h, n)));   // (workspace: hipMalloc)
-    if (p.host_engine) {   // the way in overlapped with the factorization (the update engine's dataflow waits for columns; the stream schedules cannot)
-        bool handled = false;
-        const int rc = getrf_host_engine<T>(h, m, n, A, lda, ipiv, pivot, blocksize, p, info, &handled);
-        if (handled || rc != RFLU_OK) return rc;
-    }
-    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)m * (size_t)n * sizeof(T)));
-    if ((size_t)mn > h->ipiv_cap) {
-        if (h->ipiv_dev) RFLU_HIP(hipFree(h->ipiv_dev));
-        h->ipiv_dev = nullptr;
-        h->ipiv_cap = 0;
-        RFLU_HIP(hipMalloc((void**)&h->ipiv_dev, (size_t)mn * sizeof(int64_t)));
-        h->ipiv_cap = (size_t)mn;
-    }
-    T* dA = static_cast<T*>(h->hostA_dev);
-    const auto t_call = std::chrono::steady_clock::now();
-    RFLU_HIP(hipMemcpy2DAsync(dA, (size_t)m * sizeof(T), A, (size_t)lda * sizeof(T), (size_t)m * sizeof(T), (size_t)n,
-                              hipMemcpyHostToDevice, h->stream));
-    const auto t_in = std::chrono::steady_clock::now();
-    const bool want_ipiv = (ipiv != nullptr);
-    // ---- the way back, overlapped -------------------------------------------------------------------------------------------
-    // Rows [j0, j0 + W) of the factors are final as soon as block column b has been applied everywhere (later interchanges only
-    // touch rows below), and in the row-major workspace a block of rows is one contiguous piece.  The block-column schedules report
-    // how far that has got while they enqueue (Handle::progress); per chunk of rows the events of every stream are kept.  When
-    // everything is enqueued (Handle::before_sync: 7 ms into an 80 ms factorization at N=16384) the calling thread -- which would only
-    // wait now -- brings the chunks home on a stream of its own: wait for the chunk's events, transpose its rows into a contiguous
-    // column-major piece of the staging copy, one contiguous copy into a pinned bounce buffer of the handle, and from there into the
-    // caller's columns with a few host threads while the next chunk is on the link.  Chunks are 2048 rows while the factorization
-    // has far to go and one block column at the end, so that little is left when the last leaf finishes.
-    // Two things this needs: (1) the fourth stream on a hardware pipe of its own like the other three (validate_queues; round 3
-    // first built this without and measured +26 ms instead of -30); (2) our own bounce buffers: a device-to-host copy into PAGEABLE
-    // memory issued next to the running factorization returns only when the factorization has finished (the same call next to a
-    // single long kernel does not wait: scripts/probes/d2h_block.hip), so the runtime's staging is of no use here.
-    // RFLU_HOST_EARLY_OUT=0: the round-2 sequence (everything after the factorization).
-    const int64_t chunk = h->tune.host_early_out;
-    const bool early = p.host_early;
-    struct Mark { int64_t r1; std::vector<hipEvent_t> ev; };
-    std::vector<Mark> marks;
-    size_t ev_used = 0;
-    hipStream_t C = nullptr;
-    bool scattered = false;   // finished rows have reached the caller's A (they are taken back if the factorization fails after all)
-    struct Reset { Handle* h; ~Reset() { h->progress = nullptr; h->before_sync = nullptr; h->out_done = false; } } reset{h};
-    if (early) {
-        RFLU_TRY(get_ustream(h, 96, &C));   // a masked stream = a queue of its own that validate_queues can place
-        if (h->mask_failed) C = nullptr;
-    }
-    if (early && C) {
-        const size_t bounce_bytes = (size_t)std::min(chunk, m) * (size_t)n * sizeof(T);
-        // outgoing chunks are laid out column-major in a device staging area of their own (two pieces, like the bounce buffers):
-        // the device copy of the INPUT (dA) stays intact until the factorization has succeeded, so that a failure reported
-        // after some rows have already gone home (a panel timeout or placement error is only known at the end) can give the
-        // caller its matrix back, bit for bit
-        if (ensure_buffer(&h->out_stage, &h->out_stage_bytes, 2 * bounce_bytes) != RFLU_OK) C = nullptr;
-    }
-    if (early && C) {
-        const size_t bounce_bytes = (size_t)std::min(chunk, m) * (size_t)n * sizeof(T);
-        if (h->bounce_bytes < bounce_bytes) {
-            for (int i = 0; i < 2; ++i) {
-                if (h->bounce[i]) RFLU_HIP(hipHostFree(h->bounce[i]));
-                h->bounce[i] = nullptr;
-            }
-            h->bounce_bytes = 0;
-            bool ok = true;
-            for (int i = 0; i < 2 && ok; ++i) ok = hipHostMalloc(&h->bounce[i], bounce_bytes) == hipSuccess;
-            if (ok) {
-                h->bounce_bytes = bounce_bytes;
-            } else {   // no pinned memory to be had: the plain sequence (everything after the factorization) needs none
-                (void)hipGetLastError();
-                for (int i = 0; i < 2; ++i) {
-                    if (h->bounce[i]) (void)hipHostFree(h->bounce[i]);
-                    h->bounce[i] = nullptr;
-                }
-                C = nullptr;
-            }
-        }
-    }
-    if (early && C) {
-        const hipStream_t user = h->stream;
-        auto new_event = [h, &ev_used](hipEvent_t* e) -> int {
-            if (ev_used == h->out_events.size()) {
-                hipEvent_t x;
-                RFLU_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-                h->out_events.push_back(x);
-            }
-            *e = h->out_events[ev_used++];
-            return RFLU_OK;
-        };
-        auto mark_all = [h, user, new_event](std::vector<hipEvent_t>& out) -> int {
-            auto rec = [&](hipStream_t st) -> int {
-                hipEvent_t e;
-                RFLU_TRY(new_event(&e));
-                RFLU_HIP(hipEventRecord(e, st));
-                out.push_back(e);
-                return RFLU_OK;
-            };
-            RFLU_TRY(rec(user));
-            if (h->stream != user) RFLU_TRY(rec(h->stream));
-            for (int r = 1; r < 8; ++r) {
-                if (r != 3 && h->ustreams[r]) RFLU_TRY(rec(h->ustreams[r]));
-                if (h->pstreams[r] && h->pstreams[r] != h->stream) RFLU_TRY(rec(h->pstreams[r]));
-            }
-            return RFLU_OK;
-        };
-        h->progress = [&marks, mark_all, m, chunk](int64_t r) -> int {
-            const int64_t have = marks.empty() ? 0 : marks.back().r1;
-            r = std::min(r, m);
-            // far from the end: whole chunks; within one chunk of the end: every report (one block column at a time)
-            if (r <= have || (r - have < chunk && r + chunk < m)) return RFLU_OK;
-            marks.push_back(Mark{std::min(r, have + chunk), {}});
-            return mark_all(marks.back().ev);
-        };
-        h->before_sync = [&, mark_all, new_event]() -> int {
-            {   // whatever is left (rows below the square part of a tall matrix included) is final when everything is: in chunk-sized pieces
-                int64_t have = marks.empty() ? 0 : marks.back().r1;
-                if (have < m) {
-                    std::vector<hipEvent_t> all;
-                    RFLU_TRY(mark_all(all));
-                    while (have < m) {
-                        have = std::min(m, have + chunk);
-                        marks.push_back(Mark{have, all});
-                    }
-                }
-            }
-            // the way-back stream as it is NOW: validate_queues (run by the factorization, after C was first taken) may have parked the
-            // stream of this mask and put a fresh one, on a pipe of its own, in its place
-            RFLU_TRY(get_ustream(h, 96, &C));
-            const int64_t ldr = workspace_ld(h, n);
-            const T* R = static_cast<const T*>(h->work);
-            const hipStream_t saved = h->stream;
-            const bool trace = h->tune.host_trace != 0;
-            auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-            if (trace) fprintf(stderr, "[rflu] host entry: enqueue done %.1f ms after the call (%.1f after the copy in), %zu chunks\n", since(t_call), since(t_in), marks.size());
-            const size_t nchunks = marks.size();
-            std::vector<hipEvent_t> landed(nchunks);
-            std::vector<int64_t> start(nchunks);
-            {
-                int64_t r0 = 0;
-                for (size_t k = 0; k < nchunks; ++k) { start[k] = r0; r0 = marks[k].r1; }
-            }
-            auto send = [&](size_t k) -> int {   // chunk k: events -> transpose into a contiguous piece of the staging copy -> bounce buffer
-                const int64_t r0 = start[k], rows = marks[k].r1 - r0;
-                for (hipEvent_t e : marks[k].ev)
-                    if (hipStreamWaitEvent(C, e, 0) != hipSuccess) { set_error("hipStreamWaitEvent failed"); return RFLU_ERR_HIP; }
-                T* piece = static_cast<T*>(h->out_stage) + (k & 1) * (size_t)std::min(chunk, m) * (size_t)n;
-                h->stream = C;
-                const int rc = launch_transpose<T>(h, n, rows, R + r0 * ldr, ldr, piece, rows);
-                h->stream = saved;
-                RFLU_TRY(rc);
-                RFLU_HIP(hipMemcpyAsync(h->bounce[k & 1], piece, (size_t)rows * (size_t)n * sizeof(T), hipMemcpyDeviceToHost, C));
-                RFLU_TRY(new_event(&landed[k]));
-                RFLU_HIP(hipEventRecord(landed[k], C));
-                return RFLU_OK;
-            };
-            const int nthreads = std::max(1, std::min(h->tune.host_threads, 64));
-            for (size_t k = 0; k < std::min<size_t>(2, nchunks); ++k) RFLU_TRY(send(k));
-            for (size_t k = 0; k < nchunks; ++k) {
-                RFLU_HIP(hipEventSynchronize(landed[k]));
-                const int64_t r0 = start[k], rows = marks[k].r1 - r0;
-                const T* src = static_cast<const T*>(h->bounce[k & 1]);
-                scattered = true;
-                auto scatter = [&](int64_t j0, int64_t j1) {
-                    for (int64_t j = j0; j < j1; ++j) memcpy(A + j * lda + r0, src + j * rows, (size_t)rows * sizeof(T));
-                };
-                if (nthreads == 1 || (size_t)rows * (size_t)n * sizeof(T) < ((size_t)8 << 20)) {
-                    scatter(0, n);
-                } else {
-                    std::vector<std::thread> pool;
-                    const int64_t per = (n + nthreads - 1) / nthreads;
-                    int64_t done_to = std::min<int64_t>(n, per);   // columns [per, done_to) have a thread; no exception leaves this C entry
-                    try {
-                        for (int t = 1; t < nthreads; ++t) {
-                            pool.emplace_back(scatter, std::min<int64_t>(n, t * per), std::min<int64_t>(n, (t + 1) * per));
-                            done_to = std::min<int64_t>(n, (t + 1) * per);
-                        }
-                    } catch (...) {
-                    }
-                    scatter(0, std::min<int64_t>(n, per));
-                    if (done_to < n) scatter(done_to, n);           // the threads that could not be started
-                    for (std::thread& th : pool) th.join();
-                }
-                if (trace) fprintf(stderr, "[rflu] host entry: rows [%lld, %lld) home at %.1f ms\n", (long long)r0, (long long)marks[k].r1, since(t_call));
-                if (k + 2 < nchunks) RFLU_TRY(send(k + 2));   // its bounce buffer is free again
-            }
-            h->out_done = true;
-            return RFLU_OK;
-        };
-    }
-    {
-        const int rc = getrf_cm_dev<T>(h, m, n, dA, m, (pivot || want_ipiv) ? h->ipiv_dev : nullptr, pivot, blocksize, info);
-        if (rc != RFLU_OK) {
-            // A failed call leaves the caller's matrix as it was: rows that went home early are overwritten with the input again
-            // (dA is only ever written after success: the final layout change of getrf_cm_dev).  The error text of rc is kept.
-            if (scattered) {
-                (void)hipDeviceSynchronize();
-                (void)hipMemcpy2D(A, (size_t)lda * sizeof(T), dA, (size_t)m * sizeof(T), (size_t)m * sizeof(T), (size_t)n, hipMemcpyDeviceToHost);
-            }
-            return rc;
-        }
-    }
-    if (!h->out_done)
-        RFLU_HIP(hipMemcpy2DAsync(A, (size_t)lda * sizeof(T), dA, (size_t)m * sizeof(T), (size_t)m * sizeof(T), (size_t)n,
-                                  hipMemcpyDeviceToHost, h->stream));
-    if (want_ipiv)
-        RFLU_HIP(hipMemcpyAsync(ipiv, h->ipiv_dev, (size_t)mn * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
+// ---- what host_entry.cpp calls (driver.hpp) ---------------------------------------------------------------------------------------------
+#define RFLU_INSTANTIATE_DRIVER(T)                                                                                                    \
+    template int getrf_rm<T>(Handle*, int64_t, int64_t, T*, int64_t, int64_t*, int, int64_t, int64_t*);                               \
+    template int getrf_cm_dev<T>(Handle*, int64_t, int64_t, T*, int64_t, int64_t*, int, int64_t, int64_t*);                           \
+    template int getrs_cm_dev<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t);                          \
+    template int getrs_trans_cm_dev<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t);                    \
+    template int getri_cm_dev<T>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);
+RFLU_INSTANTIATE_DRIVER(double)
+RFLU_INSTANTIATE_DRIVER(float)
 
 }  // namespace rflu
 
 using namespace rflu;
 
 static Handle* H(rflu_handle_t h) { return reinterpret_cast<Handle*>(h); }
-namespace rflu { int get_ustream(Handle* h, int reserve, hipStream_t* out); }
 
 // Every API entry runs on the handle's device and leaves the caller's current device as it found it (a framework with
 // tensors on several GPUs must not find its current device changed by a library call).
@@ -2681,7 +2150,7 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
                          T* B, int64_t ldb)                                                                           \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return getrs_host<T>(H(handle), n, nrhs, F, lda, ipiv, B, ldb);                                               \
+        return getrs_host<T>(H(handle), n, nrhs, F, lda, ipiv, B, ldb, false);                                        \
     }                                                                                                                 \
     int rflu_getrs_##SFX##_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const T* F, int64_t lda,                \
                                const int64_t* ipiv, T* B, int64_t ldb)                                                \
@@ -2701,7 +2170,7 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
                                const int64_t* ipiv, T* B, int64_t ldb)                                                \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return getrs_trans_host<T>(H(handle), n, nrhs, F, lda, ipiv, B, ldb);                                         \
+        return getrs_host<T>(H(handle), n, nrhs, F, lda, ipiv, B, ldb, true);                                         \
     }                                                                                                                 \
     int rflu_getrs_trans_##SFX##_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const T* F, int64_t lda,          \
                                      const int64_t* ipiv, T* B, int64_t ldb)                                          \

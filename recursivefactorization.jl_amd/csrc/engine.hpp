@@ -240,7 +240,7 @@ struct EngArgs {
     const unsigned long long* leaf_gate;   // the critical-path stream's counter: gate_base + (leaves completed incl. their lookahead launch)
     unsigned long long gate_base;
     int64_t* info;  // info[1] bit 0: timeout
-    // host entry (driver.cpp: getrf_host_engine): the matrix arrives block column by block column while the factorization runs, and
+    // host entry (host_entry.cpp: getrf_host_engine): the matrix arrives block column by block column while the factorization runs, and
     // finished block rows leave the same way
     const unsigned long long* arrived;     // columns [0, *arrived) of R are in place (nullptr: all of them)
     unsigned long long* rows_final;        // host-visible word: rows [0, *rows_final) of the factors are final (nullptr: nobody asks)

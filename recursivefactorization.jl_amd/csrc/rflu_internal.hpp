@@ -150,7 +150,7 @@ struct Handle {
     hipStream_t ustreams[8] = {};     // ustreams[r]: CU mask leaving 32*r CUs to the critical path (r = 1..7)
     bool mask_failed = false;         // a CU-masked stream could not be created: plain streams may share a hardware queue, so the
                                       // device-side gates (which need the streams to run concurrently) are not used
-    // host-pointer entry (getrf_host): finished block rows travel back while the rest is still being factored
+    // host-pointer entry (host_entry.cpp: getrf_host): finished block rows travel back while the rest is still being factored
     std::function<int(int64_t)> progress;      // called by the block-column schedules: every kernel that writes rows [0, r) is enqueued
     std::function<int()> before_sync;          // called by getrf_rm when the whole factorization is enqueued, before it waits for it
     bool out_done = false;                     // set by before_sync: the factors are already in the caller's buffer
@@ -247,7 +247,7 @@ struct Handle {
     void* eng_host = nullptr;                 // pinned host image of its initial value
     long long* eng_trace_buf = nullptr;       // device: RFLU_ENGINE_TRACE stamps + workgroup-time accounting (measurement only)
     bool eng_active = false;                  // a factorization's engine is resident (factor_leafwise in engine mode .. the join with its stream)
-    // host entry through the engine (driver.cpp: getrf_host_engine): the matrix arrives while it is being factored
+    // host entry through the engine (host_entry.cpp: getrf_host_engine): the matrix arrives while it is being factored
     bool eng_host_mode = false;
     unsigned long long* eng_rows_final = nullptr;       // pinned host word (rows of the factors that are final), ...
     unsigned long long* eng_rows_final_dev = nullptr;   // ... its device address
@@ -389,7 +389,7 @@ template <typename T>
 int launch_panel_pair(Handle* h, T* R, int64_t ld, int64_t m, int64_t r0, int64_t c0, int64_t* ipiv);
 template <typename T>
 int launch_transpose(Handle* h, int64_t rows_out, int64_t cols_out, const T* in, int64_t ld_in, T* out, int64_t ld_out);
-// the same on an explicit stream, touching nothing of the handle (a second host thread feeds the matrix in: getrf_host_engine)
+// the same on an explicit stream, touching nothing of the handle (a second host thread feeds the matrix in: host_entry.cpp, getrf_host_engine)
 template <typename T>
 int launch_transpose_on(hipStream_t st, int64_t rows_out, int64_t cols_out, const T* in, int64_t ld_in, T* out, int64_t ld_out);
 int launch_gate_signal_on(hipStream_t st, unsigned long long* flag, unsigned long long value);

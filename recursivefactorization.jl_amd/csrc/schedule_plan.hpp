@@ -1,5 +1,5 @@
 // schedule_plan.hpp -- which schedule factors a matrix: ONE pure function (plan_schedule) of the call, the handle's tuning and the
-// workspace, used by every entry of driver.cpp and checked on the host by tests/schedule_plan_check.cpp.  No HIP calls, no side effects.
+// workspace, used by every entry of driver.cpp and host_entry.cpp and checked on the host by tests/schedule_plan_check.cpp.  No HIP calls, no side effects.
 //
 // Which schedule serves which call (blocksize = 0 unless stated; W = the block width, default_blocksize below; sections: DESIGN.md):
 //
@@ -38,7 +38,7 @@ namespace rflu {
 enum SchedEntry {
     ENTRY_RM = 0,           // row-major device matrix (rflu_getrf_*_rm), and getrf_rm under the column-major entry
     ENTRY_CM = 1,           // column-major device matrix (getrf_cm_dev): the layout change in front
-    ENTRY_HOST = 2,         // host matrix (getrf_host): through the engine, or staged through the column-major entry
+    ENTRY_HOST = 2,         // host matrix (host_entry.cpp: getrf_host): through the engine, or staged through the column-major entry
     ENTRY_HOST_ENGINE = 3,  // getrf_rm under the host entry through the engine (Handle::eng_host_mode)
 };
 

@@ -1,4 +1,4 @@
-"""Host-pointer entry at sizes where the transfers overlap the factorization (driver.cpp: getrf_host / getrf_host_engine, n >= 8192).
+"""Host-pointer entry at sizes where the transfers overlap the factorization (host_entry.cpp: getrf_host / getrf_host_engine, n >= 8192).
 Stream schedules (Float32, NoPivot, fat matrices, RFLU_ENGINE_HOST=0): finished block rows leave through a fourth stream, pinned
 bounce buffers and a threaded scatter into the caller's columns while the rest is factored -- same factors, pivots and info as the
 device entry, to the bit.  Float64 with pivoting, square or tall (round 5): the matrix also ARRIVES while it is factored, through the
