@@ -244,6 +244,47 @@ int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, c
                                int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* Ainv_dev, int64_t ldi,
                                int64_t strideI, int64_t* info_dev);
 
+/* ---- COMPLEX: lu! / ldiv! for ComplexF64 / ComplexF32 (suffixes _cf64 / _cf32; csrc/complex.hip, csrc/complex_gemm.hip, DESIGN.md
+ * section 4.5).  The reference's lu! with a complex element type (src/lu.jl:97-130, :189-263, :290-338; test/runtests.jl:33-84).
+ * A complex array crosses the boundary as double* / float* pointing at INTERLEAVED (re, im) pairs, the storage of Julia's Complex{T}
+ * and numpy's complex128 / complex64; every lda / ldb / ldc counts COMPLEX elements.  A pointer aligned to the real type is enough.
+ *   - pivot of column k: the row with the largest MODULUS abs(z) = hypot(re, im) in the element's real precision, strict '>' from 0, so
+ *     the lowest row wins a tie and a NaN modulus never wins.  This is the reference's rule, NOT LAPACK's |re| + |im|: LAPACK's ipiv is
+ *     no comparator for these entries;
+ *   - a pivot is zero when both parts are: *info is set once (positive, 1-based) and the elimination carries on; the host glue applies
+ *     the NoPivot sign flip and `check`.  Scaling multiplies by inv(pivot), formed once per column;
+ *   - ipiv, pivot, NULL = NotIPIV (with pivot == 0 only; a non-NULL ipiv is then filled with 1..min(m,n)) as for rflu_getrf_f64_dev;
+ *     any m, n >= 0, fat matrices get the reference's tail (src/lu.jl:148-154); m == 0 or n == 0: success, nothing launched.  There is
+ *     no blocksize: one schedule, the Toledo recursion on the handle's stream down to leaves of 32 columns, all of its n^3 work in the
+ *     complex MFMA GEMM; rflu_last_path reports RFLU_PATH_HIP_RECURSIVE.  No size cliff, no CPU fallback;
+ *   - every kernel is an in-order launch on the handle's stream and NONE waits for another workgroup: no cooperative launch, no flag,
+ *     no RFLU_ERR_TIMEOUT from these entries.  Work is complete on return;
+ *   - rflu_getrs_*: ldiv!(F, B) for any nrhs, F / ipiv as the factorization left them; a singular U yields Inf/NaN, no error status.
+ *     There is no complex ldiv!(F', B) (adjoint and transpose differ here), no batched / mixed / inverse form;
+ *   - the host entries: H2D, the device entry, D2H -- only on success, so a failed call leaves the caller's arrays as they were. */
+int rflu_getrf_cf64(rflu_handle_t handle, int64_t m, int64_t n, double* A_host, int64_t lda, int64_t* ipiv_host, int pivot,
+                    int64_t* info);
+int rflu_getrf_cf32(rflu_handle_t handle, int64_t m, int64_t n, float* A_host, int64_t lda, int64_t* ipiv_host, int pivot,
+                    int64_t* info);
+int rflu_getrf_cf64_dev(rflu_handle_t handle, int64_t m, int64_t n, double* A_dev, int64_t lda, int64_t* ipiv_dev, int pivot,
+                        int64_t* info);
+int rflu_getrf_cf32_dev(rflu_handle_t handle, int64_t m, int64_t n, float* A_dev, int64_t lda, int64_t* ipiv_dev, int pivot,
+                        int64_t* info);
+int rflu_getrs_cf64(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* F_host, int64_t lda, const int64_t* ipiv_host,
+                    double* B_host, int64_t ldb);
+int rflu_getrs_cf32(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_host, int64_t lda, const int64_t* ipiv_host,
+                    float* B_host, int64_t ldb);
+int rflu_getrs_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* F_dev, int64_t lda, const int64_t* ipiv_dev,
+                        double* B_dev, int64_t ldb);
+int rflu_getrs_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda, const int64_t* ipiv_dev,
+                        float* B_dev, int64_t ldb);
+/* building block: C <- C - A*B, all row-major complex: A is M x K (lda), B is K x N (ldb), C is M x N (ldc).  Four real MFMA products
+ * per K step; 16-byte loads where the pointers (and, for _cf32, even lda / ldb) allow, element by element otherwise -- same arithmetic. */
+int rflu_gemm_rm_cf64_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K, const double* A_dev, int64_t lda,
+                          const double* B_dev, int64_t ldb, double* C_dev, int64_t ldc);
+int rflu_gemm_rm_cf32_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K, const float* A_dev, int64_t lda,
+                          const float* B_dev, int64_t ldb, float* C_dev, int64_t ldc);
+
 /* ---- MIXED PRECISION: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme) ----
  * The Float32 factorization is the faster one; refinement with Float64 residuals r = b - A x brings the solution to Float64 backward
  * error when A is not too ill-conditioned for its Float32 factors (kappa well below 1 / eps32), and says so when it does not.

@@ -13,7 +13,7 @@ Surface (the reference's own, `src/lu.jl:19-21, 67-83, 97-130`):
     RFLUAMD.lu!(A, ipiv, pivot = Val(true), thread = Val(false); check, blocksize, threshold)   # what RFLUFactorization calls
 
 returning a genuine `LinearAlgebra.LU(A, ipiv, info)` that aliases the caller's arrays.  `Float64` / `Float32` strided
-column-major matrices with at least `GPU_MIN_N[]` columns go to the GPU; everything else (other element types, non-strided
+column-major matrices with at least `GPU_MIN_N[]` columns go to the GPU (so do `ComplexF64` / `ComplexF32` ones, for `lu!` and `ldiv!(F, B)`); everything else (other element types, non-strided
 storage, small sizes, no device) goes to `RecursiveFactorization.lu!` when that package is loaded, else to
 `LinearAlgebra.lu!`/`generic_lufact!` -- the same fall-back rules the reference applies (`src/lu.jl:74-77, 92-93, 114-126`).
 """
@@ -188,6 +188,82 @@ function getrs!(F::StridedMatrix{Float32}, ipiv::Ptr{Int64}, B::StridedVecOrMat{
     return B
 end
 
+# ---- ComplexF64 / ComplexF32 (rflu_get{rf,rs}_cf64 / _cf32, include/rflu.h): the same interleaved storage as Julia's Complex{T}, so the
+# pointers are `reinterpret`ed to the real type and every leading dimension stays in complex elements.  No blocksize: one schedule.
+function getrf!(A::StridedMatrix{ComplexF64}, ipiv::Ptr{Int64}, pivot::Bool, blocksize::Integer)
+    m, n = size(A)
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getrf_cf64, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Cint, Ref{Int64}),
+               handle(), m, n, reinterpret(Ptr{Float64}, pointer(A)), stride(A, 2), ipiv, Cint(pivot), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return BlasInt(info[])
+end
+
+function getrf!(A::StridedMatrix{ComplexF32}, ipiv::Ptr{Int64}, pivot::Bool, blocksize::Integer)
+    m, n = size(A)
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getrf_cf32, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Cint, Ref{Int64}),
+               handle(), m, n, reinterpret(Ptr{Float32}, pointer(A)), stride(A, 2), ipiv, Cint(pivot), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return BlasInt(info[])
+end
+
+"device-resident complex variant: `A` points at interleaved (re, im) pairs in HBM, `lda` in complex elements"
+function getrf_complex_dev!(A::Ptr{Float64}, m::Integer, n::Integer, lda::Integer, ipiv::Ptr{Int64}, pivot::Bool)
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getrf_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Cint, Ref{Int64}),
+               handle(), m, n, A, lda, ipiv, Cint(pivot), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return BlasInt(info[])
+end
+
+function getrf_complex_dev!(A::Ptr{Float32}, m::Integer, n::Integer, lda::Integer, ipiv::Ptr{Int64}, pivot::Bool)
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getrf_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Cint, Ref{Int64}),
+               handle(), m, n, A, lda, ipiv, Cint(pivot), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return BlasInt(info[])
+end
+
+"`ldiv!(F, B)` for complex factors on the GPU (there is no complex `ldiv!(F', B)`: that one stays with the stdlib)"
+function getrs!(F::StridedMatrix{ComplexF64}, ipiv::Ptr{Int64}, B::StridedVecOrMat{ComplexF64})
+    n = size(F, 1)
+    st = ccall((:rflu_getrs_cf64, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Int64),
+               handle(), n, size(B, 2), reinterpret(Ptr{Float64}, pointer(F)), stride(F, 2), ipiv, reinterpret(Ptr{Float64}, pointer(B)), B isa AbstractVector ? n : stride(B, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+function getrs!(F::StridedMatrix{ComplexF32}, ipiv::Ptr{Int64}, B::StridedVecOrMat{ComplexF32})
+    n = size(F, 1)
+    st = ccall((:rflu_getrs_cf32, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float32}, Int64),
+               handle(), n, size(B, 2), reinterpret(Ptr{Float32}, pointer(F)), stride(F, 2), ipiv, reinterpret(Ptr{Float32}, pointer(B)), B isa AbstractVector ? n : stride(B, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+function getrs_complex_dev!(F::Ptr{Float64}, n::Integer, nrhs::Integer, lda::Integer, ipiv::Ptr{Int64}, B::Ptr{Float64}, ldb::Integer)
+    st = ccall((:rflu_getrs_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Int64),
+               handle(), n, nrhs, F, lda, ipiv, B, ldb)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+function getrs_complex_dev!(F::Ptr{Float32}, n::Integer, nrhs::Integer, lda::Integer, ipiv::Ptr{Int64}, B::Ptr{Float32}, ldb::Integer)
+    st = ccall((:rflu_getrs_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float32}, Int64),
+               handle(), n, nrhs, F, lda, ipiv, B, ldb)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
 "`ldiv!(F', B)` / `ldiv!(transpose(F), B)` on the GPU: B <- P^T L^-T U^-T B (LAPACK getrs with trans = 'T'; real types, so one routine)"
 function getrs_trans!(F::StridedMatrix{Float64}, ipiv::Ptr{Int64}, B::StridedVecOrMat{Float64})
     n = size(F, 1)
@@ -348,8 +424,9 @@ function logabsdet_batched_dev!(logabs::Ptr{Float64}, sign::Ptr{Float64}, F::Ptr
 end
 
 # ---- dispatch: who serves a call (RecursiveFactorization src/lu.jl:92-93, 114-126) -------------------------------------------
-const GPUEltype = Union{Float32, Float64}
-gpu_ok(A::StridedMatrix{<:GPUEltype}, ipiv) =
+const GPUEltype = Union{Float32, Float64}                                  # every entry serves these
+const GPUAnyEltype = Union{Float32, Float64, ComplexF32, ComplexF64}       # lu! and ldiv!(F, B) serve the complex types as well
+gpu_ok(A::StridedMatrix{<:GPUAnyEltype}, ipiv) =
     stride(A, 1) == 1 && min(size(A)...) >= GPU_MIN_N[] && (ipiv isa Vector{Int64} || ipiv isa NotIPIV) && available()
 gpu_ok(A, ipiv) = false
 
@@ -398,7 +475,7 @@ for (f, T) in [(:adjoint, :Adjoint), (:transpose, :Transpose)], lufn in (:lu, :l
 end
 
 "solve with the factors on the GPU when they are large enough, else stdlib `ldiv!`"
-function ldiv!(F::LU{T, <:StridedMatrix{T}}, B::StridedVecOrMat{T}) where {T <: GPUEltype}
+function ldiv!(F::LU{T, <:StridedMatrix{T}}, B::StridedVecOrMat{T}) where {T <: GPUAnyEltype}
     # the same layout conditions as `gpu_ok` for lu!: getrs! passes stride(F, 2) / stride(B, 2) as leading dimensions, i.e. it
     # assumes unit row stride and a square factorization; anything else (a strided view, an LU from a non-unit-stride CPU
     # fallback, a B with the wrong number of rows) stays with the stdlib

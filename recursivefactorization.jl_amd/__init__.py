@@ -26,6 +26,7 @@ from .lu import (  # noqa: F401
     last_path,
     ldiv_,
     ldiv_batched_,
+    ldiv_complex_,
     ldiv_mixed,
     logabsdet,
     logabsdet_batched,
@@ -34,6 +35,8 @@ from .lu import (  # noqa: F401
     lu_,
     lu_batched,
     lu_batched_,
+    lu_complex,
+    lu_complex_,
     lu_mixed,
     normalize_pivot,
 )
@@ -51,6 +54,7 @@ __all__ = [
     "linsolve",
     "ButterflyWorkspace", "butterfly_workspace", "butterfly_solve_", "butterfly_mul_",
     "lu", "lu_", "ldiv_", "LU", "lu_batched", "lu_batched_", "ldiv_batched_", "BatchedLU", "lu_mixed", "ldiv_mixed", "MixedLU", "NotConvergedError", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
+    "lu_complex", "lu_complex_", "ldiv_complex_",
     "inv", "inv_", "det", "logabsdet", "logdet", "inv_batched", "logabsdet_batched", "det_batched",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

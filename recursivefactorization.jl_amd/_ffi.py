@@ -85,9 +85,21 @@ _PLAIN = {
     "rflu_profile_get_bytes": (c_int, [c_p, c_int, ctypes.POINTER(c_dbl)]),
 }
 
+# ComplexF64 / ComplexF32: interleaved (re, im) behind the pointers, leading dimensions in complex elements; no blocksize
+_COMPLEX = {
+    "rflu_getrf_{s}": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_p]),
+    "rflu_getrf_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_p]),
+    "rflu_getrs_{s}": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64]),
+    "rflu_getrs_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64]),
+    "rflu_gemm_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64]),
+}
+
 EXPORTS = dict(_PLAIN)
 for _k, _v in _TYPED.items():
     for _s in ("f64", "f32"):
+        EXPORTS[_k.format(s=_s)] = _v
+for _k, _v in _COMPLEX.items():
+    for _s in ("cf64", "cf32"):
         EXPORTS[_k.format(s=_s)] = _v
 
 K_GEMM, K_TRSM, K_LASWP, K_PANEL, K_TRANSPOSE, K_MISC = range(6)

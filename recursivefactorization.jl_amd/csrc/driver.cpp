@@ -22,6 +22,7 @@
 #include <cmath>
 #include <new>
 
+#include "complex.hpp"
 #include "driver.hpp"
 #include "engine.hpp"
 #include <chrono>
@@ -2317,6 +2318,41 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
     if (nw) RFLU_HIP(hipMemcpy(out, (char*)h->pscratch + panel_trace_all_offset_bytes(), nw * sizeof(long long), hipMemcpyDeviceToHost));
     return (int)nw;
 }
+
+// ComplexF64 / ComplexF32 (complex.hip, complex_gemm.hip): interleaved (re, im) pairs behind R*, leading dimensions in complex elements
+#define DEFINE_COMPLEX(SFX, R)                                                                                        \
+    int rflu_getrf_##SFX(rflu_handle_t handle, int64_t m, int64_t n, R* A, int64_t lda, int64_t* ipiv, int pivot,     \
+                         int64_t* info)                                                                               \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetrf_host<R>(H(handle), m, n, A, lda, ipiv, pivot, info);                                            \
+    }                                                                                                                 \
+    int rflu_getrf_##SFX##_dev(rflu_handle_t handle, int64_t m, int64_t n, R* A, int64_t lda, int64_t* ipiv,          \
+                               int pivot, int64_t* info)                                                              \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetrf_cm_dev<R>(H(handle), m, n, A, lda, ipiv, pivot, info);                                          \
+    }                                                                                                                 \
+    int rflu_getrs_##SFX(rflu_handle_t handle, int64_t n, int64_t nrhs, const R* F, int64_t lda, const int64_t* ipiv, \
+                         R* B, int64_t ldb)                                                                           \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetrs_host<R>(H(handle), n, nrhs, F, lda, ipiv, B, ldb);                                              \
+    }                                                                                                                 \
+    int rflu_getrs_##SFX##_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const R* F, int64_t lda,                \
+                               const int64_t* ipiv, R* B, int64_t ldb)                                                \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetrs_cm_dev<R>(H(handle), n, nrhs, F, lda, ipiv, B, ldb);                                            \
+    }                                                                                                                 \
+    int rflu_gemm_rm_##SFX##_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K, const R* A, int64_t lda,      \
+                                 const R* B, int64_t ldb, R* C, int64_t ldc)                                          \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgemm_public<R>(H(handle), M, N, K, A, lda, B, ldb, C, ldc);                                           \
+    }
+DEFINE_COMPLEX(cf64, double)
+DEFINE_COMPLEX(cf32, float)
 
 }  // extern "C" (the multi-GPU internals below are C++)
 

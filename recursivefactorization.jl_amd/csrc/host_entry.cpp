@@ -9,6 +9,7 @@
 #include <chrono>
 #include <thread>
 
+#include "complex.hpp"
 #include "driver.hpp"
 #include "engine.hpp"
 #include "host_wayback.hpp"
@@ -420,6 +421,50 @@ int getrf_host(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv
     return RFLU_OK;
 }
 
+// ---- ComplexF64 / ComplexF32 (complex.hip): H2D, the device entry, D2H -- the factors travel only after success, so a failed call
+// leaves the caller's matrix as it was.  R* points at interleaved (re, im) pairs, lda / ldb count complex elements.
+template <typename R>
+struct HostCx { R re, im; };
+
+template <typename R>
+int cgetrf_host(Handle* h, int64_t m, int64_t n, R* A, int64_t lda, int64_t* ipiv, int pivot, int64_t* info)
+{
+    typedef HostCx<R> Z;
+    RFLU_TRY(cgetrf_check_args(m, n, A, lda, ipiv, pivot, info));
+    *info = 0;
+    const int64_t mn = std::min(m, n);
+    if (mn == 0) return RFLU_OK;
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)m * (size_t)n * sizeof(Z)));
+    RFLU_TRY(ensure_ipiv_dev(h, mn));
+    Z* dA = static_cast<Z*>(h->hostA_dev);
+    RFLU_TRY(copy_in(dA, reinterpret_cast<const Z*>(A), lda, m, n, h->stream));
+    RFLU_TRY(cgetrf_cm_dev<R>(h, m, n, reinterpret_cast<R*>(dA), m, ipiv ? h->ipiv_dev : nullptr, pivot, info));
+    RFLU_TRY(copy_out(reinterpret_cast<Z*>(A), lda, dA, m, n, h->stream));
+    if (ipiv) RFLU_HIP(hipMemcpyAsync(ipiv, h->ipiv_dev, (size_t)mn * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+template <typename R>
+int cgetrs_host(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, const int64_t* ipiv, R* B, int64_t ldb)
+{
+    typedef HostCx<R> Z;
+    RFLU_TRY(cgetrs_check_args(n, nrhs, F, lda, B, ldb));
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(Z)));
+    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * (size_t)nrhs * sizeof(Z)));
+    Z* dF = static_cast<Z*>(h->hostA_dev);
+    Z* dB = static_cast<Z*>(h->hostB_dev);
+    const int64_t* dipiv;
+    RFLU_TRY(copy_in(dF, reinterpret_cast<const Z*>(F), lda, n, n, h->stream));
+    RFLU_TRY(copy_in(dB, reinterpret_cast<const Z*>(B), ldb, n, nrhs, h->stream));
+    RFLU_TRY(stage_ipiv(h, ipiv, n, &dipiv));
+    RFLU_TRY(cgetrs_cm_dev<R>(h, n, nrhs, reinterpret_cast<const R*>(dF), n, dipiv, reinterpret_cast<R*>(dB), n));
+    RFLU_TRY(copy_out(reinterpret_cast<Z*>(B), ldb, dB, n, nrhs, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 #define RFLU_INSTANTIATE_HOST(T)                                                                                                      \
     template int getrf_host<T>(Handle*, int64_t, int64_t, T*, int64_t, int64_t*, int, int64_t, int64_t*);                             \
     template int getrs_host<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t, bool);                      \
@@ -427,5 +472,10 @@ int getrf_host(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv
     template int logabsdet_host<T>(Handle*, int64_t, const T*, int64_t, const int64_t*, double*, double*);
 RFLU_INSTANTIATE_HOST(double)
 RFLU_INSTANTIATE_HOST(float)
+#define RFLU_INSTANTIATE_HOST_COMPLEX(R)                                                                                              \
+    template int cgetrf_host<R>(Handle*, int64_t, int64_t, R*, int64_t, int64_t*, int, int64_t*);                                     \
+    template int cgetrs_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t);
+RFLU_INSTANTIATE_HOST_COMPLEX(double)
+RFLU_INSTANTIATE_HOST_COMPLEX(float)
 
 }  // namespace rflu

@@ -13,6 +13,9 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
     NoPivot failures carry a NEGATIVE info on Julia >= 1.11                        :25,250,324 -> ``NOPIVOT_NEGATIVE_INFO``
     (no counterpart here; LinearSolve.jl's RF32MixedLUFactorization: Float32 factors,      -> ``lu_mixed`` / ``ldiv_mixed`` / ``MixedLU``
      Float64 iterative refinement)
+    lu / lu! / ldiv! with T = ComplexF64 / ComplexF32 (test/runtests.jl:33-84)              -> ``lu_complex`` / ``lu_complex_`` /
+                                                                                             ``ldiv_complex_`` (names of their own: ``lu``
+                                                                                             keeps raising ``TypeError`` on complex input)
     inv / inv!, det, logabsdet, logdet on the LU object (stdlib LinearAlgebra)            -> ``inv`` / ``inv_`` / ``det`` / ``logabsdet`` /
                                                                                              ``logdet``; batched: ``inv_batched`` /
                                                                                              ``logabsdet_batched`` / ``det_batched``
@@ -176,8 +179,8 @@ def _sfx(dtype) -> str:
     if name == "float32":
         return "f32"
     raise TypeError(
-        f"the MI355X LU path serves Float64/Float32 only (got {dtype}); the reference routes other element types "
-        "through its generic CPU code (src/lu.jl:122-123), which this package does not carry"
+        f"lu / lu_ serve Float64/Float32 only (got {dtype}); ComplexF64/ComplexF32 matrices go to lu_complex / lu_complex_, and the "
+        "reference routes other element types through its generic CPU code (src/lu.jl:122-123), which this package does not carry"
     )
 
 
@@ -323,6 +326,143 @@ def ldiv_(F: LU, B, *, handle=None):
     ipiv = None if nopiv else np.ascontiguousarray(F.ipiv, dtype=np.int64)
     h.call(f"rflu_getrs_{trans}{sfx}", n, nrhs, ctypes.c_void_p(A.ctypes.data), max(n, 1),
            ctypes.c_void_p(0 if ipiv is None else ipiv.ctypes.data), ctypes.c_void_p(B.ctypes.data), max(n, 1))
+    return B
+
+
+def _csfx(dtype) -> str:
+    name = str(dtype).replace("torch.", "")
+    if name == "complex128":
+        return "cf64"
+    if name == "complex64":
+        return "cf32"
+    raise TypeError(f"lu_complex / lu_complex_ serve ComplexF64/ComplexF32 only (got {dtype}); real matrices go to lu / lu_")
+
+
+def lu_complex_(A, ipiv=None, pivot=True, thread=False, *, check=True, blocksize=None, threshold=None, handle=None) -> LU:
+    """``lu!`` for a ``complex128`` / ``complex64`` matrix, in place (``rflu_getrf_cf64`` / ``rflu_getrf_cf32`` and their ``_dev`` forms).
+
+    The pivot of a column is the row of largest modulus ``abs(z)`` (strict ``>``, the lowest row on ties) -- the reference's rule, not
+    LAPACK's ``|re| + |im|``, so ``scipy.linalg.lu_factor`` may choose other rows.  ``A``: a column-major NumPy array (host entry) or a
+    column-major CUDA tensor (``stride(0) == 1``, device entry); row-major storage is refused.  Returns the same ``LU`` as ``lu_``:
+    ``ipiv``, ``info``, ``check`` -> ``SingularException`` and the NoPivot sign of ``info`` follow the same rules.  ``blocksize``,
+    ``threshold`` and ``thread`` are accepted and ignored: the complex path has one schedule, the Toledo recursion on one stream."""
+    del thread, threshold, blocksize
+    if isinstance(A, Adjoint):
+        return Adjoint(lu_complex_(A.parent, ipiv, pivot, check=check, handle=handle))
+    piv = normalize_pivot(pivot)
+    info = ctypes.c_int64(0)
+    if getattr(A, "ndim", None) != 2:
+        raise ValueError("lu! needs a matrix")
+    m, n = int(A.shape[0]), int(A.shape[1])
+    mn = min(m, n)
+
+    if _is_torch(A):
+        import torch
+
+        if not A.is_cuda:
+            raise _ffi.RfluError("torch input must live on the MI355X (device='cuda'); host data goes in as NumPy")
+        sfx = _csfx(A.dtype)
+        if m > 1 and n > 0 and not (A.stride(0) == 1 and (n <= 1 or A.stride(1) >= m)):
+            raise ValueError("lu_complex_ works in place on column-major tensors (stride(0) == 1); use lu_complex() to copy")
+        if ipiv is None:
+            ipiv_t = torch.empty(mn, dtype=torch.int64, device=A.device) if piv else None
+        else:
+            ipiv_t = ipiv
+            if not (_is_torch(ipiv_t) and ipiv_t.is_cuda and ipiv_t.dtype == torch.int64 and ipiv_t.is_contiguous()):
+                raise TypeError("ipiv for a GPU matrix must be a contiguous int64 CUDA tensor")
+            if ipiv_t.numel() < mn:
+                raise ValueError("ipiv is shorter than min(m, n)")
+        if m > 0 and n > 0:
+            h = handle or _ffi.default_handle(A.device.index or 0)
+            h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+            h.call(f"rflu_getrf_{sfx}_dev", m, n, ctypes.c_void_p(A.data_ptr()), A.stride(1) if n > 1 else max(m, 1),
+                   ctypes.c_void_p(ipiv_t.data_ptr() if ipiv_t is not None else 0), int(piv), ctypes.byref(info))
+        out_ipiv = ipiv_t if ipiv_t is not None else NotIPIV(mn)
+    else:
+        if not isinstance(A, np.ndarray):
+            raise TypeError("A must be a numpy.ndarray or a CUDA torch.Tensor")
+        sfx = _csfx(A.dtype)
+        if not A.flags.f_contiguous:
+            raise ValueError("lu! works in place on column-major (Fortran-ordered) arrays; use lu() to copy")
+        if ipiv is None:
+            ipiv_a = np.empty(mn, dtype=np.int64) if piv else None
+        else:
+            ipiv_a = ipiv
+            if not (isinstance(ipiv_a, np.ndarray) and ipiv_a.dtype == np.int64 and ipiv_a.flags.c_contiguous):
+                raise TypeError("ipiv must be a contiguous int64 numpy array (Julia BlasInt)")
+            if ipiv_a.size < mn:
+                raise ValueError("ipiv is shorter than min(m, n)")
+        if m > 0 and n > 0:
+            h = handle or _ffi.default_handle(0)
+            h.set_stream(None)
+            h.call(f"rflu_getrf_{sfx}", m, n, ctypes.c_void_p(A.ctypes.data), max(m, 1),
+                   ctypes.c_void_p(ipiv_a.ctypes.data if ipiv_a is not None else 0), int(piv), ctypes.byref(info))
+        out_ipiv = ipiv_a if ipiv_a is not None else NotIPIV(mn)
+
+    inf = int(info.value)
+    if not piv and NOPIVOT_NEGATIVE_INFO:
+        inf = -inf
+    if _as_bool(check):
+        _checknonsingular(inf)
+    return LU(A, out_ipiv, inf)
+
+
+def lu_complex(A, pivot=True, thread=False, **kwargs) -> LU:
+    """``lu`` for a complex matrix: ``lu_complex_`` on a column-major copy."""
+    if isinstance(A, Adjoint):
+        return Adjoint(lu_complex(A.parent, pivot, thread, **kwargs))
+    if _is_torch(A):
+        C = A.T.contiguous().T   # column-major copy
+        if C.data_ptr() == A.data_ptr():
+            C = A.T.clone().T
+    else:
+        C = np.array(A, order="F", copy=True)
+    return lu_complex_(C, None, pivot, thread, **kwargs)
+
+
+def ldiv_complex_(F: LU, B, *, handle=None):
+    """``ldiv!(F, B)`` with the factors ``lu_complex_`` returned: overwrite ``B`` (a vector or a column-major n x k matrix of the factors'
+    dtype, on the factors' side of the bus) with ``A \\ B`` (``rflu_getrs_cf64`` / ``rflu_getrs_cf32`` and their ``_dev`` forms).  Raises
+    ``SingularException`` when ``F.info != 0``.  There is no complex ``ldiv!(F', B)``: an ``Adjoint`` factorization raises ``TypeError``."""
+    if isinstance(F, Adjoint):
+        raise TypeError("ldiv_complex_: the adjoint solve of a complex factorization is not served (adjoint and transpose differ)")
+    if F.info != 0:
+        raise SingularException(abs(F.info))
+    A = F.factors
+    sfx = _csfx(A.dtype)
+    n = int(A.shape[0])
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("ldiv! needs a square factorization")
+    if B.shape[0] != n:
+        raise ValueError("right-hand side has the wrong number of rows")
+    nrhs = 1 if B.ndim == 1 else int(B.shape[1])
+    nopiv = isinstance(F.ipiv, NotIPIV)
+    if _is_torch(A):
+        import torch
+
+        if not (_is_torch(B) and B.is_cuda and B.dtype == A.dtype):
+            raise TypeError("B must be a CUDA tensor of the factorization's dtype")
+        if n > 1 and A.stride(0) != 1:
+            raise ValueError("the factors must be column-major, as lu_complex_ leaves them")
+        if B.ndim == 1 and n > 1 and B.stride(0) != 1:
+            raise ValueError("a vector right-hand side must be contiguous (stride 1); copy the view first")
+        if B.ndim == 2 and n > 1 and not (B.stride(0) == 1 and (nrhs <= 1 or B.stride(1) >= n)):
+            raise ValueError("B must be column-major like the factors")
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        ldb = B.stride(1) if (B.ndim == 2 and nrhs > 1 and n > 1) else max(n, 1)
+        if n > 0 and nrhs > 0:
+            h.call(f"rflu_getrs_{sfx}_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), A.stride(1) if n > 1 else 1,
+                   ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), ctypes.c_void_p(B.data_ptr()), ldb)
+        return B
+    if not (isinstance(B, np.ndarray) and B.dtype == A.dtype and (B.ndim == 1 and B.flags.c_contiguous or B.flags.f_contiguous)):
+        raise TypeError("B must be a column-major numpy array of the factorization's dtype")
+    h = handle or _ffi.default_handle(0)
+    h.set_stream(None)
+    ipiv = None if nopiv else np.ascontiguousarray(F.ipiv, dtype=np.int64)
+    if n > 0 and nrhs > 0:
+        h.call(f"rflu_getrs_{sfx}", n, nrhs, ctypes.c_void_p(A.ctypes.data), max(n, 1),
+               ctypes.c_void_p(0 if ipiv is None else ipiv.ctypes.data), ctypes.c_void_p(B.ctypes.data), max(n, 1))
     return B
 
 
