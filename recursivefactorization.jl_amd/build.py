@@ -12,13 +12,14 @@ LIB = os.path.join(HERE, "librflu_exp.so" if os.environ.get("RFLU_EXPERIMENTS", 
 # RFLU_EXPERIMENTS=1 in the environment of the BUILD adds the kernels that were measured and lost (the sub-panel
 # leaf of round 4) -- objects and library of their own (build_exp/, librflu_exp.so) so that the default build never contains them
 EXPERIMENTS = os.environ.get("RFLU_EXPERIMENTS", "0") not in ("", "0")
-SOURCES = ["gemm.hip", "engine.hip", "panel.hip", "panel_f32.hip", "panel_local.hip", "panel_local_f32.hip", "panel_local_xcd.hip", "panel_local_xcd_f32.hip", "panel_single.hip", "panel_single_f32.hip", "trsm.hip", "trsv.hip", "laswp.hip", "butterfly.hip", "batched.hip", "mixed.hip", "inverse.hip", "complex_gemm.hip", "complex.hip", "driver.cpp", "host_entry.cpp"]
+SOURCES = ["gemm.hip", "engine.hip", "panel.hip", "panel_f32.hip", "panel_local.hip", "panel_local_f32.hip", "panel_local_xcd.hip", "panel_local_xcd_f32.hip", "panel_single.hip", "panel_single_f32.hip", "trsm.hip", "trsv.hip", "laswp.hip", "butterfly.hip", "batched.hip", "mixed.hip", "inverse.hip", "complex_gemm.hip", "complex.hip", "driver.cpp", "streams.cpp", "schedule.cpp", "mgpu.cpp", "host_entry.cpp"]
 if EXPERIMENTS:
     SOURCES += ["panel_blocked.hip", "panel_blocked_f32.hip"]
 HEADERS = ["rflu_internal.hpp", os.path.join("..", "..", "include", "rflu.h")]   # included by every source
 ALL_HEADERS = HEADERS + ["panel_common.hpp", "panel_xchg.hpp", "trsm_row.hpp", "gemm_tile.hpp", "laswp_strip.hpp", "engine.hpp", "schedule_plan.hpp", "driver.hpp", "host_wayback.hpp", "complex.hpp"]
 _PANEL_H = ["panel_common.hpp", "panel_xchg.hpp", "trsm_row.hpp"]
-EXTRA_DEPS = {"gemm.hip": ["gemm_tile.hpp"], "engine.hip": ["gemm_tile.hpp", "laswp_strip.hpp", "engine.hpp"], "driver.cpp": ["engine.hpp", "schedule_plan.hpp", "driver.hpp", "complex.hpp"],
+EXTRA_DEPS = {"gemm.hip": ["gemm_tile.hpp"], "engine.hip": ["gemm_tile.hpp", "laswp_strip.hpp", "engine.hpp"], "driver.cpp": ["schedule_plan.hpp", "driver.hpp", "complex.hpp"],
+              "streams.cpp": ["schedule_plan.hpp", "driver.hpp"], "schedule.cpp": ["engine.hpp", "schedule_plan.hpp", "driver.hpp"], "mgpu.cpp": ["schedule_plan.hpp", "driver.hpp"],
               "host_entry.cpp": ["engine.hpp", "schedule_plan.hpp", "driver.hpp", "host_wayback.hpp", "complex.hpp"],
               "complex_gemm.hip": ["gemm_tile.hpp", "complex.hpp"], "complex.hip": ["complex.hpp"],
               "laswp.hip": ["laswp_strip.hpp", "trsm_row.hpp"], "trsm.hip": ["trsm_row.hpp"], "trsv.hip": ["trsm_row.hpp"],
@@ -86,7 +87,9 @@ def build_librflu(force: bool = False, verbose: bool = False) -> str:
         return op
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        # MAX_JOBS if set, else at most 16 compilers at once: a machine may report many more CPUs than it grants a build
+        workers = int(os.environ.get("MAX_JOBS") or 0) or min(os.cpu_count() or 4, 16)
+        with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), workers))) as ex:
             list(ex.map(compile_one, jobs))
     objs = [os.path.join(OBJ, os.path.splitext(s)[0] + ".o") for s in SOURCES]
     if force or jobs or not os.path.exists(LIB):

@@ -280,7 +280,7 @@ static int launch_ctranspose(Handle* h, int64_t rows_out, int64_t cols_out, cons
     return RFLU_OK;
 }
 
-// ---- the recursion (Fact<T>::rec of driver.cpp, src/lu.jl:189-263): columns [j0, j1), rows [j0, m), the diagonal at (j0, j0) ------------
+// ---- the recursion (Fact<T>::rec of schedule.cpp, src/lu.jl:189-263): columns [j0, j1), rows [j0, m), the diagonal at (j0, j0) ------------
 // On return the interchanges ipiv[j0 .. j1) have been applied to columns [j0, j1); the caller applies them to the others.
 template <typename R>
 struct CFact {

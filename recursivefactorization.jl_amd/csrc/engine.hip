@@ -2,7 +2,7 @@
 // pulls its work from device-side counters.
 //
 // What it replaces.  schur_complement! (/root/reference/src/lu.jl:265-284), the block-row ldiv! (:235) and apply_permutation!
-// (:164-188) of the trailing matrix were three launch sequences per block column on a CU-masked "update stream" (driver.cpp:
+// (:164-188) of the trailing matrix were three launch sequences per block column on a CU-masked "update stream" (schedule.cpp:
 // factor_lookahead): interchanges -> block-row solve -> one bulk GEMM whose workgroups take their tiles in a fixed order.  The
 // bulk GEMM reached 46-50 TFLOP/s there against 57.7 alone on the same CUs: every launch ramps up and tails off, the stream's
 // own interchanges / solves run with the matrix cores idle (7 % of its time), and a block column's update cannot start before the
@@ -11,7 +11,7 @@
 // Design.  The trailing matrix is a set of COLUMN BLOCKS (W columns).  Column block cb has to receive a fixed list of operations
 // in a fixed order (engine.hpp: eng_op) -- BIG(b): block column b as a whole (K = W) for every block column at least two to its
 // left, then LEAF(g): the eight leaves of the block column right in front of it and the leaves of its own block column, one at a
-// time (K = 64: the leaf-wise schedule's window, driver.cpp: factor_leafwise) -- each in two stages ("sequences", seq = 2 op + stage):
+// time (K = 64: the leaf-wise schedule's window, schedule.cpp: factor_leafwise) -- each in two stages ("sequences", seq = 2 op + stage):
 //     stage 0: the operation's interchanges on its columns + X = inv(L11) * A12      (units of 32 columns, one workgroup each)
 //     stage 1: A22 -= A21 * X                                                        (units of one 128 x 128 tile)
 // and different column blocks are independent of each other.  Per column block a 64-bit claim word (seq << 32 | next unit) and a

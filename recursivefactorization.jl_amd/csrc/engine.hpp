@@ -1,8 +1,10 @@
 // engine.hpp -- the persistent update engine (engine.hip): state and work description shared between the host schedule
-// (driver.cpp: factor_leafwise in engine mode) and the device.  See engine.hip for the design.
+// (schedule.cpp: factor_leafwise in engine mode) and the device.  See engine.hip for the design.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "rflu_internal.hpp"
 
@@ -206,6 +208,31 @@ RFLU_HD int eng_units_of(const EngOp& o, int stage, int m)
     return ((rows + 127) / 128) * ((o.nc + 127) / 128);
 }
 
+// The state the engine starts from (host; `img` is the image that is then copied to the device): every column block claims the first
+// sequence of its list that has units -- operations without units complete by themselves -- or ENG_SEQ_DONE, the same for its deferred
+// interchanges, and `remaining` counts the claim words that are not done.
+template <typename T>
+inline void eng_initial_state(const EngGeo& geo, EngState* img)
+{
+    memset(img, 0, offsetof(EngState, cb) + (size_t)geo.ncb * sizeof(EngCB));
+    for (int cb = 0; cb < geo.ncb; ++cb) {
+        EngCB& c = img->cb[cb];
+        const int end = 2 * eng_nops(geo, cb);
+        int sq = 0;
+        while (sq < end && eng_units_of(eng_op(geo, cb, sq >> 1), sq & 1, geo.m) == 0) ++sq;
+        c.prog = 2ull * (unsigned long long)(sq >> 1);
+        c.claim = sq < end ? (unsigned long long)sq << 32 : (unsigned long long)ENG_SEQ_DONE << 32;
+        img->remaining += sq < end;
+        const int nleft = eng_nleft(geo, cb);
+        int lk = 0;
+        while (lk < nleft && eng_left_units<T>(geo, cb, lk) == 0) ++lk;
+        c.lclaim = lk < nleft ? (unsigned long long)lk << 32 : (unsigned long long)ENG_SEQ_DONE << 32;
+        c.lprog = (unsigned long long)lk;   // (left ops without units count as done)
+        if (nleft > 0 && lk > 0) img->cb[eng_first_cb(geo, eng_pb(geo, cb))].leftdone += 1ull << 32;   // ... towards the block column's own count too
+        img->remaining += lk < nleft;
+    }
+}
+
 // ---- order between the interchanges and the readers of a panel ------------------------------------------------------------------
 // The leaves of block column b are applied one by one (LEAF ops on the column blocks of block columns b and b + 1) with the rows of L
 // in the order of THAT leaf; the block column as a whole (BIG(b), block columns b + 2 ...) needs L with all of the block column's
@@ -253,7 +280,7 @@ struct EngArgs {
     int solve_rl;        // block-row solves of up to 512 rows right-looking with the block row in registers (engine.hip: eng_prep_unit)
     int host_lag;        // host entry: whole-block-column operations that lag the chain by this many block columns go first (0: never)
     int retire_xcc; // the workgroups on this XCC leave once retire_leaf leaves are done (-1: nobody retires): the short panels at the end, which
-    int retire_leaf; // the engine has little to do for, get the XCD their XCD-local exchange needs (driver.cpp: factor_leafwise)
+    int retire_leaf; // the engine has little to do for, get the XCD their XCD-local exchange needs (schedule.cpp: factor_leafwise)
 };
 
 template <typename T>

@@ -81,7 +81,7 @@ struct GemmArgs {
     int flags;   // bit1: non-temporal C accesses (bit0, "operand slab before the C tile", is always on since round 4)
     // "first columns first": the tiles of the first na_tiles_n tile columns take the lowest block indices (they are dispatched,
     // hence finished, first) and the last of them to finish publishes sig_val in *sig_flag -- the lookahead schedule's
-    // critical path needs only those columns of a bulk update (driver.cpp: factor_lookahead, GemmSignal)
+    // critical path needs only those columns of a bulk update (schedule.cpp: factor_lookahead, GemmSignal)
     int na_tiles_n;
     unsigned long long* sig_flag;
     unsigned long long sig_val;

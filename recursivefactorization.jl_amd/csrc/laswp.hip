@@ -468,7 +468,7 @@ int launch_iota_ipiv(Handle* h, int64_t* ipiv, int64_t k0, int64_t n)
 
 
 // ---- device-side stream gates ------------------------------------------------------------------------------------------
-// The leaf-wise schedule (driver.cpp: factor_leafwise) hands work between streams once per 64-column leaf.  A hipEvent record
+// The leaf-wise schedule (schedule.cpp: factor_leafwise) hands work between streams once per 64-column leaf.  A hipEvent record
 // + hipStreamWaitEvent pair costs the waiting AND the recording stream 40-50 us of pipeline bubble each (measured with
 // scripts/trace_timeline.sh) -- more than the launches the schedule removes -- so the per-leaf edges are ordinary one-wave
 // kernels on monotonically increasing 64-bit counters: gate_signal publishes `value` when the stream reaches it (everything

@@ -272,6 +272,9 @@ inline int64_t local_leaf_rows(const Tune& t, size_t esize, int64_t cap = -1)
     return cap >= 0 && cap < rows ? cap : rows;
 }
 
+// run the launchers on `s` until the end of the scope; the handle's stream is put back on every way out
+struct OnStream { Handle* h; hipStream_t saved; OnStream(Handle* h_, hipStream_t s) : h(h_), saved(h_->stream) { h->stream = s; } ~OnStream() { h->stream = saved; } OnStream(const OnStream&) = delete; OnStream& operator=(const OnStream&) = delete; };
+
 struct ProfScope {
     Handle* h;
     int k;

@@ -2,15 +2,66 @@
 // the device walks): over a grid of geometries, every column receives every earlier leaf exactly once and in order (the Schur updates of
 // /root/reference/src/lu.jl:233-240, :265-284 in the engine's decomposition; the leaf right in front of a column reaches it on the critical-path
 // stream), the leaf counts an operation waits for are sufficient and monotone, an operation's columns lie inside its column block, a leaf's
-// operation index is where eng_leaf_op_index says, and a stage with columns has units.  Compiled and run by tests/test_engine_geometry.py (no GPU).
+// operation index is where eng_leaf_op_index says, and a stage with columns has units.  The state the engine starts from (eng_initial_state,
+// Float64 and Float32) claims, per column block, the first sequence that has units -- found here by a scan from the END of the list over
+// unit counts taken from the operation's shape -- or ENG_SEQ_DONE, the same for the deferred interchanges, and counts the open claim
+// words in `remaining`.  Compiled and run by tests/test_engine_geometry.py (no GPU).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include "engine.hpp"
 using namespace rflu;
+
+// units of sequence sq (2 * op + stage) of column block cb, from the operation's shape: 32-column strips, then 128 x 128 tiles of the rows below
+static int units_by_shape(const EngGeo& g, int cb, int sq)
+{
+    const EngOp o = eng_op(g, cb, sq >> 1);
+    if (o.nc <= 0) return 0;
+    if ((sq & 1) == 0) return (o.nc + 31) / 32;
+    const int rows = g.m - (o.j0 + o.jb);
+    return rows <= 0 ? 0 : ((rows + 127) / 128) * ((o.nc + 127) / 128);
+}
+
+// violations of the initial state for element type T
+template <typename T>
+static int check_initial_state(const EngGeo& g, EngState* img, const char* tname)
+{
+    int bad = 0;
+    const unsigned long long DONE = (unsigned long long)ENG_SEQ_DONE << 32;
+    eng_initial_state<T>(g, img);
+    unsigned long long open = 0;
+    for (int cb = 0; cb < g.ncb; ++cb) {
+        const EngCB& c = img->cb[cb];
+        const int end = 2 * eng_nops(g, cb);
+        int first = end;   // first sequence with units, found from the back
+        for (int sq = end - 1; sq >= 0; --sq)
+            if (units_by_shape(g, cb, sq) > 0) first = sq;
+        const unsigned long long want_claim = first < end ? (unsigned long long)first << 32 : DONE;
+        if (c.claim != want_claim || c.prog != 2ull * (unsigned long long)(first >> 1)) {
+            if (bad++ < 10) printf("initial claim %s W=%d Wc=%d m=%d n=%d nbp=%d ahead=%d cb=%d: claim %llx prog %llu, first sequence with units %d of %d\n", tname, g.W, g.Wc, g.m, g.n,
+                                   g.nbp, g.ahead, cb, c.claim, c.prog, first, end);
+        }
+        const int nleft = eng_nleft(g, cb);
+        int lfirst = nleft;
+        for (int lk = nleft - 1; lk >= 0; --lk)
+            if (eng_left_units<T>(g, cb, lk) > 0) lfirst = lk;
+        const unsigned long long want_lclaim = lfirst < nleft ? (unsigned long long)lfirst << 32 : DONE;
+        if (c.lclaim != want_lclaim || c.lprog != (unsigned long long)lfirst) {
+            if (bad++ < 10) printf("initial left claim %s W=%d Wc=%d m=%d n=%d nbp=%d ahead=%d cb=%d: lclaim %llx lprog %llu, first left op with units %d of %d\n", tname, g.W, g.Wc, g.m,
+                                   g.n, g.nbp, g.ahead, cb, c.lclaim, c.lprog, lfirst, nleft);
+        }
+        open += (c.claim != DONE) + (c.lclaim != DONE);
+    }
+    if (img->remaining != open) {
+        if (bad++ < 10) printf("initial remaining %s W=%d Wc=%d m=%d n=%d nbp=%d ahead=%d: %llu vs %llu open claim words\n", tname, g.W, g.Wc, g.m, g.n, g.nbp, g.ahead, img->remaining, open);
+    }
+    return bad;
+}
+
 int main(int argc, char** argv)
 {
     int bad = 0, cases = 0;
+    std::vector<EngState> image(1);
     const int Ws[] = {128, 256, 512};
     for (int W : Ws)
         for (int Wc : {128, 256, 512}) {
@@ -27,6 +78,8 @@ int main(int argc, char** argv)
                     g.nbp = nbp;
                     g.ahead = ahead;   // leaf windows over the own block column and `ahead` block columns right of it (engine.hpp)
                     ++cases;
+                    bad += check_initial_state<double>(g, image.data(), "f64");
+                    bad += check_initial_state<float>(g, image.data(), "f32");
                     const int served_leaves = (std::min(nbp * W, g.mn) + NB - 1) / NB;
                     // the per-block-column counts the interchange ordering rests on (engine.hpp: "order between the interchanges ..."): who has
                     // BIG(b), and where the LEAF ops of block column b end in the lists of the column blocks in front of which it lies
