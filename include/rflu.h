@@ -244,8 +244,8 @@ int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, c
                                int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* Ainv_dev, int64_t ldi,
                                int64_t strideI, int64_t* info_dev);
 
-/* ---- COMPLEX: lu! / ldiv! for ComplexF64 / ComplexF32 (suffixes _cf64 / _cf32; csrc/complex.hip, csrc/complex_gemm.hip, DESIGN.md
- * section 4.5).  The reference's lu! with a complex element type (src/lu.jl:97-130, :189-263, :290-338; test/runtests.jl:33-84).
+/* ---- COMPLEX: lu! / ldiv! for ComplexF64 / ComplexF32 (suffixes _cf64 / _cf32; csrc/complex.hip, csrc/complex_gemm.hip,
+ * csrc/complex_solve.hip, DESIGN.md sections 4.5 and 4.6).  The reference's lu! with a complex element type (src/lu.jl:97-130, :189-263, :290-338; test/runtests.jl:33-84).
  * A complex array crosses the boundary as double* / float* pointing at INTERLEAVED (re, im) pairs, the storage of Julia's Complex{T}
  * and numpy's complex128 / complex64; every lda / ldb / ldc counts COMPLEX elements.  A pointer aligned to the real type is enough.
  *   - pivot of column k: the row with the largest MODULUS abs(z) = hypot(re, im) in the element's real precision, strict '>' from 0, so
@@ -260,7 +260,14 @@ int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, c
  *   - every kernel is an in-order launch on the handle's stream and NONE waits for another workgroup: no cooperative launch, no flag,
  *     no RFLU_ERR_TIMEOUT from these entries.  Work is complete on return;
  *   - rflu_getrs_*: ldiv!(F, B) for any nrhs, F / ipiv as the factorization left them; a singular U yields Inf/NaN, no error status.
- *     There is no complex ldiv!(F', B) (adjoint and transpose differ here), no batched / mixed / inverse form;
+ *     There is no batched / mixed / inverse form;
+ *   - rflu_getrs_trans_*: ldiv!(transpose(F), B) and ldiv!(F', B), which differ for these element types, so the entries take `conj`:
+ *     conj = 0 solves transpose(A) x = b (LAPACK 'T', B <- P^T L^-T U^-T B), conj = 1 solves A' x = b (LAPACK 'C', B <- P^T L^-H U^-H B),
+ *     any other value is RFLU_ERR_ARG.  Everything else is as rflu_getrs_*: storage, lda / ldb, NULL ipiv = NotIPIV, alignment, any
+ *     lda >= n, Inf/NaN and RFLU_OK for a singular U, n == 0 or nrhs == 0 succeed with nothing launched, the same argument checks.
+ *     F is ONLY READ, IN PLACE (a column-major F read row-major is its transpose): no n x n copy, no workspace that grows as n^2.
+ *     Up to 8 right-hand sides are solved in B's own columns (csrc/complex_solve.hip), more go through a
+ *     row-major image of B and the complex GEMM.  Results are bit-identical from run to run and whatever the alignment of F and lda;
  *   - the host entries: H2D, the device entry, D2H -- only on success, so a failed call leaves the caller's arrays as they were. */
 int rflu_getrf_cf64(rflu_handle_t handle, int64_t m, int64_t n, double* A_host, int64_t lda, int64_t* ipiv_host, int pivot,
                     int64_t* info);
@@ -278,6 +285,14 @@ int rflu_getrs_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const dou
                         double* B_dev, int64_t ldb);
 int rflu_getrs_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda, const int64_t* ipiv_dev,
                         float* B_dev, int64_t ldb);
+int rflu_getrs_trans_cf64(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* F_host, int64_t lda, const int64_t* ipiv_host,
+                          double* B_host, int64_t ldb, int conj);
+int rflu_getrs_trans_cf32(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_host, int64_t lda, const int64_t* ipiv_host,
+                          float* B_host, int64_t ldb, int conj);
+int rflu_getrs_trans_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* F_dev, int64_t lda, const int64_t* ipiv_dev,
+                              double* B_dev, int64_t ldb, int conj);
+int rflu_getrs_trans_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda, const int64_t* ipiv_dev,
+                              float* B_dev, int64_t ldb, int conj);
 /* building block: C <- C - A*B, all row-major complex: A is M x K (lda), B is K x N (ldb), C is M x N (ldc).  Four real MFMA products
  * per K step; 16-byte loads where the pointers (and, for _cf32, even lda / ldb) allow, element by element otherwise -- same arithmetic. */
 int rflu_gemm_rm_cf64_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K, const double* A_dev, int64_t lda,

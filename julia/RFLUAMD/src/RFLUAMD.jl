@@ -13,7 +13,7 @@ Surface (the reference's own, `src/lu.jl:19-21, 67-83, 97-130`):
     RFLUAMD.lu!(A, ipiv, pivot = Val(true), thread = Val(false); check, blocksize, threshold)   # what RFLUFactorization calls
 
 returning a genuine `LinearAlgebra.LU(A, ipiv, info)` that aliases the caller's arrays.  `Float64` / `Float32` strided
-column-major matrices with at least `GPU_MIN_N[]` columns go to the GPU (so do `ComplexF64` / `ComplexF32` ones, for `lu!` and `ldiv!(F, B)`); everything else (other element types, non-strided
+column-major matrices with at least `GPU_MIN_N[]` columns go to the GPU (so do `ComplexF64` / `ComplexF32` ones, for `lu!`, `ldiv!(F, B)`, `ldiv!(F', B)` and `ldiv!(transpose(F), B)`); everything else (other element types, non-strided
 storage, small sizes, no device) goes to `RecursiveFactorization.lu!` when that package is loaded, else to
 `LinearAlgebra.lu!`/`generic_lufact!` -- the same fall-back rules the reference applies (`src/lu.jl:74-77, 92-93, 114-126`).
 """
@@ -229,7 +229,7 @@ function getrf_complex_dev!(A::Ptr{Float32}, m::Integer, n::Integer, lda::Intege
     return BlasInt(info[])
 end
 
-"`ldiv!(F, B)` for complex factors on the GPU (there is no complex `ldiv!(F', B)`: that one stays with the stdlib)"
+"`ldiv!(F, B)` for complex factors on the GPU (`ldiv!(F', B)` and `ldiv!(transpose(F), B)` are served by `getrs_ctrans!` below)"
 function getrs!(F::StridedMatrix{ComplexF64}, ipiv::Ptr{Int64}, B::StridedVecOrMat{ComplexF64})
     n = size(F, 1)
     st = ccall((:rflu_getrs_cf64, librflu), Cint,
@@ -279,6 +279,31 @@ function getrs_trans!(F::StridedMatrix{Float32}, ipiv::Ptr{Int64}, B::StridedVec
     st = ccall((:rflu_getrs_trans_f32, librflu), Cint,
                (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float32}, Int64),
                handle(), n, size(B, 2), F, stride(F, 2), ipiv, B, B isa AbstractVector ? n : stride(B, 2))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+"""
+    getrs_ctrans!(F, ipiv, B, conj)
+
+The transposed solves for complex factors on the GPU (`rflu_getrs_trans_cf64` / `_cf32`), which differ for these element types:
+`conj = false` is `ldiv!(transpose(F), B)` (B <- P^T L^-T U^-T B, LAPACK 'T'), `conj = true` is `ldiv!(F', B)` (B <- P^T L^-H U^-H B,
+LAPACK 'C').  The factors are only read, in place.
+"""
+function getrs_ctrans!(F::StridedMatrix{ComplexF64}, ipiv::Ptr{Int64}, B::StridedVecOrMat{ComplexF64}, conj::Bool)
+    n = size(F, 1)
+    st = ccall((:rflu_getrs_trans_cf64, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Int64, Cint),
+               handle(), n, size(B, 2), reinterpret(Ptr{Float64}, pointer(F)), stride(F, 2), ipiv, reinterpret(Ptr{Float64}, pointer(B)), B isa AbstractVector ? n : stride(B, 2), Cint(conj))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+function getrs_ctrans!(F::StridedMatrix{ComplexF32}, ipiv::Ptr{Int64}, B::StridedVecOrMat{ComplexF32}, conj::Bool)
+    n = size(F, 1)
+    st = ccall((:rflu_getrs_trans_cf32, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float32}, Int64, Cint),
+               handle(), n, size(B, 2), reinterpret(Ptr{Float32}, pointer(F)), stride(F, 2), ipiv, reinterpret(Ptr{Float32}, pointer(B)), B isa AbstractVector ? n : stride(B, 2), Cint(conj))
     st == RFLU_OK || error("librflu: ", last_error())
     return B
 end
@@ -426,6 +451,7 @@ end
 # ---- dispatch: who serves a call (RecursiveFactorization src/lu.jl:92-93, 114-126) -------------------------------------------
 const GPUEltype = Union{Float32, Float64}                                  # every entry serves these
 const GPUAnyEltype = Union{Float32, Float64, ComplexF32, ComplexF64}       # lu! and ldiv!(F, B) serve the complex types as well
+const GPUComplexEltype = Union{ComplexF32, ComplexF64}                     # ldiv!(F', B) / ldiv!(transpose(F), B): two different solves
 gpu_ok(A::StridedMatrix{<:GPUAnyEltype}, ipiv) =
     stride(A, 1) == 1 && min(size(A)...) >= GPU_MIN_N[] && (ipiv isa Vector{Int64} || ipiv isa NotIPIV) && available()
 gpu_ok(A, ipiv) = false
@@ -534,6 +560,30 @@ function ldiv!(Ft::Union{AdjointLU{T}, TransposeLU{T}}, B::StridedVecOrMat{T}) w
     if lay_ok && size(F.factors, 1) >= GPU_MIN_N[] && available() && (F.ipiv isa Vector{Int64} || F.ipiv isa NotIPIV)
         p = F.ipiv isa NotIPIV ? Ptr{Int64}(C_NULL) : pointer(F.ipiv)
         GC.@preserve F B getrs_trans!(F.factors, p, B)
+        return B
+    end
+    return LinearAlgebra.ldiv!(Ft, B)
+end
+
+"solve A' x = b (the conjugate transpose) with complex factors of A on the GPU (same conditions as `ldiv!(F, B)`), else stdlib `ldiv!`"
+function ldiv!(Ft::AdjointLU{T}, B::StridedVecOrMat{T}) where {T <: GPUComplexEltype}
+    F = parent(Ft)
+    lay_ok = stride(F.factors, 1) == 1 && stride(B, 1) == 1 && size(F.factors, 1) == size(F.factors, 2) == size(B, 1)
+    if lay_ok && size(F.factors, 1) >= GPU_MIN_N[] && available() && (F.ipiv isa Vector{Int64} || F.ipiv isa NotIPIV)
+        p = F.ipiv isa NotIPIV ? Ptr{Int64}(C_NULL) : pointer(F.ipiv)
+        GC.@preserve F B getrs_ctrans!(F.factors, p, B, true)
+        return B
+    end
+    return LinearAlgebra.ldiv!(Ft, B)
+end
+
+"solve transpose(A) x = b (no conjugation) with complex factors of A on the GPU (same conditions as `ldiv!(F, B)`), else stdlib `ldiv!`"
+function ldiv!(Ft::TransposeLU{T}, B::StridedVecOrMat{T}) where {T <: GPUComplexEltype}
+    F = parent(Ft)
+    lay_ok = stride(F.factors, 1) == 1 && stride(B, 1) == 1 && size(F.factors, 1) == size(F.factors, 2) == size(B, 1)
+    if lay_ok && size(F.factors, 1) >= GPU_MIN_N[] && available() && (F.ipiv isa Vector{Int64} || F.ipiv isa NotIPIV)
+        p = F.ipiv isa NotIPIV ? Ptr{Int64}(C_NULL) : pointer(F.ipiv)
+        GC.@preserve F B getrs_ctrans!(F.factors, p, B, false)
         return B
     end
     return LinearAlgebra.ldiv!(Ft, B)

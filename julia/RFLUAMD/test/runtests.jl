@@ -43,6 +43,20 @@ end
         end
     end
 end
+@testset "RFLUAMD ldiv! with the adjoint / transposed COMPLEX factorization (two different solves)" begin
+    RFLUAMD.GPU_MIN_N[] = 64
+    for _p in (true, false), T in (ComplexF64, ComplexF32), n in (64, 65, 300, 1000)
+        A = rand(T, n, n) + T(10) * I
+        F = RFLUAMD.lu(A, Val(_p))
+        b = rand(T, n); B = rand(T, n, 9)                     # a vector (few-right-hand-side path) and 9 columns (GEMM path)
+        for (Ft, opA) in ((F', A'), (transpose(F), transpose(A)))
+            x = RFLUAMD.ldiv!(Ft, copy(b))
+            @test norm(opA * x - b) < 1000n * eps(real(T))
+            X = RFLUAMD.ldiv!(Ft, copy(B))
+            @test norm(opA * X - B) < 1000n * eps(real(T))
+        end
+    end
+end
 @testset "RFLUAMD inv! / det / logabsdet from the factors" begin
     RFLUAMD.GPU_MIN_N[] = 64
     for _p in (true, false), T in (Float64, Float32), n in (64, 65, 300, 1000)

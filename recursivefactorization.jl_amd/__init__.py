@@ -27,6 +27,8 @@ from .lu import (  # noqa: F401
     ldiv_,
     ldiv_batched_,
     ldiv_complex_,
+    ldiv_complex_adjoint_,
+    ldiv_complex_transpose_,
     ldiv_mixed,
     logabsdet,
     logabsdet_batched,
@@ -54,7 +56,7 @@ __all__ = [
     "linsolve",
     "ButterflyWorkspace", "butterfly_workspace", "butterfly_solve_", "butterfly_mul_",
     "lu", "lu_", "ldiv_", "LU", "lu_batched", "lu_batched_", "ldiv_batched_", "BatchedLU", "lu_mixed", "ldiv_mixed", "MixedLU", "NotConvergedError", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
-    "lu_complex", "lu_complex_", "ldiv_complex_",
+    "lu_complex", "lu_complex_", "ldiv_complex_", "ldiv_complex_adjoint_", "ldiv_complex_transpose_",
     "inv", "inv_", "det", "logabsdet", "logdet", "inv_batched", "logabsdet_batched", "det_batched",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

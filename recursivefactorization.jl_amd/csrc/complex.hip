@@ -5,32 +5,9 @@
 // another workgroup, so there is no residency requirement, no flag to spin on and no timeout status on this path.
 #include <algorithm>
 
-#include "complex.hpp"
+#include "complex_dev.hpp"
 
 namespace rflu {
-
-template <typename R>
-struct Cx {   // 2-word POD, the layout of Julia's Complex{R}
-    R re, im;
-};
-template <typename R>
-__device__ __forceinline__ Cx<R> cmul(Cx<R> a, Cx<R> b) { return Cx<R>{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-template <typename R>
-__device__ __forceinline__ Cx<R> csub(Cx<R> a, Cx<R> b) { return Cx<R>{a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ double cmodulus(Cx<double> z) { return hypot(z.re, z.im); }
-__device__ __forceinline__ float cmodulus(Cx<float> z) { return hypotf(z.re, z.im); }
-// a / b by Smith's formula (one reciprocal, no overflow of |b|^2); b == 0 gives Inf / NaN like the real division
-template <typename R>
-__device__ __forceinline__ Cx<R> cdiv(Cx<R> a, Cx<R> b)
-{
-    if (fabs(b.re) >= fabs(b.im)) {
-        if (b.re == R(0) && b.im == R(0)) return Cx<R>{a.re / fabs(b.re), a.im / fabs(b.im)};
-        const R rat = b.im / b.re, scl = R(1) / (b.re + b.im * rat);
-        return Cx<R>{(a.re + a.im * rat) * scl, (a.im - a.re * rat) * scl};
-    }
-    const R rat = b.re / b.im, scl = R(1) / (b.re * rat + b.im);
-    return Cx<R>{(a.re * rat + a.im) * scl, (a.im * rat - a.re) * scl};
-}
 
 // ---- leaf panel: _generic_lufact! on rows [j0, m) x columns [j0, j0 + w), w <= CLEAF, ONE workgroup ------------------------------------
 // Per column k: the modulus argmax over the rows below (strict '>' from 0, the lowest row on ties, a NaN modulus never wins), the
@@ -140,9 +117,10 @@ static int launch_cleaf(Handle* h, R* A, int64_t ld, int64_t m, int64_t j0, int6
 }
 
 // ---- base solves on one leaf-sized triangle (n <= CLEAF), one thread per right-hand side, the solution in registers ---------------------
-// UPPER = false: B <- L^-1 B, L unit lower (ldiv!(UnitLowerTriangular(A11), A12), src/lu.jl:235); UPPER = true: B <- U^-1 B, a zero on
-// U's diagonal gives Inf / NaN.  T is n x n row-major (ldt), B is n x nrhs row-major (ldb).
-template <typename R, bool UPPER>
+// UPPER = false, UNIT = true: B <- L^-1 B, L unit lower (ldiv!(UnitLowerTriangular(A11), A12), src/lu.jl:235); UPPER = true, UNIT = false:
+// B <- U^-1 B, a zero on U's diagonal gives Inf / NaN.  The other two kinds serve the transposed solves (complex_solve.hip): lower with
+// the stored diagonal is U^T, upper with a unit diagonal is L^T.  T is n x n row-major (ldt), B is n x nrhs row-major (ldb).
+template <typename R, bool UPPER, bool UNIT>
 __global__ void __launch_bounds__(128) ctri_base_kernel(int n, int64_t nrhs, const R* __restrict__ T, int64_t ldt, R* __restrict__ B, int64_t ldb)
 {
     __shared__ R Ts[2 * CLEAF * CLEAF];
@@ -165,7 +143,7 @@ __global__ void __launch_bounds__(128) ctri_base_kernel(int n, int64_t nrhs, con
                 const bool use = UPPER ? (t > i && t < n) : (t < i);
                 if (use) acc = csub(acc, cmul(Cx<R>{Ts[2 * (i * CLEAF + t)], Ts[2 * (i * CLEAF + t) + 1]}, x[t]));
             }
-            if (UPPER) acc = cdiv(acc, Cx<R>{Ts[2 * (i * CLEAF + i)], Ts[2 * (i * CLEAF + i) + 1]});
+            if (!UNIT) acc = cdiv(acc, Cx<R>{Ts[2 * (i * CLEAF + i)], Ts[2 * (i * CLEAF + i) + 1]});
             x[i] = acc;
             B[2 * (i * ldb + c)] = acc.re;
             B[2 * (i * ldb + c) + 1] = acc.im;
@@ -173,37 +151,49 @@ __global__ void __launch_bounds__(128) ctri_base_kernel(int n, int64_t nrhs, con
     }
 }
 
-template <typename R, bool UPPER>
+template <typename R, bool UPPER, bool UNIT>
 static int launch_ctri_base(Handle* h, int64_t n, int64_t nrhs, const R* T, int64_t ldt, R* B, int64_t ldb)
 {
     if (n <= 0 || nrhs <= 0) return RFLU_OK;
     ProfScope ps(h, RFLU_K_TRSM, 4.0 * (double)n * n * nrhs);
-    hipLaunchKernelGGL((ctri_base_kernel<R, UPPER>), dim3((unsigned)((nrhs + 127) / 128)), dim3(128), 0, h->stream, (int)n, nrhs, T, ldt, B, ldb);
+    hipLaunchKernelGGL((ctri_base_kernel<R, UPPER, UNIT>), dim3((unsigned)((nrhs + 127) / 128)), dim3(128), 0, h->stream, (int)n, nrhs, T, ldt, B, ldb);
     RFLU_HIP(hipGetLastError());
     return RFLU_OK;
 }
 
 // above the base size: the recursive splitting of trsm_rec / triu_solve_rec (driver.cpp) on CLEAF boundaries, the complex GEMM in between
-template <typename R>
+template <typename R, bool UNIT = true>
 static int ctrsm_rec(Handle* h, int64_t n, int64_t nrhs, const R* L, int64_t ldl, R* B, int64_t ldb)
 {
     if (n <= 0 || nrhs <= 0) return RFLU_OK;
-    if (n <= CLEAF) return launch_ctri_base<R, false>(h, n, nrhs, L, ldl, B, ldb);
+    if (n <= CLEAF) return launch_ctri_base<R, false, UNIT>(h, n, nrhs, L, ldl, B, ldb);
     const int64_t n1 = ((n + CLEAF - 1) / CLEAF + 1) / 2 * CLEAF;
-    RFLU_TRY(ctrsm_rec<R>(h, n1, nrhs, L, ldl, B, ldb));
+    RFLU_TRY((ctrsm_rec<R, UNIT>(h, n1, nrhs, L, ldl, B, ldb)));
     RFLU_TRY(launch_cgemm<R>(h, n - n1, nrhs, n1, L + 2 * (n1 * ldl), ldl, B, ldb, B + 2 * (n1 * ldb), ldb));
-    return ctrsm_rec<R>(h, n - n1, nrhs, L + 2 * (n1 * ldl + n1), ldl, B + 2 * (n1 * ldb), ldb);
+    return ctrsm_rec<R, UNIT>(h, n - n1, nrhs, L + 2 * (n1 * ldl + n1), ldl, B + 2 * (n1 * ldb), ldb);
 }
 
-template <typename R>
+template <typename R, bool UNIT = false>
 static int ctriu_rec(Handle* h, int64_t n, int64_t nrhs, const R* U, int64_t ldu, R* B, int64_t ldb)
 {
     if (n <= 0 || nrhs <= 0) return RFLU_OK;
-    if (n <= CLEAF) return launch_ctri_base<R, true>(h, n, nrhs, U, ldu, B, ldb);
+    if (n <= CLEAF) return launch_ctri_base<R, true, UNIT>(h, n, nrhs, U, ldu, B, ldb);
     const int64_t n1 = ((n + CLEAF - 1) / CLEAF + 1) / 2 * CLEAF;   // rows of the top block
-    RFLU_TRY(ctriu_rec<R>(h, n - n1, nrhs, U + 2 * (n1 * ldu + n1), ldu, B + 2 * (n1 * ldb), ldb));
+    RFLU_TRY((ctriu_rec<R, UNIT>(h, n - n1, nrhs, U + 2 * (n1 * ldu + n1), ldu, B + 2 * (n1 * ldb), ldb)));
     RFLU_TRY(launch_cgemm<R>(h, n1, nrhs, n - n1, U + 2 * n1, ldu, B + 2 * (n1 * ldb), ldb, B, ldb));
-    return ctriu_rec<R>(h, n1, nrhs, U, ldu, B, ldb);
+    return ctriu_rec<R, UNIT>(h, n1, nrhs, U, ldu, B, ldb);
+}
+
+// the two recursions with the diagonal kind chosen at run time, for complex_solve.hip
+template <typename R>
+int ctri_lower_rec(Handle* h, int64_t n, int64_t nrhs, const R* T, int64_t ldt, R* B, int64_t ldb, bool unit)
+{
+    return unit ? ctrsm_rec<R, true>(h, n, nrhs, T, ldt, B, ldb) : ctrsm_rec<R, false>(h, n, nrhs, T, ldt, B, ldb);
+}
+template <typename R>
+int ctri_upper_rec(Handle* h, int64_t n, int64_t nrhs, const R* T, int64_t ldt, R* B, int64_t ldb, bool unit)
+{
+    return unit ? ctriu_rec<R, true>(h, n, nrhs, T, ldt, B, ldb) : ctriu_rec<R, false>(h, n, nrhs, T, ldt, B, ldb);
 }
 
 // ---- interchanges: rows k <-> ipiv[k] - 1 for k in [k0, k1), in order, on columns [c0, c0 + ncols); one thread per column -------------
@@ -240,8 +230,8 @@ static int launch_claswp(Handle* h, R* A, int64_t ld, int64_t rows, int64_t c0, 
 // ---- layout change: out[r][c] = in[c][r], `out` is rows_out x cols_out row-major (a column-major m x n matrix with lda IS a row-major
 // n x m matrix with ld = lda).  transpose_kernel of laswp.hip holds a 64 x 65 tile: 66560 B of a 16-byte element, more than a
 // workgroup's static LDS, so this is a 32 x 33 one.  The tiles are numbered along blockIdx.x alone (2^31 tiles of 1024 elements are
-// beyond any memory), so neither dimension meets a grid limit.
-template <typename R>
+// beyond any memory), so neither dimension meets a grid limit.  CONJ conjugates on the way (the adjoint solve of complex_solve.hip).
+template <typename R, bool CONJ>
 __global__ void __launch_bounds__(256) ctranspose_kernel(int64_t rows_out, int64_t cols_out, const R* __restrict__ in, int64_t ld_in,
                                                           R* __restrict__ out, int64_t ld_out, unsigned tiles_x)
 {
@@ -252,7 +242,7 @@ __global__ void __launch_bounds__(256) ctranspose_kernel(int64_t rows_out, int64
         const int64_t ir = c0 + i, ic = r0 + tx;
         const bool ok = ir < cols_out && ic < rows_out;
         tile[i][tx][0] = ok ? in[2 * (ir * ld_in + ic)] : R(0);
-        tile[i][tx][1] = ok ? in[2 * (ir * ld_in + ic) + 1] : R(0);
+        tile[i][tx][1] = ok ? (CONJ ? -in[2 * (ir * ld_in + ic) + 1] : in[2 * (ir * ld_in + ic) + 1]) : R(0);
     }
     __syncthreads();
     for (int i = ty; i < 32; i += 8) {
@@ -265,7 +255,7 @@ __global__ void __launch_bounds__(256) ctranspose_kernel(int64_t rows_out, int64
 }
 
 template <typename R>
-static int launch_ctranspose(Handle* h, int64_t rows_out, int64_t cols_out, const R* in, int64_t ld_in, R* out, int64_t ld_out)
+int launch_ctranspose(Handle* h, int64_t rows_out, int64_t cols_out, const R* in, int64_t ld_in, R* out, int64_t ld_out, bool conj)
 {
     if (rows_out <= 0 || cols_out <= 0) return RFLU_OK;
     const int64_t gx = (cols_out + 31) / 32, gy = (rows_out + 31) / 32;
@@ -274,8 +264,10 @@ static int launch_ctranspose(Handle* h, int64_t rows_out, int64_t cols_out, cons
         return RFLU_ERR_ARG;
     }
     ProfScope ps(h, RFLU_K_TRANSPOSE, 4.0 * sizeof(R) * (double)rows_out * (double)cols_out);
-    hipLaunchKernelGGL(ctranspose_kernel<R>, dim3((unsigned)(gx * gy)), dim3(256), 0, h->stream, rows_out, cols_out, in, ld_in, out, ld_out,
-                       (unsigned)gx);
+    if (conj) hipLaunchKernelGGL((ctranspose_kernel<R, true>), dim3((unsigned)(gx * gy)), dim3(256), 0, h->stream, rows_out, cols_out, in, ld_in, out,
+                                 ld_out, (unsigned)gx);
+    else hipLaunchKernelGGL((ctranspose_kernel<R, false>), dim3((unsigned)(gx * gy)), dim3(256), 0, h->stream, rows_out, cols_out, in, ld_in, out,
+                            ld_out, (unsigned)gx);
     RFLU_HIP(hipGetLastError());
     return RFLU_OK;
 }
@@ -304,8 +296,6 @@ struct CFact {
         return RFLU_OK;
     }
 };
-
-static int64_t cworkspace_ld(int64_t n) { return (n + 7) / 8 * 8; }   // rows start on 64- / 128-byte boundaries
 
 // row-major m x n in place; ipiv / info_dev as the leaves write them (info_dev[0] zeroed by the caller)
 template <typename R>
@@ -380,7 +370,10 @@ int cgemm_public(Handle* h, int64_t M, int64_t N, int64_t K, const R* A, int64_t
 #define RFLU_INSTANTIATE_COMPLEX(R)                                                                                                  \
     template int cgetrf_cm_dev<R>(Handle*, int64_t, int64_t, R*, int64_t, int64_t*, int, int64_t*);                                  \
     template int cgetrs_cm_dev<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t);                        \
-    template int cgemm_public<R>(Handle*, int64_t, int64_t, int64_t, const R*, int64_t, const R*, int64_t, R*, int64_t);
+    template int cgemm_public<R>(Handle*, int64_t, int64_t, int64_t, const R*, int64_t, const R*, int64_t, R*, int64_t);                \
+    template int launch_ctranspose<R>(Handle*, int64_t, int64_t, const R*, int64_t, R*, int64_t, bool);                                 \
+    template int ctri_lower_rec<R>(Handle*, int64_t, int64_t, const R*, int64_t, R*, int64_t, bool);                                    \
+    template int ctri_upper_rec<R>(Handle*, int64_t, int64_t, const R*, int64_t, R*, int64_t, bool);
 RFLU_INSTANTIATE_COMPLEX(double)
 RFLU_INSTANTIATE_COMPLEX(float)
 

@@ -1,5 +1,5 @@
-// complex.hpp -- the ComplexF64 / ComplexF32 path of librflu.so: what complex_gemm.hip, complex.hip, driver.cpp
-// (the C ABI) and host_entry.cpp (the host-pointer entries) need from each other.
+// complex.hpp -- the ComplexF64 / ComplexF32 path of librflu.so (DESIGN.md sections 4.5, 4.6): what complex_gemm.hip, complex.hip,
+// complex_solve.hip, driver.cpp (the C ABI) and host_entry.cpp (the host-pointer entries) need from each other.
 //
 // A complex array crosses every boundary as R* (R = double / float) pointing at interleaved (re, im) pairs -- the storage of Julia's
 // Complex{R} and numpy's complex128 / complex64 -- and every leading dimension counts COMPLEX elements.  Inside, the matrix lives in the
@@ -11,6 +11,12 @@
 namespace rflu {
 
 constexpr int CLEAF = 32;   // leaf width of the complex recursion (columns per leaf panel, rows of a base triangle)
+// The transposed / adjoint solve (complex_solve.hip).  Neither value is tuned and nobody has measured either: they are structural
+// starting values.  8 is the pass width of the real path's solves, 256 rows keep the launch count near n / 64.
+constexpr int CNARROW = 8;   // up to this many right-hand sides the solve works on B's columns in place (the few-right-hand-side path)
+constexpr int CNB = 256;     // rows of a diagonal block of that path: one streaming launch and one one-workgroup launch per block
+
+inline int64_t cworkspace_ld(int64_t n) { return (n + 7) / 8 * 8; }   // rows start on 64- / 128-byte boundaries
 
 // the argument rules of the getrf / getrs entries, one copy for the device entries (complex.hip) and the host entries (host_entry.cpp)
 inline int cgetrf_check_args(int64_t m, int64_t n, const void* A, int64_t lda, const int64_t* ipiv, int pivot, const int64_t* info)
@@ -35,6 +41,15 @@ inline int cgetrs_check_args(int64_t n, int64_t nrhs, const void* F, int64_t lda
     }
     return RFLU_OK;
 }
+// the transposed solves: conj = 0 is LAPACK's 'T', conj = 1 its 'C'; everything else as the forward solve, in its words
+inline int cgetrs_trans_check_args(int64_t n, int64_t nrhs, const void* F, int64_t lda, const void* B, int64_t ldb, int conj)
+{
+    if (conj != 0 && conj != 1) {
+        set_error("complex getrs_trans: conj must be 0 (transpose) or 1 (adjoint), got %d", conj);
+        return RFLU_ERR_ARG;
+    }
+    return cgetrs_check_args(n, nrhs, F, lda, B, ldb);
+}
 
 // complex_gemm.hip: C <- C - A * B, all row-major complex; A is M x K (lda), B is K x N (ldb), C is M x N (ldc)
 template <typename R>
@@ -48,10 +63,25 @@ int cgetrs_cm_dev(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, c
 template <typename R>
 int cgemm_public(Handle* h, int64_t M, int64_t N, int64_t K, const R* A, int64_t lda, const R* B, int64_t ldb, R* C, int64_t ldc);
 
+// complex.hip, for complex_solve.hip: the layout change out[r][c] = in[c][r] (conjugated when `conj`), and the recursive triangular
+// solves B <- T^-1 B on row-major operands with the triangle's diagonal stored (`unit` false) or taken as 1 (`unit` true)
+template <typename R>
+int launch_ctranspose(Handle* h, int64_t rows_out, int64_t cols_out, const R* in, int64_t ld_in, R* out, int64_t ld_out, bool conj = false);
+template <typename R>
+int ctri_lower_rec(Handle* h, int64_t n, int64_t nrhs, const R* T, int64_t ldt, R* B, int64_t ldb, bool unit);
+template <typename R>
+int ctri_upper_rec(Handle* h, int64_t n, int64_t nrhs, const R* T, int64_t ldt, R* B, int64_t ldb, bool unit);
+
+// complex_solve.hip: ldiv!(transpose(F), B) (conj = 0) and ldiv!(F', B) (conj = 1) on column-major device arrays; F is only read
+template <typename R>
+int cgetrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, const int64_t* ipiv, R* B, int64_t ldb, int conj);
+
 // host_entry.cpp: caller-owned column-major host arrays; copied back only on success
 template <typename R>
 int cgetrf_host(Handle* h, int64_t m, int64_t n, R* A, int64_t lda, int64_t* ipiv, int pivot, int64_t* info);
 template <typename R>
 int cgetrs_host(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, const int64_t* ipiv, R* B, int64_t ldb);
+template <typename R>
+int cgetrs_trans_host(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, const int64_t* ipiv, R* B, int64_t ldb, int conj);
 
 }  // namespace rflu

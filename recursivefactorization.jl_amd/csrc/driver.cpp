@@ -1145,6 +1145,18 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
         CHECK_HANDLE(handle);                                                                                         \
         return cgetrs_cm_dev<R>(H(handle), n, nrhs, F, lda, ipiv, B, ldb);                                            \
     }                                                                                                                 \
+    int rflu_getrs_trans_##SFX(rflu_handle_t handle, int64_t n, int64_t nrhs, const R* F, int64_t lda,                \
+                               const int64_t* ipiv, R* B, int64_t ldb, int conj)                                      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetrs_trans_host<R>(H(handle), n, nrhs, F, lda, ipiv, B, ldb, conj);                                  \
+    }                                                                                                                 \
+    int rflu_getrs_trans_##SFX##_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const R* F, int64_t lda,          \
+                                     const int64_t* ipiv, R* B, int64_t ldb, int conj)                                \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetrs_trans_cm_dev<R>(H(handle), n, nrhs, F, lda, ipiv, B, ldb, conj);                                \
+    }                                                                                                                 \
     int rflu_gemm_rm_##SFX##_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K, const R* A, int64_t lda,      \
                                  const R* B, int64_t ldb, R* C, int64_t ldc)                                          \
     {                                                                                                                 \

@@ -465,6 +465,27 @@ int cgetrs_host(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, con
     return RFLU_OK;
 }
 
+// ldiv!(transpose(F), B) / ldiv!(F', B): the same staging, the transposed device entry in the middle
+template <typename R>
+int cgetrs_trans_host(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, const int64_t* ipiv, R* B, int64_t ldb, int conj)
+{
+    typedef HostCx<R> Z;
+    RFLU_TRY(cgetrs_trans_check_args(n, nrhs, F, lda, B, ldb, conj));
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(Z)));
+    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * (size_t)nrhs * sizeof(Z)));
+    Z* dF = static_cast<Z*>(h->hostA_dev);
+    Z* dB = static_cast<Z*>(h->hostB_dev);
+    const int64_t* dipiv;
+    RFLU_TRY(copy_in(dF, reinterpret_cast<const Z*>(F), lda, n, n, h->stream));
+    RFLU_TRY(copy_in(dB, reinterpret_cast<const Z*>(B), ldb, n, nrhs, h->stream));
+    RFLU_TRY(stage_ipiv(h, ipiv, n, &dipiv));
+    RFLU_TRY(cgetrs_trans_cm_dev<R>(h, n, nrhs, reinterpret_cast<const R*>(dF), n, dipiv, reinterpret_cast<R*>(dB), n, conj));
+    RFLU_TRY(copy_out(reinterpret_cast<Z*>(B), ldb, dB, n, nrhs, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 #define RFLU_INSTANTIATE_HOST(T)                                                                                                      \
     template int getrf_host<T>(Handle*, int64_t, int64_t, T*, int64_t, int64_t*, int, int64_t, int64_t*);                             \
     template int getrs_host<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t, bool);                      \
@@ -474,7 +495,8 @@ RFLU_INSTANTIATE_HOST(double)
 RFLU_INSTANTIATE_HOST(float)
 #define RFLU_INSTANTIATE_HOST_COMPLEX(R)                                                                                              \
     template int cgetrf_host<R>(Handle*, int64_t, int64_t, R*, int64_t, int64_t*, int, int64_t*);                                     \
-    template int cgetrs_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t);
+    template int cgetrs_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t);                           \
+    template int cgetrs_trans_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t, int);
 RFLU_INSTANTIATE_HOST_COMPLEX(double)
 RFLU_INSTANTIATE_HOST_COMPLEX(float)
 

@@ -16,6 +16,8 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
     lu / lu! / ldiv! with T = ComplexF64 / ComplexF32 (test/runtests.jl:33-84)              -> ``lu_complex`` / ``lu_complex_`` /
                                                                                              ``ldiv_complex_`` (names of their own: ``lu``
                                                                                              keeps raising ``TypeError`` on complex input)
+    ldiv!(F', B) / ldiv!(transpose(F), B) for complex factors                               -> ``ldiv_complex_adjoint_`` /
+                                                                                             ``ldiv_complex_transpose_``
     inv / inv!, det, logabsdet, logdet on the LU object (stdlib LinearAlgebra)            -> ``inv`` / ``inv_`` / ``det`` / ``logabsdet`` /
                                                                                              ``logdet``; batched: ``inv_batched`` /
                                                                                              ``logabsdet_batched`` / ``det_batched``
@@ -420,12 +422,17 @@ def lu_complex(A, pivot=True, thread=False, **kwargs) -> LU:
     return lu_complex_(C, None, pivot, thread, **kwargs)
 
 
-def ldiv_complex_(F: LU, B, *, handle=None):
-    """``ldiv!(F, B)`` with the factors ``lu_complex_`` returned: overwrite ``B`` (a vector or a column-major n x k matrix of the factors'
-    dtype, on the factors' side of the bus) with ``A \\ B`` (``rflu_getrs_cf64`` / ``rflu_getrs_cf32`` and their ``_dev`` forms).  Raises
-    ``SingularException`` when ``F.info != 0``.  There is no complex ``ldiv!(F', B)``: an ``Adjoint`` factorization raises ``TypeError``."""
+def _ldiv_complex_call(F, B, handle, entry: str, extra: tuple, what: str):
+    """The checks and the call shared by ``ldiv_complex_``, ``ldiv_complex_transpose_`` and ``ldiv_complex_adjoint_``: shape, dtype,
+    column-major layout, ``F.info != 0`` -> ``SingularException``, the side of the bus; ``n == 0`` / ``nrhs == 0`` return ``B`` without
+    touching a device.  ``entry`` is the C entry without its suffixes (``rflu_getrs`` / ``rflu_getrs_trans``), ``extra`` its trailing
+    arguments."""
     if isinstance(F, Adjoint):
-        raise TypeError("ldiv_complex_: the adjoint solve of a complex factorization is not served (adjoint and transpose differ)")
+        if entry == "rflu_getrs":
+            raise TypeError("ldiv_complex_: an Adjoint-wrapped complex factorization is not served here (adjoint and transpose differ, and "
+                            "Transpose is an alias of Adjoint): call ldiv_complex_adjoint_ or ldiv_complex_transpose_ with the plain LU")
+        raise TypeError(f"{what} takes the plain LU that lu_complex_ returned, not an Adjoint wrapper (Transpose is an alias of Adjoint, "
+                        "so the wrapper cannot say which of the two solves is meant): the function's name does")
     if F.info != 0:
         raise SingularException(abs(F.info))
     A = F.factors
@@ -448,22 +455,51 @@ def ldiv_complex_(F: LU, B, *, handle=None):
             raise ValueError("a vector right-hand side must be contiguous (stride 1); copy the view first")
         if B.ndim == 2 and n > 1 and not (B.stride(0) == 1 and (nrhs <= 1 or B.stride(1) >= n)):
             raise ValueError("B must be column-major like the factors")
+        if n == 0 or nrhs == 0:
+            return B
         h = handle or _ffi.default_handle(A.device.index or 0)
         h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
         ldb = B.stride(1) if (B.ndim == 2 and nrhs > 1 and n > 1) else max(n, 1)
-        if n > 0 and nrhs > 0:
-            h.call(f"rflu_getrs_{sfx}_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), A.stride(1) if n > 1 else 1,
-                   ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), ctypes.c_void_p(B.data_ptr()), ldb)
+        h.call(f"{entry}_{sfx}_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), A.stride(1) if n > 1 else 1,
+               ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), ctypes.c_void_p(B.data_ptr()), ldb, *extra)
         return B
     if not (isinstance(B, np.ndarray) and B.dtype == A.dtype and (B.ndim == 1 and B.flags.c_contiguous or B.flags.f_contiguous)):
         raise TypeError("B must be a column-major numpy array of the factorization's dtype")
+    if n == 0 or nrhs == 0:
+        return B
     h = handle or _ffi.default_handle(0)
     h.set_stream(None)
     ipiv = None if nopiv else np.ascontiguousarray(F.ipiv, dtype=np.int64)
-    if n > 0 and nrhs > 0:
-        h.call(f"rflu_getrs_{sfx}", n, nrhs, ctypes.c_void_p(A.ctypes.data), max(n, 1),
-               ctypes.c_void_p(0 if ipiv is None else ipiv.ctypes.data), ctypes.c_void_p(B.ctypes.data), max(n, 1))
+    h.call(f"{entry}_{sfx}", n, nrhs, ctypes.c_void_p(A.ctypes.data), max(n, 1),
+           ctypes.c_void_p(0 if ipiv is None else ipiv.ctypes.data), ctypes.c_void_p(B.ctypes.data), max(n, 1), *extra)
     return B
+
+
+def ldiv_complex_(F: LU, B, *, handle=None):
+    """``ldiv!(F, B)`` with the factors ``lu_complex_`` returned: overwrite ``B`` (a vector or a column-major n x k matrix of the factors'
+    dtype, on the factors' side of the bus) with ``A \\ B`` (``rflu_getrs_cf64`` / ``rflu_getrs_cf32`` and their ``_dev`` forms).  Raises
+    ``SingularException`` when ``F.info != 0``.  An ``Adjoint`` factorization raises ``TypeError``: ``ldiv!(F', B)`` and
+    ``ldiv!(transpose(F), B)`` are ``ldiv_complex_adjoint_`` and ``ldiv_complex_transpose_``."""
+    return _ldiv_complex_call(F, B, handle, "rflu_getrs", (), "ldiv_complex_")
+
+
+def ldiv_complex_adjoint_(F: LU, B, *, handle=None):
+    """``ldiv!(F', B)`` for complex factors: overwrite ``B`` with ``A' \\ B``, ``A'`` the conjugate transpose (``rflu_getrs_trans_cf64`` /
+    ``_cf32`` and their ``_dev`` forms with ``conj = 1``, LAPACK's ``'C'``).  ``F`` is the plain ``LU`` that ``lu_complex_`` returned and
+    ``B`` as for ``ldiv_complex_``; the factors are only read.
+
+    This is a function of its own rather than a dispatch on a wrapper because in this package ``Transpose is Adjoint`` (one wrapper class,
+    right for real matrices), while for a complex factorization the adjoint and the transpose are different solves: a wrapper could
+    silently mean the wrong one, a function name cannot.  An ``Adjoint``-wrapped argument therefore raises ``TypeError``."""
+    return _ldiv_complex_call(F, B, handle, "rflu_getrs_trans", (1,), "ldiv_complex_adjoint_")
+
+
+def ldiv_complex_transpose_(F: LU, B, *, handle=None):
+    """``ldiv!(transpose(F), B)`` for complex factors: overwrite ``B`` with ``transpose(A) \\ B``, no conjugation (``rflu_getrs_trans_cf64``
+    / ``_cf32`` and their ``_dev`` forms with ``conj = 0``, LAPACK's ``'T'``).  Arguments as for ``ldiv_complex_adjoint_``, and a function
+    of its own for the same reason: ``Transpose is Adjoint`` here, so a wrapper could not tell this solve from the adjoint one.  An
+    ``Adjoint``-wrapped argument raises ``TypeError``."""
+    return _ldiv_complex_call(F, B, handle, "rflu_getrs_trans", (0,), "ldiv_complex_transpose_")
 
 
 def _unwrap_adjoint(F, what: str):
