@@ -48,7 +48,7 @@ enum rflu_path {
     RFLU_PATH_HIP_BLOCKED = 2,   /* right-looking block columns on one stream (profiling modes, devices without 256 CUs) */
     RFLU_PATH_HIP_LOOKAHEAD = 3, /* block-column lookahead / leaf-wise schedules on CU-masked streams */
     RFLU_PATH_HIP_ENGINE = 4,    /* the leaf-wise chain with every trailing update pulled by the persistent update engine (csrc/engine.hip) */
-    RFLU_PATH_HIP_BATCHED = 5    /* rflu_get{rf,rs}_batched_*: one launch of the batched kernels, one group of threads per matrix (csrc/batched.hip) */
+    RFLU_PATH_HIP_BATCHED = 5    /* rflu_get{rf,rs}_batched_*: one launch of the batched kernels, one group of threads per matrix (csrc/batched.hip, csrc/batched_complex.hip) */
 };
 
 /* kernel classes for the built-in per-kernel timers (rflu_profile_*) */
@@ -260,7 +260,7 @@ int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, c
  *   - every kernel is an in-order launch on the handle's stream and NONE waits for another workgroup: no cooperative launch, no flag,
  *     no RFLU_ERR_TIMEOUT from these entries.  Work is complete on return;
  *   - rflu_getrs_*: ldiv!(F, B) for any nrhs, F / ipiv as the factorization left them; a singular U yields Inf/NaN, no error status.
- *     There is no batched / mixed / inverse form;
+ *     The batched form is rflu_get{rf,rs}_batched_cf64_dev / _cf32_dev below; there is no mixed / inverse form;
  *   - rflu_getrs_trans_*: ldiv!(transpose(F), B) and ldiv!(F', B), which differ for these element types, so the entries take `conj`:
  *     conj = 0 solves transpose(A) x = b (LAPACK 'T', B <- P^T L^-T U^-T B), conj = 1 solves A' x = b (LAPACK 'C', B <- P^T L^-H U^-H B),
  *     any other value is RFLU_ERR_ARG.  Everything else is as rflu_getrs_*: storage, lda / ldb, NULL ipiv = NotIPIV, alignment, any
@@ -293,6 +293,36 @@ int rflu_getrs_trans_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, con
                               double* B_dev, int64_t ldb, int conj);
 int rflu_getrs_trans_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda, const int64_t* ipiv_dev,
                               float* B_dev, int64_t ldb, int conj);
+/* BATCHED COMPLEX: `batch` independent small ComplexF64 / ComplexF32 systems in one call (csrc/batched_complex.hip, DESIGN.md section
+ * 4.7).  Storage as in the other complex entries: double* / float* to interleaved (re, im) pairs; lda, ldb, strideA / strideF / strideB
+ * count COMPLEX elements.  Everything else is the contract of the BATCHED entries above, word for word: strided matrices (matrix b at
+ * A_dev + b*strideA complex elements), row_major = 0 / 1 with lda >= m / n, ipiv at ipiv_dev + b*stride_ipiv (1-based; NULL only with
+ * pivot == 0; a non-NULL ipiv with pivot == 0 is filled with the identity), info_dev a required DEVICE array of `batch` entries,
+ * B in the orientation of F; batch == 0, m == 0, n == 0 or nrhs == 0 succeed with nothing launched; negative sizes, too-small lda /
+ * strides and NULL pointers give RFLU_ERR_ARG with a message; work goes on the handle's stream and is complete on return.
+ *   - per matrix the semantics of the COMPLEX entries: pivot = the row of largest modulus hypot(re, im), strict '>' from 0, the lowest
+ *     row on ties, a NaN modulus never wins; a pivot with BOTH parts zero sets info once (1-based) and the elimination carries on
+ *     unscaled; inv(pivot) once per column and one multiply per row; pivot == 0 is NoPivot;
+ *   - rflu_getrs_batched_c*: trans = 0: B <- U^-1 L^-1 P B; trans = 1 (LAPACK 'T'): B <- P^T L^-T U^-T B, solves transpose(A) x = b;
+ *     trans = 2 (LAPACK 'C'): B <- P^T L^-H U^-H B, solves A' x = b.  The two differ for these element types; any other value is
+ *     RFLU_ERR_ARG.  Any nrhs.  A singular matrix yields Inf/NaN in its own right-hand sides only;
+ *   - ONE launch up to max(m, n) <= 128 (ComplexF32) and max(m, n) <= 64 (ComplexF64; 65 x 64 x 16 B of LDS per matrix): a group of
+ *     64..256 threads per matrix, the matrix in LDS between its one load and its one store, no kernel waits for another workgroup;
+ *     rflu_last_path reports RFLU_PATH_HIP_BATCHED;
+ *   - above that limit a COLUMN-MAJOR batch is looped over the single-matrix complex device path (rflu_getrf_c*_dev, rflu_getrs_c*_dev /
+ *     rflu_getrs_trans_c*_dev), each matrix's info written into info_dev: correct, NOT fast, no size cliff, and rflu_last_path reports
+ *     what that path reports.  A ROW-MAJOR batch above the limit is RFLU_ERR_ARG with a message that says so: the single-matrix
+ *     complex path is column-major only. */
+int rflu_getrf_batched_cf64_dev(rflu_handle_t handle, int64_t batch, int64_t m, int64_t n, double* A_dev, int64_t lda, int64_t strideA,
+                                int row_major, int64_t* ipiv_dev, int64_t stride_ipiv, int pivot, int64_t* info_dev);
+int rflu_getrf_batched_cf32_dev(rflu_handle_t handle, int64_t batch, int64_t m, int64_t n, float* A_dev, int64_t lda, int64_t strideA,
+                                int row_major, int64_t* ipiv_dev, int64_t stride_ipiv, int pivot, int64_t* info_dev);
+int rflu_getrs_batched_cf64_dev(rflu_handle_t handle, int64_t batch, int64_t n, int64_t nrhs, const double* F_dev, int64_t lda,
+                                int64_t strideF, int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, double* B_dev, int64_t ldb,
+                                int64_t strideB, int trans);
+int rflu_getrs_batched_cf32_dev(rflu_handle_t handle, int64_t batch, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda,
+                                int64_t strideF, int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* B_dev, int64_t ldb,
+                                int64_t strideB, int trans);
 /* building block: C <- C - A*B, all row-major complex: A is M x K (lda), B is K x N (ldb), C is M x N (ldc).  Four real MFMA products
  * per K step; 16-byte loads where the pointers (and, for _cf32, even lda / ldb) allow, element by element otherwise -- same arithmetic. */
 int rflu_gemm_rm_cf64_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K, const double* A_dev, int64_t lda,

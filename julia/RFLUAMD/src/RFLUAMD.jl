@@ -169,6 +169,53 @@ function getrs_batched_dev!(F::Ptr{Float32}, batch::Integer, n::Integer, nrhs::I
     return B
 end
 
+# The complex batches (`rflu_get{rf,rs}_batched_cf64_dev` / `_cf32_dev`, include/rflu.h): the same argument lists, pointers to
+# `ComplexF64` / `ComplexF32` device memory `reinterpret`ed to the real type, `lda` / `ldb` and every stride in COMPLEX elements.  One
+# launch up to 64 (`ComplexF64`) / 128 (`ComplexF32`) rows and columns; larger column-major batches are looped, larger row-major ones
+# are an error.  The solve takes `trans` as LAPACK's letter: 'N' (A), 'T' (transpose(A)) or 'C' (A'), which differ for these elements.
+function getrf_batched_dev!(A::Ptr{ComplexF64}, batch::Integer, m::Integer, n::Integer, lda::Integer, strideA::Integer, row_major::Bool,
+                            ipiv::Ptr{Int64}, stride_ipiv::Integer, pivot::Bool, info::Ptr{Int64})
+    st = ccall((:rflu_getrf_batched_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Int64}, Int64, Cint, Ptr{Int64}),
+               handle(), batch, m, n, reinterpret(Ptr{Float64}, A), lda, strideA, Cint(row_major), ipiv, stride_ipiv, Cint(pivot), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function getrf_batched_dev!(A::Ptr{ComplexF32}, batch::Integer, m::Integer, n::Integer, lda::Integer, strideA::Integer, row_major::Bool,
+                            ipiv::Ptr{Int64}, stride_ipiv::Integer, pivot::Bool, info::Ptr{Int64})
+    st = ccall((:rflu_getrf_batched_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Int64}, Int64, Cint, Ptr{Int64}),
+               handle(), batch, m, n, reinterpret(Ptr{Float32}, A), lda, strideA, Cint(row_major), ipiv, stride_ipiv, Cint(pivot), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function batched_trans_code(trans::AbstractChar)
+    trans == 'N' && return Cint(0)
+    trans == 'T' && return Cint(1)
+    trans == 'C' && return Cint(2)
+    throw(ArgumentError("trans must be 'N', 'T' or 'C'"))
+end
+
+function getrs_batched_dev!(F::Ptr{ComplexF64}, batch::Integer, n::Integer, nrhs::Integer, lda::Integer, strideF::Integer, row_major::Bool,
+                            ipiv::Ptr{Int64}, stride_ipiv::Integer, B::Ptr{ComplexF64}, ldb::Integer, strideB::Integer, trans::AbstractChar)
+    st = ccall((:rflu_getrs_batched_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Int64, Cint),
+               handle(), batch, n, nrhs, reinterpret(Ptr{Float64}, F), lda, strideF, Cint(row_major), ipiv, stride_ipiv, reinterpret(Ptr{Float64}, B), ldb, strideB, batched_trans_code(trans))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+function getrs_batched_dev!(F::Ptr{ComplexF32}, batch::Integer, n::Integer, nrhs::Integer, lda::Integer, strideF::Integer, row_major::Bool,
+                            ipiv::Ptr{Int64}, stride_ipiv::Integer, B::Ptr{ComplexF32}, ldb::Integer, strideB::Integer, trans::AbstractChar)
+    st = ccall((:rflu_getrs_batched_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Int64}, Int64, Ptr{Float32}, Int64, Int64, Cint),
+               handle(), batch, n, nrhs, reinterpret(Ptr{Float32}, F), lda, strideF, Cint(row_major), ipiv, stride_ipiv, reinterpret(Ptr{Float32}, B), ldb, strideB, batched_trans_code(trans))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
 "`ldiv!(F, B)` on the GPU: B <- U^-1 L^-1 P B (stdlib `ldiv!(::LU, B)`; the package's own for NotIPIV, src/lu.jl:60-64)"
 function getrs!(F::StridedMatrix{Float64}, ipiv::Ptr{Int64}, B::StridedVecOrMat{Float64})
     n = size(F, 1)

@@ -97,6 +97,33 @@ if Base.find_package("AMDGPU") !== nothing
             @test norm(A[:, :, k] * x[:, k] - b[:, k]) < 1000n * eps(T) * norm(A[:, :, k]) * norm(x[:, k])
         end
     end
+    # complex batches: info of a singular matrix stays its own; 'N', 'T' and 'C' each solve their own operator
+    @testset "RFLUAMD complex batched getrf / getrs ($T)" for T in (ComplexF64, ComplexF32)
+        n, batch = 32, 1024
+        A = rand(T, n, n, batch); A[:, 5, 7] .= 0
+        b = rand(T, n, batch)
+        dA = ROCArray(A)
+        dipiv, dinfo = ROCArray(zeros(Int64, n, batch)), ROCArray(fill(Int64(-1), batch))
+        GC.@preserve dA dipiv dinfo begin
+            RFLUAMD.getrf_batched_dev!(Ptr{T}(UInt(pointer(dA))), batch, n, n, n, n * n, false, Ptr{Int64}(UInt(pointer(dipiv))), n, true,
+                                       Ptr{Int64}(UInt(pointer(dinfo))))
+            @test RFLUAMD.last_path() == 5
+        end
+        info = Array(dinfo)
+        @test info[7] == 5 && count(!iszero, info) == 1
+        for (trans, op) in (('N', identity), ('T', transpose), ('C', adjoint))
+            dB = ROCArray(b)
+            GC.@preserve dA dB dipiv begin
+                RFLUAMD.getrs_batched_dev!(Ptr{T}(UInt(pointer(dA))), batch, n, 1, n, n * n, false, Ptr{Int64}(UInt(pointer(dipiv))), n,
+                                           Ptr{T}(UInt(pointer(dB))), n, n, trans)
+            end
+            x = Array(dB)
+            for k in (1, 2, 1000, batch)
+                M = op(A[:, :, k])
+                @test norm(M * x[:, k] - b[:, k]) < 1000n * eps(real(T)) * norm(M) * norm(x[:, k])
+            end
+        end
+    end
     # mixed precision: Float32 factors, Float64 refinement; A and b untouched, dsgesv's rule met, the residual kernel alone
     @testset "RFLUAMD mixed-precision solve" begin
         n, nrhs = 1000, 9

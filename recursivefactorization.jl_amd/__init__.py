@@ -28,6 +28,7 @@ from .lu import (  # noqa: F401
     ldiv_batched_,
     ldiv_complex_,
     ldiv_complex_adjoint_,
+    ldiv_complex_batched_,
     ldiv_complex_transpose_,
     ldiv_mixed,
     logabsdet,
@@ -39,6 +40,8 @@ from .lu import (  # noqa: F401
     lu_batched_,
     lu_complex,
     lu_complex_,
+    lu_complex_batched,
+    lu_complex_batched_,
     lu_mixed,
     normalize_pivot,
 )
@@ -57,6 +60,7 @@ __all__ = [
     "ButterflyWorkspace", "butterfly_workspace", "butterfly_solve_", "butterfly_mul_",
     "lu", "lu_", "ldiv_", "LU", "lu_batched", "lu_batched_", "ldiv_batched_", "BatchedLU", "lu_mixed", "ldiv_mixed", "MixedLU", "NotConvergedError", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
     "lu_complex", "lu_complex_", "ldiv_complex_", "ldiv_complex_adjoint_", "ldiv_complex_transpose_",
+    "lu_complex_batched", "lu_complex_batched_", "ldiv_complex_batched_",
     "inv", "inv_", "det", "logabsdet", "logdet", "inv_batched", "logabsdet_batched", "det_batched",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

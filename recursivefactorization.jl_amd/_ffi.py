@@ -94,6 +94,8 @@ _COMPLEX = {
     "rflu_getrs_trans_{s}": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int]),
     "rflu_getrs_trans_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_int]),
     "rflu_gemm_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64]),
+    "rflu_getrf_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_int, c_p]),
+    "rflu_getrs_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int]),
 }
 
 EXPORTS = dict(_PLAIN)

@@ -1,0 +1,484 @@
+// batched_complex.hip -- LU and solve for a BATCH of small independent ComplexF64 / ComplexF32 matrices:
+// batched.hip's two kernels with the element of complex.hip.  ComplexF32: max(m, n) <= CBATCHED_MAX_DIM_CF32 = 128 (the bytes of the
+// Float64 real kernel), ComplexF64: max(m, n) <= CBATCHED_MAX_DIM_CF64 = 64 (65 x 64 x 16 B = 66.5 KB; two matrices and their passes of
+// right-hand sides fit the 160 KiB of a CU).
+//
+// Shape of both kernels, as in batched.hip: a GROUP of 64 / 128 / 256 threads (max(m, n) <= 32 / 64 / 128) owns one matrix; a 256-thread
+// workgroup holds 4 / 2 / 1 groups.  The matrix is read from HBM once into LDS, worked on there, and written once.  The matrices never
+// talk to each other: no global-memory hand-off, no cooperative launch, nothing a workgroup could wait for -- one workgroup barrier per
+// pivot column is all the synchronisation there is.  A group beyond the end of the batch works on zeros and stores nothing.
+//
+// LDS image: INTERLEAVED elements (re, im side by side, 16 / 8 bytes, moved as one double2 / float2), column-major with an ODD leading
+// dimension counted in elements.  Chosen over separate re / im planes because it keeps the property the planes were offered for -- a
+// column and a row are both bank-conflict free -- at half the LDS instructions: a column is contiguous; along a row consecutive lanes
+// are ld * 16 bytes apart, i.e. 4 * ld dwords, and with ld odd the 16 lanes that one ds_read_b128 services together land on 16
+// different groups of 4 banks (ComplexF32: ds_read_b64, 2 * ld dwords apart, 32 lanes on 32 different bank pairs).  One element is one
+// LDS instruction instead of two, and the image of a caller's element is a plain copy.
+//
+// Factorization, per matrix the semantics of _generic_lufact! (the reference's src/lu.jl:290-338) for a complex element exactly as
+// cleaf_kernel (complex.hip) states them: the pivot of column k is the row of largest modulus cmodulus(z) = hypot(re, im), strict '>'
+// from 0 with the lowest current row on ties (a NaN modulus never wins, an all-zero column keeps row k); a pivot whose two parts are
+// zero sets info once and the elimination carries on unscaled; otherwise inv = cdiv({1, 0}, piv) once per column, one cmul per row,
+// and the rank-1 update csub(a, cmul(l, u)).  NoPivot takes row k.  The mechanics are batched.hip's:
+//   * thread (r, c) of a group owns row r and every CT-th column; rows are never moved in LDS: a row carries its current POSITION
+//     (interchange by renaming) and goes to that position in the one store at the end;
+//   * every wave of the group finds the pivot of column k redundantly (two rows per lane, one 64-bit DPP max over the bits of the
+//     modulus -- a non-negative real, so its bits order like its value; 0 for zero and NaN; the low-position tie-break only when two
+//     lanes hold the same maximum), so no wave waits for another one's search;
+//   * l_ik is written back one step late by the row's first thread.  One barrier per column.
+// Solve: factors and 8 right-hand sides in LDS; the interchanges composed into one permutation in registers by the group's first wave
+// while the factors arrive; two column-oriented substitutions with one barrier per column.  trans = 0: B <- U^-1 L^-1 P B; trans = 1
+// (LAPACK 'T'): B <- P^T L^-T U^-T B; trans = 2 ('C'): B <- P^T L^-H U^-H B -- both read the same LDS image by rows, 'C' conjugates the
+// element as it is read.  Diagonal: ONE reciprocal cdiv({1, 0}, d_kk) per column, formed once per matrix into LDS, then multiplies:
+// a complex division per right-hand side and thread would cost more than the whole rank-1 step it feeds, and the extra rounding
+// (a few eps per element) is far inside the 20 n eps backward-error bar of the tests.  A zero on the diagonal gives Inf / NaN in that
+// matrix's own right-hand sides only.
+// (The DPP maximum and the thread geometry are restated here: batched.hip is the real-only file and includes nothing but
+// rflu_internal.hpp.)
+#include <algorithm>
+
+#include "complex_dev.hpp"
+
+namespace rflu {
+
+namespace {
+
+typedef unsigned long long cu64;
+constexpr int CBT = 256;                   // threads per workgroup
+constexpr int CBNR = 8;                    // right-hand sides per pass of the solve
+constexpr unsigned CPOS_NONE = 0x7fffffffu;
+
+template <typename R> struct CVec;
+template <> struct CVec<double> { typedef double2 type; };
+template <> struct CVec<float> { typedef float2 type; };
+
+// the LDS image of one matrix (or of a pass of right-hand sides): element (i, j) at s[i + j * ld], one vector load / store each
+template <typename R>
+struct CImage {
+    typename CVec<R>::type* s;
+    int ld;
+    __device__ __forceinline__ Cx<R> get(int i, int j) const { const typename CVec<R>::type v = s[i + j * ld]; return Cx<R>{v.x, v.y}; }
+    __device__ __forceinline__ void put(int i, int j, Cx<R> z) const { typename CVec<R>::type v; v.x = z.re; v.y = z.im; s[i + j * ld] = v; }
+};
+
+struct CGeo {
+    int tpm;        // threads per matrix (64 | 128 | 256)
+    int tpm_log;
+    int rt_log;     // log2 of RT = rows of the (row, column-slice) thread grid: the smallest power of two >= m
+    int ct_log;     // log2 of the same for the columns (row-major loads and stores: lanes along a row)
+    int ld;         // LDS leading dimension in complex elements (odd)
+    unsigned group_bytes;
+    unsigned off_x, off_d, off_int;   // byte offsets inside a group's LDS: right-hand sides, diagonal reciprocals (solve), integer arrays
+};
+
+int clog2_ceil(int64_t v)
+{
+    int l = 0;
+    for (; ((int64_t)1 << l) < v; ++l) {}
+    return l;
+}
+
+CGeo cbatched_geo(int64_t m, int64_t n, size_t csize, bool solve)   // csize: bytes of a complex element
+{
+    CGeo g;
+    const int64_t mx = std::max(m, n);
+    g.tpm_log = mx <= 32 ? 6 : (mx <= 64 ? 7 : 8);
+    g.tpm = 1 << g.tpm_log;
+    g.rt_log = clog2_ceil(m);
+    g.ct_log = clog2_ceil(n);
+    g.ld = (int)(m | 1);
+    size_t off = (size_t)g.ld * (size_t)n * csize;   // csize is 8 or 16 and the base is 16-byte aligned: every section below stays aligned
+    off = (off + 15) & ~(size_t)15;
+    g.off_x = (unsigned)off;
+    if (solve) off += ((size_t)g.ld * CBNR * csize + 15) & ~(size_t)15;
+    g.off_d = (unsigned)off;
+    if (solve) off += ((size_t)n * csize + 15) & ~(size_t)15;
+    g.off_int = (unsigned)off;
+    off += ((size_t)(m + std::min(m, n)) * sizeof(int) + 15) & ~(size_t)15;
+    g.group_bytes = (unsigned)off;
+    return g;
+}
+
+// the modulus as an integer that orders like it; 0 for zeros and NaN (neither ever beats a candidate: `absi > amax`, lu.jl:301)
+__device__ __forceinline__ cu64 ckey(double v) { return (v > 0.0) ? (cu64)__double_as_longlong(v) : 0ull; }
+__device__ __forceinline__ cu64 ckey(float v) { return (v > 0.0f) ? (cu64)__float_as_uint(v) : 0ull; }
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ cu64 cdpp_max(cu64 v)
+{
+    const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+    const int olo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
+    const int ohi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
+    const cu64 o = ((cu64)(unsigned)ohi << 32) | (cu64)(unsigned)olo;
+    return o > v ? o : v;
+}
+// maximum over the 64 lanes of a wave (all of them active), wave-uniform: the DPP ladder of batched.hip
+__device__ __forceinline__ cu64 cwave_max(cu64 v)
+{
+    v = cdpp_max<0xB1, 0xf>(v);    // quad_perm:[1,0,3,2]
+    v = cdpp_max<0x4E, 0xf>(v);    // quad_perm:[2,3,0,1]
+    v = cdpp_max<0x141, 0xf>(v);   // row_half_mirror
+    v = cdpp_max<0x140, 0xf>(v);   // row_mirror
+    v = cdpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+    v = cdpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds the maximum
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((cu64)hi << 32) | (cu64)lo;
+}
+
+// ---- the one load ----------------------------------------------------------------------------------------------------------------
+// element (i, j) of the caller's matrix: G[i + j*lda] (column-major) or G[i*lda + j] (row-major), lda in complex elements; in LDS
+// always (i, j) of the image.  Column-major: lanes along a column (thread grid RT x TPM/RT); row-major: lanes along a row (CT x TPM/CT).
+// `valid` = false (a group beyond the end of the batch): zeros.
+template <typename R>
+__device__ __forceinline__ void cbload_matrix(const CImage<R>& S, const Cx<R>* G, int64_t lda, int row_major, int m, int n, const CGeo& g,
+                                              int t, bool valid)
+{
+    const Cx<R> zero{R(0), R(0)};
+    if (!row_major) {
+        const int r = t & ((1 << g.rt_log) - 1), c0 = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+        if (r < m)
+            for (int j = c0; j < n; j += cs) S.put(r, j, valid ? G[r + (int64_t)j * lda] : zero);
+    } else {
+        const int c = t & ((1 << g.ct_log) - 1), r0 = t >> g.ct_log, rs = g.tpm >> g.ct_log;
+        if (c < n)
+            for (int i = r0; i < m; i += rs) S.put(i, c, valid ? G[(int64_t)i * lda + c] : zero);
+    }
+}
+
+template <typename R>
+struct CFactorArgs {
+    Cx<R>* A;
+    int64_t* ipiv;
+    int64_t* info;
+    int64_t lda, strideA, stride_ipiv, batch;
+    int m, n, row_major, pivot;
+    CGeo g;
+};
+
+template <typename R>
+__global__ void __launch_bounds__(CBT) cgetrf_batched_kernel(CFactorArgs<R> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char cbsmem[];
+    const CGeo g = a.g;
+    const int m = a.m, n = a.n, mn = m < n ? m : n;
+    const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1), lane = t & 63;
+    const int64_t b = (int64_t)blockIdx.x * (CBT >> g.tpm_log) + grp;
+    const bool valid = b < a.batch;
+    unsigned char* base = cbsmem + (size_t)grp * g.group_bytes;
+    const CImage<R> S{reinterpret_cast<typename CVec<R>::type*>(base), g.ld};
+    unsigned* spiv = reinterpret_cast<unsigned*>(base + g.off_int);   // [mn] position the pivot of step k came from
+    unsigned* spos = spiv + mn;                                        // [m]  final position of every row
+    Cx<R>* G = a.A + (valid ? b : 0) * a.strideA;
+
+    cbload_matrix<R>(S, G, a.lda, a.row_major, m, n, g, t, valid);
+
+    // the row this thread updates, and the rows this lane looks at in the pivot search (every wave searches all rows)
+    const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+    bool act = r < m;
+    unsigned mypos = act ? (unsigned)r : CPOS_NONE;
+    unsigned pos0 = lane < m ? (unsigned)lane : CPOS_NONE, pos1 = lane + 64 < m ? (unsigned)(lane + 64) : CPOS_NONE;
+    Cx<R> lprev{R(0), R(0)};
+    bool updprev = false;
+    int info = 0;
+
+    for (int k = 0; k < mn; ++k) {
+        __syncthreads();   // elimination k-1 is in LDS (k == 0: the matrix)
+        if (updprev && c == 0) S.put(r, k - 1, lprev);   // nobody reads column k-1 any more
+        int q = k;                   // row (as loaded) that becomes the pivot row
+        unsigned gp = (unsigned)k;   // its current position
+        if (a.pivot) {
+            cu64 key = 0;
+            unsigned pos = CPOS_NONE;
+            int phys = 0;
+            if (pos0 != CPOS_NONE) {
+                key = ckey(cmodulus(S.get(lane, k)));
+                pos = pos0;
+                phys = lane;
+            }
+            if (pos1 != CPOS_NONE) {
+                const cu64 k1 = ckey(cmodulus(S.get(lane + 64, k)));
+                if (pos == CPOS_NONE || k1 > key || (k1 == key && pos1 < pos)) {
+                    key = k1;
+                    pos = pos1;
+                    phys = lane + 64;
+                }
+            }
+            const cu64 mx = cwave_max(key);
+            const bool hit = pos != CPOS_NONE && key == mx;
+            cu64 mask = __ballot(hit);
+            if (__popcll(mask) > 1) {   // exact ties (and columns of zeros / NaN): the lowest position
+                const unsigned pm = ~(unsigned)cwave_max(hit ? (cu64)(~pos) : 0ull);
+                mask = __ballot(hit && pos == pm);
+            }
+            // position k is always among the candidates, so mask != 0
+            const int wl = __builtin_amdgcn_readfirstlane(__ffsll((long long)mask) - 1) & 63;
+            gp = (unsigned)__builtin_amdgcn_readlane((int)pos, wl);
+            q = __builtin_amdgcn_readlane(phys, wl);
+            if (pos0 != CPOS_NONE) pos0 = (lane == q) ? CPOS_NONE : (pos0 == (unsigned)k ? gp : pos0);
+            if (pos1 != CPOS_NONE) pos1 = (lane + 64 == q) ? CPOS_NONE : (pos1 == (unsigned)k ? gp : pos1);
+        }
+        const Cx<R> piv = S.get(q, k);
+        const bool zero = piv.re == R(0) && piv.im == R(0);   // iszero: both parts
+        const Cx<R> inv = zero ? Cx<R>{R(1), R(0)} : cdiv(Cx<R>{R(1), R(0)}, piv);
+        if (t == 0) {
+            spiv[k] = gp;
+            if (zero && info == 0) info = k + 1;
+        }
+        updprev = false;
+        if (act) {
+            if (r == q) {
+                act = false;
+                mypos = (unsigned)k;
+            } else {
+                if (mypos == (unsigned)k) mypos = gp;
+                const Cx<R> aik = S.get(r, k);
+                const Cx<R> l = zero ? aik : cmul(aik, inv);   // a zero pivot: the column stays as it is
+#pragma unroll 4
+                for (int j = k + 1 + c; j < n; j += cs) S.put(r, j, csub(S.get(r, j), cmul(l, S.get(q, j))));
+                lprev = l;
+                updprev = true;
+            }
+        }
+    }
+    __syncthreads();
+    if (updprev && c == 0) S.put(r, mn - 1, lprev);
+    if (c == 0 && r < m) spos[r] = mypos;
+    __syncthreads();
+
+    if (!valid) return;
+    if (!a.row_major) {
+        if (r < m)
+            for (int j = c; j < n; j += cs) G[(int64_t)mypos + (int64_t)j * a.lda] = S.get(r, j);
+    } else {
+        const int cc = t & ((1 << g.ct_log) - 1), r0 = t >> g.ct_log, rs = g.tpm >> g.ct_log;
+        if (cc < n)
+            for (int i = r0; i < m; i += rs) G[(int64_t)spos[i] * a.lda + cc] = S.get(i, cc);
+    }
+    if (a.ipiv) {
+        int64_t* ip = a.ipiv + b * a.stride_ipiv;
+        for (int k = t; k < mn; k += g.tpm) ip[k] = (int64_t)spiv[k] + 1;
+    }
+    if (t == 0) a.info[b] = (int64_t)info;
+}
+
+template <typename R>
+struct CSolveArgs {
+    const Cx<R>* F;
+    const int64_t* ipiv;
+    Cx<R>* B;
+    int64_t lda, strideF, stride_ipiv, ldb, strideB, batch, nrhs;
+    int n, row_major, trans;
+    CGeo g;
+};
+
+// F(i, k) of the triangle being solved.  MODE 0: the LDS image by columns; 1 ('T'): by rows; 2 ('C'): by rows, conjugated as it is read
+template <typename R, int MODE>
+__device__ __forceinline__ Cx<R> cbf(const CImage<R>& S, int i, int k)
+{
+    Cx<R> z = MODE ? S.get(k, i) : S.get(i, k);
+    if (MODE == 2) z.im = -z.im;
+    return z;
+}
+
+// x <- op(F)^-1 x on the group's pass of right-hand sides: a unit or non-unit LOWER triangle forward, then the other one backward.
+// Column-oriented: after the barrier of step k every thread reads x_k (for the non-unit triangle it scales by 1 / f_kk for itself; the
+// stored x_k stays unscaled until the triangle is done, so nobody reads a value that is being replaced), then takes it out of its own
+// row.  D[k] = 1 / op(F)(k, k).
+template <typename R, int MODE>
+__device__ __forceinline__ void cbsubstitute(const CImage<R>& S, const CImage<R>& X, const CImage<R>& D, int n, int nr, int r, int c, int cs)
+{
+    constexpr bool UNIT_LOWER = MODE == 0;   // L (unit) forward and U backward; transposed: U^T forward and L^T (unit) backward
+    for (int k = 0; k < n; ++k) {
+        if (r > k && r < n) {
+            const Cx<R> f = cbf<R, MODE>(S, r, k);
+            const Cx<R> d = D.get(k, 0);
+            for (int j = c; j < nr; j += cs) {
+                const Cx<R> xk = UNIT_LOWER ? X.get(k, j) : cmul(X.get(k, j), d);
+                X.put(r, j, csub(X.get(r, j), cmul(f, xk)));
+            }
+        }
+        __syncthreads();
+    }
+    if (!UNIT_LOWER) {
+        if (r < n) {
+            const Cx<R> d = D.get(r, 0);
+            for (int j = c; j < nr; j += cs) X.put(r, j, cmul(X.get(r, j), d));
+        }
+        __syncthreads();
+    }
+    for (int k = n - 1; k >= 0; --k) {
+        if (r < k) {
+            const Cx<R> f = cbf<R, MODE>(S, r, k);
+            const Cx<R> d = D.get(k, 0);
+            for (int j = c; j < nr; j += cs) {
+                const Cx<R> xk = UNIT_LOWER ? cmul(X.get(k, j), d) : X.get(k, j);
+                X.put(r, j, csub(X.get(r, j), cmul(f, xk)));
+            }
+        }
+        __syncthreads();
+    }
+    if (UNIT_LOWER) {
+        if (r < n) {
+            const Cx<R> d = D.get(r, 0);
+            for (int j = c; j < nr; j += cs) X.put(r, j, cmul(X.get(r, j), d));
+        }
+        __syncthreads();
+    }
+}
+
+template <typename R>
+__global__ void __launch_bounds__(CBT) cgetrs_batched_kernel(CSolveArgs<R> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char cbsmem[];
+    const CGeo g = a.g;
+    const int n = a.n;
+    const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1), lane = t & 63;
+    const int64_t b = (int64_t)blockIdx.x * (CBT >> g.tpm_log) + grp;
+    const bool valid = b < a.batch;
+    unsigned char* base = cbsmem + (size_t)grp * g.group_bytes;
+    const CImage<R> S{reinterpret_cast<typename CVec<R>::type*>(base), g.ld};
+    const CImage<R> X{reinterpret_cast<typename CVec<R>::type*>(base + g.off_x), g.ld};
+    const CImage<R> D{reinterpret_cast<typename CVec<R>::type*>(base + g.off_d), 0};   // [n]: reciprocal of the diagonal
+    int* sperm = reinterpret_cast<int*>(base + g.off_int);   // [n]: row i of P*B is row sperm[i] of B
+    const int64_t bb = valid ? b : 0;
+    const Cx<R>* F = a.F + bb * a.strideF;
+    Cx<R>* B = a.B + bb * a.strideB;
+
+    cbload_matrix<R>(S, F, a.lda, a.row_major, n, n, g, t, valid);
+    if (t < 64) {
+        // the interchanges k <-> ipiv[k]-1, k = 0 .. n-1, composed into one permutation: two entries per lane, 2 n readlanes
+        int p0 = lane, p1 = lane + 64, i0 = lane, i1 = lane + 64;
+        if (a.ipiv && valid) {
+            const int64_t* ip = a.ipiv + b * a.stride_ipiv;
+            if (lane < n) i0 = (int)(ip[lane] - 1);
+            if (lane + 64 < n) i1 = (int)(ip[lane + 64] - 1);
+        }
+        if (a.ipiv) {
+            for (int k = 0; k < n; ++k) {
+                const int ku = __builtin_amdgcn_readfirstlane(k);
+                int p = ku < 64 ? __builtin_amdgcn_readlane(i0, ku) : __builtin_amdgcn_readlane(i1, ku - 64);
+                if (p <= ku || p >= n) continue;   // nothing to exchange (or not an interchange getrf could have written)
+                const int vk = ku < 64 ? __builtin_amdgcn_readlane(p0, ku) : __builtin_amdgcn_readlane(p1, ku - 64);
+                const int vp = p < 64 ? __builtin_amdgcn_readlane(p0, p) : __builtin_amdgcn_readlane(p1, p - 64);
+                if (lane == (ku & 63)) { if (ku < 64) p0 = vp; else p1 = vp; }
+                if (lane == (p & 63)) { if (p < 64) p0 = vk; else p1 = vk; }
+            }
+        }
+        if (lane < n) sperm[lane] = p0;
+        if (lane + 64 < n) sperm[lane + 64] = p1;
+    }
+    __syncthreads();
+    if (t < n) {   // one reciprocal per column for the whole solve; conj(1 / d) = 1 / conj(d) term by term in cdiv
+        Cx<R> d = S.get(t, t);
+        if (a.trans == 2) d.im = -d.im;
+        D.put(t, 0, cdiv(Cx<R>{R(1), R(0)}, d));
+    }
+    __syncthreads();
+
+    const Cx<R> zero{R(0), R(0)};
+    const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+    const int rr = t & (CBNR - 1), ri0 = t >> 3, ris = g.tpm >> 3;   // row-major right-hand sides: lanes along a row of B
+    for (int64_t j0 = 0; j0 < a.nrhs; j0 += CBNR) {
+        const int nr = (int)(a.nrhs - j0 < CBNR ? a.nrhs - j0 : CBNR);
+        // row i of the pass: from row perm[i] of B (forward solve: P B), or row i (transposed: the interchanges come last)
+        if (!a.row_major) {
+            if (r < n) {
+                const int src = a.trans ? r : sperm[r];
+                for (int j = c; j < nr; j += cs) X.put(r, j, valid ? B[src + (j0 + j) * a.ldb] : zero);
+            }
+        } else if (rr < nr) {
+            for (int i = ri0; i < n; i += ris) {
+                const int src = a.trans ? i : sperm[i];
+                X.put(i, rr, valid ? B[(int64_t)src * a.ldb + j0 + rr] : zero);
+            }
+        }
+        __syncthreads();
+        if (a.trans == 0) cbsubstitute<R, 0>(S, X, D, n, nr, r, c, cs);
+        else if (a.trans == 1) cbsubstitute<R, 1>(S, X, D, n, nr, r, c, cs);
+        else cbsubstitute<R, 2>(S, X, D, n, nr, r, c, cs);
+        if (valid) {
+            if (!a.row_major) {
+                if (r < n) {
+                    const int dst = a.trans ? sperm[r] : r;
+                    for (int j = c; j < nr; j += cs) B[dst + (j0 + j) * a.ldb] = X.get(r, j);
+                }
+            } else if (rr < nr) {
+                for (int i = ri0; i < n; i += ris) {
+                    const int dst = a.trans ? sperm[i] : i;
+                    B[(int64_t)dst * a.ldb + j0 + rr] = X.get(i, rr);
+                }
+            }
+        }
+        __syncthreads();   // the pass has left LDS before the next one arrives
+    }
+}
+
+template <typename K>
+int cbatched_lds_attr(bool* done, K kernel, size_t lds)
+{
+    if (lds > 64 * 1024 && !*done) {   // above the default limit a kernel has to ask once (160 KiB per CU on gfx950)
+        RFLU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        *done = true;
+    }
+    return RFLU_OK;
+}
+
+}  // namespace
+
+template <typename R>
+bool cbatched_fits(int64_t m, int64_t n)
+{
+    return std::max(m, n) <= (sizeof(R) == 8 ? CBATCHED_MAX_DIM_CF64 : CBATCHED_MAX_DIM_CF32);
+}
+
+template <typename R>
+int launch_cgetrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, R* A, int64_t lda, int64_t strideA, int row_major,
+                          int64_t* ipiv, int64_t stride_ipiv, int pivot, int64_t* info)
+{
+    CFactorArgs<R> a;
+    a.A = reinterpret_cast<Cx<R>*>(A); a.ipiv = ipiv; a.info = info;
+    a.lda = lda; a.strideA = strideA; a.stride_ipiv = stride_ipiv; a.batch = batch;
+    a.m = (int)m; a.n = (int)n; a.row_major = row_major; a.pivot = pivot;
+    a.g = cbatched_geo(m, n, sizeof(Cx<R>), false);
+    const int groups = CBT / a.g.tpm;
+    const size_t lds = (size_t)groups * a.g.group_bytes;
+    RFLU_TRY(cbatched_lds_attr(&h->cbatched_attr_set[0][sizeof(R) == 4], &cgetrf_batched_kernel<R>, lds));
+    const int64_t wgs = (batch + groups - 1) / groups;
+    ProfScope ps(h, RFLU_K_PANEL, 4.0 * (double)batch * (double)m * (double)n * (double)std::min(m, n),
+                 2.0 * (double)batch * (double)m * (double)n * sizeof(Cx<R>));
+    hipLaunchKernelGGL((cgetrf_batched_kernel<R>), dim3((unsigned)wgs), dim3(CBT), lds, h->stream, a);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+template <typename R>
+int launch_cgetrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const R* F, int64_t lda, int64_t strideF, int row_major,
+                          const int64_t* ipiv, int64_t stride_ipiv, R* B, int64_t ldb, int64_t strideB, int trans)
+{
+    CSolveArgs<R> a;
+    a.F = reinterpret_cast<const Cx<R>*>(F); a.ipiv = ipiv; a.B = reinterpret_cast<Cx<R>*>(B);
+    a.lda = lda; a.strideF = strideF; a.stride_ipiv = stride_ipiv; a.ldb = ldb; a.strideB = strideB; a.batch = batch; a.nrhs = nrhs;
+    a.n = (int)n; a.row_major = row_major; a.trans = trans;
+    a.g = cbatched_geo(n, n, sizeof(Cx<R>), true);
+    const int groups = CBT / a.g.tpm;
+    const size_t lds = (size_t)groups * a.g.group_bytes;
+    RFLU_TRY(cbatched_lds_attr(&h->cbatched_attr_set[1][sizeof(R) == 4], &cgetrs_batched_kernel<R>, lds));
+    const int64_t wgs = (batch + groups - 1) / groups;
+    ProfScope ps(h, RFLU_K_TRSM, 8.0 * (double)batch * (double)n * (double)n * (double)nrhs,
+                 (double)batch * ((double)n * (double)n + 2.0 * (double)n * (double)nrhs) * sizeof(Cx<R>));
+    hipLaunchKernelGGL((cgetrs_batched_kernel<R>), dim3((unsigned)wgs), dim3(CBT), lds, h->stream, a);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+template bool cbatched_fits<double>(int64_t, int64_t);
+template bool cbatched_fits<float>(int64_t, int64_t);
+template int launch_cgetrf_batched<double>(Handle*, int64_t, int64_t, int64_t, double*, int64_t, int64_t, int, int64_t*, int64_t, int, int64_t*);
+template int launch_cgetrf_batched<float>(Handle*, int64_t, int64_t, int64_t, float*, int64_t, int64_t, int, int64_t*, int64_t, int, int64_t*);
+template int launch_cgetrs_batched<double>(Handle*, int64_t, int64_t, int64_t, const double*, int64_t, int64_t, int, const int64_t*, int64_t,
+                                           double*, int64_t, int64_t, int);
+template int launch_cgetrs_batched<float>(Handle*, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, int, const int64_t*, int64_t,
+                                          float*, int64_t, int64_t, int);
+
+}  // namespace rflu

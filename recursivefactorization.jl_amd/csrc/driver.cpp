@@ -439,6 +439,97 @@ static int getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, cons
     return RFLU_OK;
 }
 
+// ---- complex batched entries (include/rflu.h; kernels: batched_complex.hip).  The argument rules of the real
+// entries above, lda / ldb / strides in complex elements.  Above the one-launch limit: column-major batches loop over the single-matrix
+// complex device path; row-major ones are refused, because that path is column-major only.
+template <typename R>
+static int cgetrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, R* A, int64_t lda, int64_t strideA, int row_major,
+                          int64_t* ipiv, int64_t stride_ipiv, int pivot, int64_t* info_dev)
+{
+    if (batch < 0 || m < 0 || n < 0) {
+        set_error("complex getrf_batched: negative size batch=%lld m=%lld n=%lld", (long long)batch, (long long)m, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0 || m == 0 || n == 0) return RFLU_OK;
+    const int64_t mn = std::min(m, n), rows = row_major ? n : m, cols = row_major ? m : n;   // rows = the contiguous dimension
+    if (A == nullptr || info_dev == nullptr) { set_error("complex getrf_batched: null matrix or info pointer"); return RFLU_ERR_ARG; }
+    if (pivot && ipiv == nullptr) { set_error("complex getrf_batched: pivot != 0 needs an ipiv buffer"); return RFLU_ERR_ARG; }
+    if (lda < rows || (batch > 1 && strideA < (cols - 1) * lda + rows)) {
+        set_error("complex getrf_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", (long long)lda, (long long)strideA,
+                  (long long)m, (long long)n, row_major ? "row-major" : "column-major");
+        return RFLU_ERR_ARG;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < mn) {
+        set_error("complex getrf_batched: stride_ipiv=%lld < min(m, n)", (long long)stride_ipiv);
+        return RFLU_ERR_ARG;
+    }
+    if (cbatched_fits<R>(m, n)) {
+        RFLU_TRY(launch_cgetrf_batched<R>(h, batch, m, n, A, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info_dev));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        h->last_path = RFLU_PATH_HIP_BATCHED;
+        return RFLU_OK;
+    }
+    if (row_major) {
+        set_error("complex getrf_batched: row-major matrices larger than %d x %d are not served (the single-matrix complex path that "
+                  "larger batches loop over is column-major only)", sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32,
+                  sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32);
+        return RFLU_ERR_ARG;
+    }
+    std::vector<int64_t> infos((size_t)batch, 0);
+    for (int64_t b = 0; b < batch; ++b)
+        RFLU_TRY(cgetrf_cm_dev<R>(h, m, n, A + 2 * b * strideA, lda, ipiv ? ipiv + b * stride_ipiv : nullptr, pivot, &infos[(size_t)b]));
+    RFLU_HIP(hipMemcpyAsync(info_dev, infos.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+template <typename R>
+static int cgetrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const R* F, int64_t lda, int64_t strideF, int row_major,
+                          const int64_t* ipiv, int64_t stride_ipiv, R* B, int64_t ldb, int64_t strideB, int trans)
+{
+    if (batch < 0 || n < 0 || nrhs < 0) {
+        set_error("complex getrs_batched: negative size batch=%lld n=%lld nrhs=%lld", (long long)batch, (long long)n, (long long)nrhs);
+        return RFLU_ERR_ARG;
+    }
+    if (trans < 0 || trans > 2) {
+        set_error("complex getrs_batched: trans must be 0 (A), 1 (transpose) or 2 (adjoint), got %d", trans);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0 || n == 0 || nrhs == 0) return RFLU_OK;
+    if (F == nullptr || B == nullptr) { set_error("complex getrs_batched: null pointer"); return RFLU_ERR_ARG; }
+    const int64_t brows = row_major ? nrhs : n, bcols = row_major ? n : nrhs;   // brows = the contiguous dimension of B
+    if (lda < n || ldb < brows || (batch > 1 && (strideF < (n - 1) * lda + n || strideB < (bcols - 1) * ldb + brows))) {
+        set_error("complex getrs_batched: lda=%lld strideF=%lld ldb=%lld strideB=%lld too small for n=%lld nrhs=%lld (%s)", (long long)lda,
+                  (long long)strideF, (long long)ldb, (long long)strideB, (long long)n, (long long)nrhs, row_major ? "row-major" : "column-major");
+        return RFLU_ERR_ARG;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < n) {
+        set_error("complex getrs_batched: stride_ipiv=%lld < n", (long long)stride_ipiv);
+        return RFLU_ERR_ARG;
+    }
+    if (cbatched_fits<R>(n, n)) {
+        RFLU_TRY(launch_cgetrs_batched<R>(h, batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb, strideB, trans));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        h->last_path = RFLU_PATH_HIP_BATCHED;
+        return RFLU_OK;
+    }
+    if (row_major) {
+        set_error("complex getrs_batched: row-major matrices larger than %d x %d are not served (the single-matrix complex path that "
+                  "larger batches loop over is column-major only)", sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32,
+                  sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32);
+        return RFLU_ERR_ARG;
+    }
+    for (int64_t b = 0; b < batch; ++b) {
+        const R* Fb = F + 2 * b * strideF;
+        const int64_t* ip = ipiv ? ipiv + b * stride_ipiv : nullptr;
+        R* Bb = B + 2 * b * strideB;
+        if (trans) RFLU_TRY(cgetrs_trans_cm_dev<R>(h, n, nrhs, Fb, lda, ip, Bb, ldb, trans == 2 ? 1 : 0));
+        else RFLU_TRY(cgetrs_cm_dev<R>(h, n, nrhs, Fb, lda, ip, Bb, ldb));
+    }
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 // ---- inv / det / logabsdet from the factors (include/rflu.h; kernels and the two sweeps: inverse.hip) ----------
 template <typename T>
 static int logabsdet_dev(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign)
@@ -700,7 +791,7 @@ static Handle* H(rflu_handle_t h) { return reinterpret_cast<Handle*>(h); }
 
 extern "C" {
 
-int rflu_version(void) { return 104; }
+int rflu_version(void) { return 105; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -1162,6 +1253,21 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
         return cgemm_public<R>(H(handle), M, N, K, A, lda, B, ldb, C, ldc);                                           \
+    }                                                                                                                 \
+    int rflu_getrf_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t m, int64_t n, R* A, int64_t lda,  \
+                                       int64_t strideA, int row_major, int64_t* ipiv, int64_t stride_ipiv, int pivot,  \
+                                       int64_t* info_dev)                                                              \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetrf_batched<R>(H(handle), batch, m, n, A, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info_dev); \
+    }                                                                                                                 \
+    int rflu_getrs_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, int64_t nrhs, const R* F,      \
+                                       int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,              \
+                                       int64_t stride_ipiv, R* B, int64_t ldb, int64_t strideB, int trans)            \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetrs_batched<R>(H(handle), batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb,    \
+                                 strideB, trans);                                                                     \
     }
 DEFINE_COMPLEX(cf64, double)
 DEFINE_COMPLEX(cf32, float)

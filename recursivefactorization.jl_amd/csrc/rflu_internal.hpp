@@ -243,6 +243,7 @@ struct Handle {
     bool eng_attr_set[2] = {false, false};    // same for the persistent update engine (engine.hip)
     bool batched_attr_set[2][2] = {};         // same for the batched kernels (batched.hip): [factorization|solve][Float64|Float32]
     bool batched_inv_attr_set[2] = {};        // ... and the batched inverse: [Float64|Float32]
+    bool cbatched_attr_set[2][2] = {};        // ... and the complex batched kernels (batched_complex.hip): [factorization|solve][ComplexF64|ComplexF32]
     void* eng_state = nullptr;                // device: EngState (engine.hpp)
     void* eng_host = nullptr;                 // pinned host image of its initial value
     long long* eng_trace_buf = nullptr;       // device: RFLU_ENGINE_TRACE stamps + workgroup-time accounting (measurement only)
@@ -413,6 +414,8 @@ int launch_butterfly_vec(Handle* h, int64_t n, int64_t nrhs, T* X, int64_t ldx, 
 // load and the one store in LDS.  Matrix b at A + b*strideA, element (i, j) at [i + j*lda] or (row_major) [i*lda + j]; info: DEVICE
 // array of `batch` entries.  The solve: B in the orientation of F, any nrhs in passes of 8, trans = B <- A^-T B.
 constexpr int64_t BATCHED_MAX_DIM = 128;
+constexpr int64_t CBATCHED_MAX_DIM_CF32 = 128;   // batched_complex.hip, ComplexF32: the bytes of the Float64 real kernel
+constexpr int64_t CBATCHED_MAX_DIM_CF64 = 64;    // ComplexF64: 65 x 64 x 16 B = 66.5 KB per matrix, two groups and their right-hand sides per CU
 bool batched_fits(int64_t m, int64_t n);
 template <typename T>
 int launch_getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, int64_t lda, int64_t strideA, int row_major,
@@ -420,6 +423,17 @@ int launch_getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, i
 template <typename T>
 int launch_getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const T* F, int64_t lda, int64_t strideF, int row_major,
                          const int64_t* ipiv, int64_t stride_ipiv, T* B, int64_t ldb, int64_t strideB, int trans);
+
+// batched_complex.hip: the same two kernels for ComplexF64 / ComplexF32 (R = double / float behind interleaved (re, im) pairs; lda, ldb
+// and the strides in complex elements), max(m, n) <= CBATCHED_MAX_DIM_CF64 / _CF32.  trans: 0 = A, 1 = transpose(A), 2 = A'.
+template <typename R>
+bool cbatched_fits(int64_t m, int64_t n);
+template <typename R>
+int launch_cgetrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, R* A, int64_t lda, int64_t strideA, int row_major,
+                          int64_t* ipiv, int64_t stride_ipiv, int pivot, int64_t* info);
+template <typename R>
+int launch_cgetrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const R* F, int64_t lda, int64_t strideF, int row_major,
+                          const int64_t* ipiv, int64_t stride_ipiv, R* B, int64_t ldb, int64_t strideB, int trans);
 
 // the batched inverse: Ainv_b <- A_b^-1 from the factors, out of place, Ainv in the orientation of F; info[b] = first zero u_ii or 0
 template <typename T>

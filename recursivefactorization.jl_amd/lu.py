@@ -18,6 +18,9 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
                                                                                              keeps raising ``TypeError`` on complex input)
     ldiv!(F', B) / ldiv!(transpose(F), B) for complex factors                               -> ``ldiv_complex_adjoint_`` /
                                                                                              ``ldiv_complex_transpose_``
+    (no counterpart: many small complex systems at once)                                    -> ``lu_complex_batched_`` /
+                                                                                             ``lu_complex_batched`` /
+                                                                                             ``ldiv_complex_batched_``
     inv / inv!, det, logabsdet, logdet on the LU object (stdlib LinearAlgebra)            -> ``inv`` / ``inv_`` / ``det`` / ``logabsdet`` /
                                                                                              ``logdet``; batched: ``inv_batched`` /
                                                                                              ``logabsdet_batched`` / ``det_batched``
@@ -801,6 +804,14 @@ def _batched_layout(A, what: str):
     return row_major, ld, (s0 if b > 1 else max(span, 1))
 
 
+def _batched_sfx(dtype, what: str) -> str:
+    """``_sfx`` for the real batched functions: a complex batch is pointed at the functions that serve it."""
+    if str(dtype).replace("torch.", "") in ("complex128", "complex64"):
+        raise TypeError(f"{what} serves Float64/Float32 only (got {dtype}); ComplexF64/ComplexF32 batches go to lu_complex_batched_ / "
+                        "lu_complex_batched / ldiv_complex_batched_")
+    return _sfx(dtype)
+
+
 def _check_batched_info(info_t, piv: bool):
     bad = (info_t != 0).nonzero()
     if bad.numel():
@@ -808,28 +819,22 @@ def _check_batched_info(info_t, piv: bool):
         raise SingularException(abs(int(info_t[i].item())), i)
 
 
-def lu_batched_(A, ipiv=None, pivot=True, *, check=True, handle=None) -> BatchedLU:
-    """``lu!`` on every matrix of a batch at once: ``A`` is a 3-D CUDA tensor (batch, m, n) whose matrices are dense column-major
-    (``stride(1) == 1``, e.g. a C-contiguous (batch, n, m) tensor seen through ``.transpose(1, 2)``) or row-major (``stride(2) == 1``),
-    at any batch stride that keeps them apart; factored in place by ``rflu_getrf_batched_*_dev``.  Up to 128 rows and columns the whole
-    batch is ONE kernel launch (``last_path() == "hip-batched"``); larger matrices are looped over the single-matrix path.
-
-    ``ipiv``: None -> allocated, (batch, min(m, n)) int64 (``NotIPIV`` for NoPivot); or a CUDA int64 tensor of that shape with unit
-    stride along a row -- with NoPivot it comes back filled with the identity (src/lu.jl:111-113).  ``check=True`` copies ``info``
-    back and raises ``SingularException`` with the first failing matrix's ``info`` and its index in ``batch_index``."""
+def _lu_batched_call(A, ipiv, pivot, check, handle, what: str, sfx_of) -> BatchedLU:
+    """The checks and the call shared by ``lu_batched_`` and ``lu_complex_batched_``; ``sfx_of`` maps the dtype to the entry's suffix
+    or raises ``TypeError``.  Every check comes before the library is touched."""
     piv = normalize_pivot(pivot)
     if not _is_torch(A):
-        raise TypeError("lu_batched_ works on CUDA torch tensors (the batch lives in HBM)")
+        raise TypeError(f"{what} works on CUDA torch tensors (the batch lives in HBM)")
     if A.ndim != 3:
-        raise ValueError("lu_batched_ needs a 3-D tensor (batch, m, n)")
+        raise ValueError(f"{what} needs a 3-D tensor (batch, m, n)")
     import torch
 
     if not A.is_cuda:
-        raise TypeError("lu_batched_: the batch must live on the MI355X (device='cuda')")
-    sfx = _sfx(A.dtype)
+        raise TypeError(f"{what}: the batch must live on the MI355X (device='cuda')")
+    sfx = sfx_of(A.dtype, what)
     batch, m, n = (int(x) for x in A.shape)
     mn = min(m, n)
-    row_major, ld, stride_a = _batched_layout(A, "lu_batched_")
+    row_major, ld, stride_a = _batched_layout(A, what)
     if ipiv is None:
         ipiv_t = torch.empty((batch, mn), dtype=torch.int64, device=A.device) if piv else None
     else:
@@ -854,14 +859,70 @@ def lu_batched_(A, ipiv=None, pivot=True, *, check=True, handle=None) -> Batched
     return BatchedLU(A, ipiv_t if ipiv_t is not None else NotIPIV(mn), info_t)
 
 
+def _batched_copy(A, what: str):
+    """A copy of a batch that keeps the layout of its matrices (``lu_batched`` / ``lu_complex_batched``)."""
+    if not _is_torch(A) or A.ndim != 3:
+        raise ValueError(f"{what} needs a 3-D CUDA tensor (batch, m, n)")
+    C = A.transpose(1, 2).contiguous().transpose(1, 2) if (A.stride(1) == 1 and A.shape[2] > 1) else A.contiguous()
+    return C.clone() if C.data_ptr() == A.data_ptr() else C
+
+
+def _ldiv_batched_call(F, B, trans: int, check, handle, what: str, made_by: str, sfx_of):
+    """The checks and the call shared by ``ldiv_batched_`` and ``ldiv_complex_batched_``; ``trans`` is the C entry's value."""
+    if not isinstance(F, BatchedLU):
+        raise TypeError(f"{what} needs the BatchedLU that {made_by} returned")
+    A = F.factors
+    import torch
+
+    batch, m, n = (int(x) for x in A.shape)
+    if m != n:
+        raise ValueError("ldiv! needs square factorizations")
+    if not (_is_torch(B) and B.is_cuda and B.dtype == A.dtype):
+        raise TypeError("B must be a CUDA tensor of the factorization's dtype")
+    if B.ndim not in (2, 3) or B.shape[0] != batch or B.shape[1] != n:
+        raise ValueError(f"B must have shape (batch, n) or (batch, n, nrhs) with batch = {batch}, n = {n}")
+    row_major, ld, stride_f = _batched_layout(A, what)
+    nrhs = 1 if B.ndim == 2 else int(B.shape[2])
+    if B.ndim == 2:
+        if n > 1 and B.stride(1) != 1 or batch > 1 and B.stride(0) < n:
+            raise ValueError("a batch of vectors must have unit stride along a vector and a batch stride of at least n")
+        ldb, stride_b = (n if not row_major else 1), (int(B.stride(0)) if batch > 1 else max(n, 1))
+    else:
+        b_rm, ldb, stride_b = _batched_layout(B, f"{what} (B)")
+        if b_rm != row_major and n > 1 and nrhs > 1:
+            raise ValueError("B must have the orientation of the factors (column-major with column-major, row-major with row-major)")
+        if b_rm != row_major:   # a single row or column fits both readings: take the factors'
+            ldb = max(nrhs, 1) if row_major else max(n, 1)
+    nopiv = isinstance(F.ipiv, NotIPIV)
+    if not nopiv and not (_is_torch(F.ipiv) and F.ipiv.is_cuda and F.ipiv.dtype == torch.int64):
+        raise TypeError("ipiv of a batch must be an int64 CUDA tensor (or NotIPIV)")
+    if _as_bool(check):
+        _check_batched_info(F.info, True)
+    if batch > 0 and n > 0 and nrhs > 0:
+        sfx = sfx_of(A.dtype, what)
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        stride_ip = 0 if nopiv else (int(F.ipiv.stride(0)) if batch > 1 else max(n, 1))
+        h.call(f"rflu_getrs_batched_{sfx}_dev", batch, n, nrhs, ctypes.c_void_p(A.data_ptr()), ld, stride_f, row_major,
+               ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), stride_ip, ctypes.c_void_p(B.data_ptr()), ldb, stride_b, trans)
+    return B
+
+
+def lu_batched_(A, ipiv=None, pivot=True, *, check=True, handle=None) -> BatchedLU:
+    """``lu!`` on every matrix of a batch at once: ``A`` is a 3-D CUDA tensor (batch, m, n) whose matrices are dense column-major
+    (``stride(1) == 1``, e.g. a C-contiguous (batch, n, m) tensor seen through ``.transpose(1, 2)``) or row-major (``stride(2) == 1``),
+    at any batch stride that keeps them apart; factored in place by ``rflu_getrf_batched_*_dev``.  Up to 128 rows and columns the whole
+    batch is ONE kernel launch (``last_path() == "hip-batched"``); larger matrices are looped over the single-matrix path.
+
+    ``ipiv``: None -> allocated, (batch, min(m, n)) int64 (``NotIPIV`` for NoPivot); or a CUDA int64 tensor of that shape with unit
+    stride along a row -- with NoPivot it comes back filled with the identity (src/lu.jl:111-113).  ``check=True`` copies ``info``
+    back and raises ``SingularException`` with the first failing matrix's ``info`` and its index in ``batch_index``."""
+    return _lu_batched_call(A, ipiv, pivot, check, handle, "lu_batched_", _batched_sfx)
+
+
 def lu_batched(A, pivot=True, **kwargs) -> BatchedLU:
     """``lu`` on every matrix of a batch: ``lu_batched_`` on a copy that keeps the layout of ``A``'s matrices."""
-    if not _is_torch(A) or A.ndim != 3:
-        raise ValueError("lu_batched needs a 3-D CUDA tensor (batch, m, n)")
-    C = A.transpose(1, 2).contiguous().transpose(1, 2) if (A.stride(1) == 1 and A.shape[2] > 1) else A.contiguous()
-    if C.data_ptr() == A.data_ptr():
-        C = C.clone()
-    return lu_batched_(C, None, pivot, **kwargs)
+    return lu_batched_(_batched_copy(A, "lu_batched"), None, pivot, **kwargs)
 
 
 def ldiv_batched_(F, B, *, trans=False, check=True, handle=None):
@@ -873,41 +934,7 @@ def ldiv_batched_(F, B, *, trans=False, check=True, handle=None):
         F, trans = F.parent, not trans
         if isinstance(F, Adjoint):
             raise TypeError("ldiv! of a doubly wrapped factorization: unwrap it first")
-    if not isinstance(F, BatchedLU):
-        raise TypeError("ldiv_batched_ needs the BatchedLU that lu_batched_ returned")
-    A = F.factors
-    import torch
-
-    batch, m, n = (int(x) for x in A.shape)
-    if m != n:
-        raise ValueError("ldiv! needs square factorizations")
-    if not (_is_torch(B) and B.is_cuda and B.dtype == A.dtype):
-        raise TypeError("B must be a CUDA tensor of the factorization's dtype")
-    if B.ndim not in (2, 3) or B.shape[0] != batch or B.shape[1] != n:
-        raise ValueError(f"B must have shape (batch, n) or (batch, n, nrhs) with batch = {batch}, n = {n}")
-    row_major, ld, stride_f = _batched_layout(A, "ldiv_batched_")
-    nrhs = 1 if B.ndim == 2 else int(B.shape[2])
-    if B.ndim == 2:
-        if n > 1 and B.stride(1) != 1 or batch > 1 and B.stride(0) < n:
-            raise ValueError("a batch of vectors must have unit stride along a vector and a batch stride of at least n")
-        ldb, stride_b = (n if not row_major else 1), (int(B.stride(0)) if batch > 1 else max(n, 1))
-    else:
-        b_rm, ldb, stride_b = _batched_layout(B, "ldiv_batched_ (B)")
-        if b_rm != row_major and n > 1 and nrhs > 1:
-            raise ValueError("B must have the orientation of the factors (column-major with column-major, row-major with row-major)")
-        if b_rm != row_major:   # a single row or column fits both readings: take the factors'
-            ldb = max(nrhs, 1) if row_major else max(n, 1)
-    if _as_bool(check):
-        _check_batched_info(F.info, True)
-    if batch > 0 and n > 0 and nrhs > 0:
-        sfx = _sfx(A.dtype)
-        h = handle or _ffi.default_handle(A.device.index or 0)
-        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
-        nopiv = isinstance(F.ipiv, NotIPIV)
-        stride_ip = 0 if nopiv else (int(F.ipiv.stride(0)) if batch > 1 else max(n, 1))
-        h.call(f"rflu_getrs_batched_{sfx}_dev", batch, n, nrhs, ctypes.c_void_p(A.data_ptr()), ld, stride_f, row_major,
-               ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), stride_ip, ctypes.c_void_p(B.data_ptr()), ldb, stride_b, int(bool(trans)))
-    return B
+    return _ldiv_batched_call(F, B, int(bool(trans)), check, handle, "ldiv_batched_", "lu_batched_", _batched_sfx)
 
 
 def _batched_square(F, what: str):
@@ -978,6 +1005,55 @@ def det_batched(F, *, handle=None):
 
     la, sg = logabsdet_batched(F, handle=handle)
     return torch.where(sg == 0, torch.zeros_like(sg), sg * torch.exp(la))
+
+
+def _cbatched_sfx(dtype, what: str) -> str:
+    name = str(dtype).replace("torch.", "")
+    if name == "complex128":
+        return "cf64"
+    if name == "complex64":
+        return "cf32"
+    raise TypeError(f"{what} serves ComplexF64/ComplexF32 only (got {dtype}); real batches go to lu_batched_ / ldiv_batched_")
+
+
+def lu_complex_batched_(A, ipiv=None, pivot=True, *, check=True, handle=None) -> BatchedLU:
+    """``lu!`` on every matrix of a ``complex128`` / ``complex64`` batch at once: ``lu_batched_`` for complex elements, served by
+    ``rflu_getrf_batched_cf64_dev`` / ``_cf32_dev``.  ``A``: a 3-D CUDA tensor (batch, m, n) whose matrices are dense column-major
+    (``stride(1) == 1``) or row-major (``stride(2) == 1``) at any batch stride that keeps them apart; factored in place.  Per matrix the
+    rule of ``lu_complex_``: the pivot is the row of largest modulus ``abs(z)`` (strict ``>``, the lowest row on ties), not LAPACK's
+    ``|re| + |im|``.  Up to 128 (``complex64``) / 64 (``complex128``) rows and columns the whole batch is ONE kernel launch
+    (``last_path() == "hip-batched"``); larger column-major matrices are looped over the single-matrix complex path, larger row-major
+    ones are refused by the library (that path is column-major only).
+
+    ``ipiv``, ``check`` -> ``SingularException`` with ``batch_index``, the NoPivot sign of ``info`` and the returned ``BatchedLU`` are
+    those of ``lu_batched_``."""
+    return _lu_batched_call(A, ipiv, pivot, check, handle, "lu_complex_batched_", _cbatched_sfx)
+
+
+def lu_complex_batched(A, pivot=True, **kwargs) -> BatchedLU:
+    """``lu`` on every matrix of a complex batch: ``lu_complex_batched_`` on a copy that keeps the layout of ``A``'s matrices."""
+    return lu_complex_batched_(_batched_copy(A, "lu_complex_batched"), None, pivot, **kwargs)
+
+
+_CBATCHED_TRANS = {"N": 0, "T": 1, "C": 2}
+
+
+def ldiv_complex_batched_(F, B, *, trans="N", check=True, handle=None):
+    """``ldiv!`` on every system of a complex batch: overwrite ``B`` -- (batch, n) or (batch, n, nrhs), in the orientation of the
+    factors -- with ``A_b \\ B_b`` (``trans="N"``), ``transpose(A_b) \\ B_b`` (``"T"``) or ``A_b' \\ B_b`` (``"C"``, the conjugate
+    transpose); LAPACK's letters, because for complex matrices the last two differ and a flag could not say which is meant.
+    ``Adjoint(F)`` means ``"C"`` (and takes no ``trans`` besides the default); a doubly wrapped factorization is refused.  Served by
+    ``rflu_getrs_batched_cf64_dev`` / ``_cf32_dev``.  ``check`` as in ``ldiv_batched_``."""
+    if not isinstance(trans, str) or trans not in _CBATCHED_TRANS:
+        raise ValueError(f'trans must be "N", "T" or "C", got {trans!r}')
+    if isinstance(F, Adjoint):
+        F = F.parent
+        if isinstance(F, Adjoint):
+            raise TypeError("ldiv! of a doubly wrapped factorization: unwrap it first")
+        if trans != "N":
+            raise ValueError('Adjoint(F) already means trans="C": pass the plain BatchedLU together with trans')
+        trans = "C"
+    return _ldiv_batched_call(F, B, _CBATCHED_TRANS[trans], check, handle, "ldiv_complex_batched_", "lu_complex_batched_", _cbatched_sfx)
 
 
 def last_path(device: int = 0) -> str:
