@@ -16,13 +16,13 @@ SOURCES = ["gemm.hip", "engine.hip", "panel.hip", "panel_f32.hip", "panel_local.
 if EXPERIMENTS:
     SOURCES += ["panel_blocked.hip", "panel_blocked_f32.hip"]
 HEADERS = ["rflu_internal.hpp", os.path.join("..", "..", "include", "rflu.h")]   # included by every source
-ALL_HEADERS = HEADERS + ["panel_common.hpp", "panel_xchg.hpp", "trsm_row.hpp", "gemm_tile.hpp", "laswp_strip.hpp", "engine.hpp", "schedule_plan.hpp", "driver.hpp", "host_wayback.hpp", "complex.hpp", "complex_dev.hpp"]
+ALL_HEADERS = HEADERS + ["panel_common.hpp", "panel_xchg.hpp", "trsm_row.hpp", "gemm_tile.hpp", "laswp_strip.hpp", "engine.hpp", "schedule_plan.hpp", "driver.hpp", "host_wayback.hpp", "complex.hpp", "complex_dev.hpp", "batched_kernels.hpp"]
 _PANEL_H = ["panel_common.hpp", "panel_xchg.hpp", "trsm_row.hpp"]
 EXTRA_DEPS = {"gemm.hip": ["gemm_tile.hpp"], "engine.hip": ["gemm_tile.hpp", "laswp_strip.hpp", "engine.hpp"], "driver.cpp": ["schedule_plan.hpp", "driver.hpp", "complex.hpp"],
               "streams.cpp": ["schedule_plan.hpp", "driver.hpp"], "schedule.cpp": ["engine.hpp", "schedule_plan.hpp", "driver.hpp"], "mgpu.cpp": ["schedule_plan.hpp", "driver.hpp"],
               "host_entry.cpp": ["engine.hpp", "schedule_plan.hpp", "driver.hpp", "host_wayback.hpp", "complex.hpp"],
               "complex_gemm.hip": ["gemm_tile.hpp", "complex.hpp"], "complex.hip": ["complex.hpp", "complex_dev.hpp"], "complex_solve.hip": ["complex.hpp", "complex_dev.hpp"],
-              "batched_complex.hip": ["complex.hpp", "complex_dev.hpp"],
+              "batched.hip": ["batched_kernels.hpp"], "batched_complex.hip": ["complex.hpp", "complex_dev.hpp", "batched_kernels.hpp"],
               "laswp.hip": ["laswp_strip.hpp", "trsm_row.hpp"], "trsm.hip": ["trsm_row.hpp"], "trsv.hip": ["trsm_row.hpp"],
               "panel.hip": _PANEL_H, "panel_local.hip": _PANEL_H, "panel_single.hip": _PANEL_H, "panel_blocked.hip": _PANEL_H,
               "panel_f32.hip": ["panel.hip", *_PANEL_H], "panel_local_f32.hip": ["panel_local.hip", *_PANEL_H],

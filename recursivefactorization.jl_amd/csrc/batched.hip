@@ -19,53 +19,14 @@
 // the group's first wave while the factors arrive), then two column-oriented substitutions with one barrier per column; the
 // transposed solve reads the same LDS image by rows (U^T forward, L^T backward) and scatters through the permutation.
 // Roofline: n dependent steps of {barrier, pivot search, LDS rank-1 update}; only for n <= 16 the one load and one store matter.
-#include <algorithm>
-
-#include "rflu_internal.hpp"
+// Geometry, the DPP maximum and the launch are shared with batched_complex.hip: batched_kernels.hpp.
+#include "batched_kernels.hpp"
 
 namespace rflu {
 
+using namespace batched;
+
 namespace {
-
-typedef unsigned long long bu64;
-constexpr int BT = 256;                   // threads per workgroup
-constexpr int BNR = 8;                    // right-hand sides per pass of the solve
-constexpr unsigned BPOS_NONE = 0x7fffffffu;
-
-struct BGeo {
-    int tpm;        // threads per matrix (64 | 128 | 256)
-    int tpm_log;
-    int rt_log;     // log2 of RT = rows of the (row, column-slice) thread grid: the smallest power of two >= m
-    int ct_log;     // log2 of the same for the columns (row-major loads and stores: lanes along a row)
-    int ld;         // LDS leading dimension (odd)
-    unsigned group_bytes;
-    unsigned off_x, off_int;   // byte offsets inside a group's LDS: right-hand sides (solve), integer arrays
-};
-
-int blog2_ceil(int64_t v)
-{
-    int l = 0;
-    while (((int64_t)1 << l) < v) ++l;
-    return l;
-}
-
-BGeo batched_geo(int64_t m, int64_t n, size_t esize, bool solve)
-{
-    BGeo g;
-    const int64_t mx = std::max(m, n);
-    g.tpm_log = mx <= 32 ? 6 : (mx <= 64 ? 7 : 8);
-    g.tpm = 1 << g.tpm_log;
-    g.rt_log = blog2_ceil(m);
-    g.ct_log = blog2_ceil(n);
-    g.ld = (int)(m | 1);
-    size_t off = ((size_t)g.ld * (size_t)n * esize + 15) & ~(size_t)15;
-    g.off_x = (unsigned)off;
-    if (solve) off += ((size_t)g.ld * BNR * esize + 15) & ~(size_t)15;
-    g.off_int = (unsigned)off;
-    off += ((size_t)(m + std::min(m, n)) * sizeof(int) + 15) & ~(size_t)15;
-    g.group_bytes = (unsigned)off;
-    return g;
-}
 
 // |v| as an integer that orders like the magnitude; 0 for zeros and NaN (neither ever beats a candidate: `absi > amax`, lu.jl:301)
 __device__ __forceinline__ bu64 bkey(double v)
@@ -75,29 +36,6 @@ __device__ __forceinline__ bu64 bkey(double v)
 __device__ __forceinline__ bu64 bkey(float v)
 {
     return (__builtin_fabsf(v) > 0.0f) ? (bu64)(__float_as_uint(v) & 0x7fffffffu) : 0ull;
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ bu64 bdpp_max(bu64 v)
-{
-    const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-    const int olo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    const int ohi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    const bu64 o = ((bu64)(unsigned)ohi << 32) | (bu64)(unsigned)olo;
-    return o > v ? o : v;
-}
-// maximum over the 64 lanes of a wave (all of them active), wave-uniform: the DPP ladder of panel_single.hip on 64-bit keys
-__device__ __forceinline__ bu64 bwave_max(bu64 v)
-{
-    v = bdpp_max<0xB1, 0xf>(v);    // quad_perm:[1,0,3,2]
-    v = bdpp_max<0x4E, 0xf>(v);    // quad_perm:[2,3,0,1]
-    v = bdpp_max<0x141, 0xf>(v);   // row_half_mirror
-    v = bdpp_max<0x140, 0xf>(v);   // row_mirror
-    v = bdpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v = bdpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds the maximum
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-    return ((bu64)hi << 32) | (bu64)lo;
 }
 
 // ---- the one load and the one store ---------------------------------------------------------------------------------------------
@@ -140,7 +78,7 @@ __global__ void __launch_bounds__(BT) getrf_batched_kernel(BFactorArgs<T> a)
     const bool valid = b < a.batch;
     unsigned char* base = bsmem + (size_t)grp * g.group_bytes;
     T* s = reinterpret_cast<T*>(base);
-    unsigned* spiv = reinterpret_cast<unsigned*>(base + g.off_int);   // [mn] position the pivot of step k came from
+    unsigned* spiv = reinterpret_cast<unsigned*>(base + g.off_a);   // [mn] position the pivot of step k came from
     unsigned* spos = spiv + mn;                                        // [m]  final position of every row
     T* G = a.A + (valid ? b : 0) * a.strideA;
 
@@ -307,7 +245,7 @@ __global__ void __launch_bounds__(BT) getrs_batched_kernel(BSolveArgs<T> a)
     unsigned char* base = bsmem + (size_t)grp * g.group_bytes;
     T* s = reinterpret_cast<T*>(base);
     T* x = reinterpret_cast<T*>(base + g.off_x);
-    int* sperm = reinterpret_cast<int*>(base + g.off_int);   // [n]: row i of P*B is row sperm[i] of B
+    int* sperm = reinterpret_cast<int*>(base + g.off_a);   // [n]: row i of P*B is row sperm[i] of B
     const int64_t bb = valid ? b : 0;
     const T* F = a.F + bb * a.strideF;
     T* B = a.B + bb * a.strideB;
@@ -398,7 +336,7 @@ __global__ void __launch_bounds__(BT) getri_batched_kernel(BInvArgs<T> a)
     unsigned char* base = bsmem + (size_t)grp * g.group_bytes;
     T* s = reinterpret_cast<T*>(base);
     T* x = reinterpret_cast<T*>(base + g.off_x);
-    int* sperm = reinterpret_cast<int*>(base + g.off_int);   // [n]: row i of P*I is row sperm[i] of I
+    int* sperm = reinterpret_cast<int*>(base + g.off_a);   // [n]: row i of P*I is row sperm[i] of I
     const int64_t bb = valid ? b : 0;
     const T* F = a.F + bb * a.strideF;
     T* X = a.Ainv + bb * a.strideI;
@@ -455,16 +393,6 @@ __global__ void __launch_bounds__(BT) getri_batched_kernel(BInvArgs<T> a)
     }
 }
 
-template <typename K>
-int batched_lds_attr(bool* done, K kernel, size_t lds)
-{
-    if (lds > 64 * 1024 && !*done) {   // above the default limit a kernel has to ask once (160 KiB per CU on gfx950)
-        RFLU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        *done = true;
-    }
-    return RFLU_OK;
-}
-
 }  // namespace
 
 bool batched_fits(int64_t m, int64_t n) { return std::max(m, n) <= BATCHED_MAX_DIM; }
@@ -477,16 +405,9 @@ int launch_getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, i
     a.A = A; a.ipiv = ipiv; a.info = info;
     a.lda = lda; a.strideA = strideA; a.stride_ipiv = stride_ipiv; a.batch = batch;
     a.m = (int)m; a.n = (int)n; a.row_major = row_major; a.pivot = pivot;
-    a.g = batched_geo(m, n, sizeof(T), false);
-    const int groups = BT / a.g.tpm;
-    const size_t lds = (size_t)groups * a.g.group_bytes;
-    RFLU_TRY(batched_lds_attr(&h->batched_attr_set[0][sizeof(T) == 4], &getrf_batched_kernel<T>, lds));
-    const int64_t wgs = (batch + groups - 1) / groups;
-    ProfScope ps(h, RFLU_K_PANEL, (double)batch * (double)m * (double)n * (double)std::min(m, n),
-                 2.0 * (double)batch * (double)m * (double)n * sizeof(T));
-    hipLaunchKernelGGL((getrf_batched_kernel<T>), dim3((unsigned)wgs), dim3(BT), lds, h->stream, a);
-    RFLU_HIP(hipGetLastError());
-    return RFLU_OK;
+    a.g = batched_geo(m, n, sizeof(T), false, false);
+    return launch_batched(h, 0, sizeof(T) == 4, &getrf_batched_kernel<T>, a, batch, RFLU_K_PANEL, (double)batch * (double)m * (double)n * (double)std::min(m, n),
+                          2.0 * (double)batch * (double)m * (double)n * sizeof(T));
 }
 
 template <typename T>
@@ -497,16 +418,9 @@ int launch_getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, cons
     a.F = F; a.ipiv = ipiv; a.B = B;
     a.lda = lda; a.strideF = strideF; a.stride_ipiv = stride_ipiv; a.ldb = ldb; a.strideB = strideB; a.batch = batch; a.nrhs = nrhs;
     a.n = (int)n; a.row_major = row_major; a.trans = trans;
-    a.g = batched_geo(n, n, sizeof(T), true);
-    const int groups = BT / a.g.tpm;
-    const size_t lds = (size_t)groups * a.g.group_bytes;
-    RFLU_TRY(batched_lds_attr(&h->batched_attr_set[1][sizeof(T) == 4], &getrs_batched_kernel<T>, lds));
-    const int64_t wgs = (batch + groups - 1) / groups;
-    ProfScope ps(h, RFLU_K_TRSM, 2.0 * (double)batch * (double)n * (double)n * (double)nrhs,
-                 (double)batch * ((double)n * (double)n + 2.0 * (double)n * (double)nrhs) * sizeof(T));
-    hipLaunchKernelGGL((getrs_batched_kernel<T>), dim3((unsigned)wgs), dim3(BT), lds, h->stream, a);
-    RFLU_HIP(hipGetLastError());
-    return RFLU_OK;
+    a.g = batched_geo(n, n, sizeof(T), true, false);
+    return launch_batched(h, 1, sizeof(T) == 4, &getrs_batched_kernel<T>, a, batch, RFLU_K_TRSM, 2.0 * (double)batch * (double)n * (double)n * (double)nrhs,
+                          (double)batch * ((double)n * (double)n + 2.0 * (double)n * (double)nrhs) * sizeof(T));
 }
 
 template <typename T>
@@ -517,15 +431,9 @@ int launch_getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_
     a.F = F; a.ipiv = ipiv; a.Ainv = Ainv; a.info = info;
     a.lda = lda; a.strideF = strideF; a.stride_ipiv = stride_ipiv; a.ldi = ldi; a.strideI = strideI; a.batch = batch;
     a.n = (int)n; a.row_major = row_major;
-    a.g = batched_geo(n, n, sizeof(T), true);
-    const int groups = BT / a.g.tpm;
-    const size_t lds = (size_t)groups * a.g.group_bytes;
-    RFLU_TRY(batched_lds_attr(&h->batched_inv_attr_set[sizeof(T) == 4], &getri_batched_kernel<T>, lds));
-    const int64_t wgs = (batch + groups - 1) / groups;
-    ProfScope ps(h, RFLU_K_TRSM, 2.0 * (double)batch * (double)n * (double)n * (double)n, 2.0 * (double)batch * (double)n * (double)n * sizeof(T));
-    hipLaunchKernelGGL((getri_batched_kernel<T>), dim3((unsigned)wgs), dim3(BT), lds, h->stream, a);
-    RFLU_HIP(hipGetLastError());
-    return RFLU_OK;
+    a.g = batched_geo(n, n, sizeof(T), true, false);
+    return launch_batched(h, 2, sizeof(T) == 4, &getri_batched_kernel<T>, a, batch, RFLU_K_TRSM, 2.0 * (double)batch * (double)n * (double)n * (double)n,
+                          2.0 * (double)batch * (double)n * (double)n * sizeof(T));
 }
 
 template int launch_getri_batched<double>(Handle*, int64_t, int64_t, const double*, int64_t, int64_t, int, const int64_t*, int64_t, double*,

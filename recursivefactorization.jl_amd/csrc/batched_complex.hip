@@ -33,20 +33,15 @@
 // a complex division per right-hand side and thread would cost more than the whole rank-1 step it feeds, and the extra rounding
 // (a few eps per element) is far inside the 20 n eps backward-error bar of the tests.  A zero on the diagonal gives Inf / NaN in that
 // matrix's own right-hand sides only.
-// (The DPP maximum and the thread geometry are restated here: batched.hip is the real-only file and includes nothing but
-// rflu_internal.hpp.)
-#include <algorithm>
-
+// Geometry, the DPP maximum and the launch are shared with batched.hip: batched_kernels.hpp.
 #include "complex_dev.hpp"
+#include "batched_kernels.hpp"
 
 namespace rflu {
 
-namespace {
+using namespace batched;
 
-typedef unsigned long long cu64;
-constexpr int CBT = 256;                   // threads per workgroup
-constexpr int CBNR = 8;                    // right-hand sides per pass of the solve
-constexpr unsigned CPOS_NONE = 0x7fffffffu;
+namespace {
 
 template <typename R> struct CVec;
 template <> struct CVec<double> { typedef double2 type; };
@@ -61,77 +56,16 @@ struct CImage {
     __device__ __forceinline__ void put(int i, int j, Cx<R> z) const { typename CVec<R>::type v; v.x = z.re; v.y = z.im; s[i + j * ld] = v; }
 };
 
-struct CGeo {
-    int tpm;        // threads per matrix (64 | 128 | 256)
-    int tpm_log;
-    int rt_log;     // log2 of RT = rows of the (row, column-slice) thread grid: the smallest power of two >= m
-    int ct_log;     // log2 of the same for the columns (row-major loads and stores: lanes along a row)
-    int ld;         // LDS leading dimension in complex elements (odd)
-    unsigned group_bytes;
-    unsigned off_x, off_d, off_int;   // byte offsets inside a group's LDS: right-hand sides, diagonal reciprocals (solve), integer arrays
-};
-
-int clog2_ceil(int64_t v)
-{
-    int l = 0;
-    for (; ((int64_t)1 << l) < v; ++l) {}
-    return l;
-}
-
-CGeo cbatched_geo(int64_t m, int64_t n, size_t csize, bool solve)   // csize: bytes of a complex element
-{
-    CGeo g;
-    const int64_t mx = std::max(m, n);
-    g.tpm_log = mx <= 32 ? 6 : (mx <= 64 ? 7 : 8);
-    g.tpm = 1 << g.tpm_log;
-    g.rt_log = clog2_ceil(m);
-    g.ct_log = clog2_ceil(n);
-    g.ld = (int)(m | 1);
-    size_t off = (size_t)g.ld * (size_t)n * csize;   // csize is 8 or 16 and the base is 16-byte aligned: every section below stays aligned
-    off = (off + 15) & ~(size_t)15;
-    g.off_x = (unsigned)off;
-    if (solve) off += ((size_t)g.ld * CBNR * csize + 15) & ~(size_t)15;
-    g.off_d = (unsigned)off;
-    if (solve) off += ((size_t)n * csize + 15) & ~(size_t)15;
-    g.off_int = (unsigned)off;
-    off += ((size_t)(m + std::min(m, n)) * sizeof(int) + 15) & ~(size_t)15;
-    g.group_bytes = (unsigned)off;
-    return g;
-}
-
 // the modulus as an integer that orders like it; 0 for zeros and NaN (neither ever beats a candidate: `absi > amax`, lu.jl:301)
-__device__ __forceinline__ cu64 ckey(double v) { return (v > 0.0) ? (cu64)__double_as_longlong(v) : 0ull; }
-__device__ __forceinline__ cu64 ckey(float v) { return (v > 0.0f) ? (cu64)__float_as_uint(v) : 0ull; }
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ cu64 cdpp_max(cu64 v)
-{
-    const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-    const int olo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    const int ohi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    const cu64 o = ((cu64)(unsigned)ohi << 32) | (cu64)(unsigned)olo;
-    return o > v ? o : v;
-}
-// maximum over the 64 lanes of a wave (all of them active), wave-uniform: the DPP ladder of batched.hip
-__device__ __forceinline__ cu64 cwave_max(cu64 v)
-{
-    v = cdpp_max<0xB1, 0xf>(v);    // quad_perm:[1,0,3,2]
-    v = cdpp_max<0x4E, 0xf>(v);    // quad_perm:[2,3,0,1]
-    v = cdpp_max<0x141, 0xf>(v);   // row_half_mirror
-    v = cdpp_max<0x140, 0xf>(v);   // row_mirror
-    v = cdpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v = cdpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds the maximum
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-    return ((cu64)hi << 32) | (cu64)lo;
-}
+__device__ __forceinline__ bu64 ckey(double v) { return (v > 0.0) ? (bu64)__double_as_longlong(v) : 0ull; }
+__device__ __forceinline__ bu64 ckey(float v) { return (v > 0.0f) ? (bu64)__float_as_uint(v) : 0ull; }
 
 // ---- the one load ----------------------------------------------------------------------------------------------------------------
 // element (i, j) of the caller's matrix: G[i + j*lda] (column-major) or G[i*lda + j] (row-major), lda in complex elements; in LDS
 // always (i, j) of the image.  Column-major: lanes along a column (thread grid RT x TPM/RT); row-major: lanes along a row (CT x TPM/CT).
 // `valid` = false (a group beyond the end of the batch): zeros.
 template <typename R>
-__device__ __forceinline__ void cbload_matrix(const CImage<R>& S, const Cx<R>* G, int64_t lda, int row_major, int m, int n, const CGeo& g,
+__device__ __forceinline__ void cbload_matrix(const CImage<R>& S, const Cx<R>* G, int64_t lda, int row_major, int m, int n, const BGeo& g,
                                               int t, bool valid)
 {
     const Cx<R> zero{R(0), R(0)};
@@ -153,21 +87,21 @@ struct CFactorArgs {
     int64_t* info;
     int64_t lda, strideA, stride_ipiv, batch;
     int m, n, row_major, pivot;
-    CGeo g;
+    BGeo g;
 };
 
 template <typename R>
-__global__ void __launch_bounds__(CBT) cgetrf_batched_kernel(CFactorArgs<R> a)
+__global__ void __launch_bounds__(BT) cgetrf_batched_kernel(CFactorArgs<R> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char cbsmem[];
-    const CGeo g = a.g;
+    const BGeo g = a.g;
     const int m = a.m, n = a.n, mn = m < n ? m : n;
     const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1), lane = t & 63;
-    const int64_t b = (int64_t)blockIdx.x * (CBT >> g.tpm_log) + grp;
+    const int64_t b = (int64_t)blockIdx.x * (BT >> g.tpm_log) + grp;
     const bool valid = b < a.batch;
     unsigned char* base = cbsmem + (size_t)grp * g.group_bytes;
     const CImage<R> S{reinterpret_cast<typename CVec<R>::type*>(base), g.ld};
-    unsigned* spiv = reinterpret_cast<unsigned*>(base + g.off_int);   // [mn] position the pivot of step k came from
+    unsigned* spiv = reinterpret_cast<unsigned*>(base + g.off_b);   // [mn] position the pivot of step k came from
     unsigned* spos = spiv + mn;                                        // [m]  final position of every row
     Cx<R>* G = a.A + (valid ? b : 0) * a.strideA;
 
@@ -176,8 +110,8 @@ __global__ void __launch_bounds__(CBT) cgetrf_batched_kernel(CFactorArgs<R> a)
     // the row this thread updates, and the rows this lane looks at in the pivot search (every wave searches all rows)
     const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
     bool act = r < m;
-    unsigned mypos = act ? (unsigned)r : CPOS_NONE;
-    unsigned pos0 = lane < m ? (unsigned)lane : CPOS_NONE, pos1 = lane + 64 < m ? (unsigned)(lane + 64) : CPOS_NONE;
+    unsigned mypos = act ? (unsigned)r : BPOS_NONE;
+    unsigned pos0 = lane < m ? (unsigned)lane : BPOS_NONE, pos1 = lane + 64 < m ? (unsigned)(lane + 64) : BPOS_NONE;
     Cx<R> lprev{R(0), R(0)};
     bool updprev = false;
     int info = 0;
@@ -188,35 +122,35 @@ __global__ void __launch_bounds__(CBT) cgetrf_batched_kernel(CFactorArgs<R> a)
         int q = k;                   // row (as loaded) that becomes the pivot row
         unsigned gp = (unsigned)k;   // its current position
         if (a.pivot) {
-            cu64 key = 0;
-            unsigned pos = CPOS_NONE;
+            bu64 key = 0;
+            unsigned pos = BPOS_NONE;
             int phys = 0;
-            if (pos0 != CPOS_NONE) {
+            if (pos0 != BPOS_NONE) {
                 key = ckey(cmodulus(S.get(lane, k)));
                 pos = pos0;
                 phys = lane;
             }
-            if (pos1 != CPOS_NONE) {
-                const cu64 k1 = ckey(cmodulus(S.get(lane + 64, k)));
-                if (pos == CPOS_NONE || k1 > key || (k1 == key && pos1 < pos)) {
+            if (pos1 != BPOS_NONE) {
+                const bu64 k1 = ckey(cmodulus(S.get(lane + 64, k)));
+                if (pos == BPOS_NONE || k1 > key || (k1 == key && pos1 < pos)) {
                     key = k1;
                     pos = pos1;
                     phys = lane + 64;
                 }
             }
-            const cu64 mx = cwave_max(key);
-            const bool hit = pos != CPOS_NONE && key == mx;
-            cu64 mask = __ballot(hit);
+            const bu64 mx = bwave_max(key);
+            const bool hit = pos != BPOS_NONE && key == mx;
+            bu64 mask = __ballot(hit);
             if (__popcll(mask) > 1) {   // exact ties (and columns of zeros / NaN): the lowest position
-                const unsigned pm = ~(unsigned)cwave_max(hit ? (cu64)(~pos) : 0ull);
+                const unsigned pm = ~(unsigned)bwave_max(hit ? (bu64)(~pos) : 0ull);
                 mask = __ballot(hit && pos == pm);
             }
             // position k is always among the candidates, so mask != 0
             const int wl = __builtin_amdgcn_readfirstlane(__ffsll((long long)mask) - 1) & 63;
             gp = (unsigned)__builtin_amdgcn_readlane((int)pos, wl);
             q = __builtin_amdgcn_readlane(phys, wl);
-            if (pos0 != CPOS_NONE) pos0 = (lane == q) ? CPOS_NONE : (pos0 == (unsigned)k ? gp : pos0);
-            if (pos1 != CPOS_NONE) pos1 = (lane + 64 == q) ? CPOS_NONE : (pos1 == (unsigned)k ? gp : pos1);
+            if (pos0 != BPOS_NONE) pos0 = (lane == q) ? BPOS_NONE : (pos0 == (unsigned)k ? gp : pos0);
+            if (pos1 != BPOS_NONE) pos1 = (lane + 64 == q) ? BPOS_NONE : (pos1 == (unsigned)k ? gp : pos1);
         }
         const Cx<R> piv = S.get(q, k);
         const bool zero = piv.re == R(0) && piv.im == R(0);   // iszero: both parts
@@ -269,7 +203,7 @@ struct CSolveArgs {
     Cx<R>* B;
     int64_t lda, strideF, stride_ipiv, ldb, strideB, batch, nrhs;
     int n, row_major, trans;
-    CGeo g;
+    BGeo g;
 };
 
 // F(i, k) of the triangle being solved.  MODE 0: the LDS image by columns; 1 ('T'): by rows; 2 ('C'): by rows, conjugated as it is read
@@ -328,19 +262,19 @@ __device__ __forceinline__ void cbsubstitute(const CImage<R>& S, const CImage<R>
 }
 
 template <typename R>
-__global__ void __launch_bounds__(CBT) cgetrs_batched_kernel(CSolveArgs<R> a)
+__global__ void __launch_bounds__(BT) cgetrs_batched_kernel(CSolveArgs<R> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char cbsmem[];
-    const CGeo g = a.g;
+    const BGeo g = a.g;
     const int n = a.n;
     const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1), lane = t & 63;
-    const int64_t b = (int64_t)blockIdx.x * (CBT >> g.tpm_log) + grp;
+    const int64_t b = (int64_t)blockIdx.x * (BT >> g.tpm_log) + grp;
     const bool valid = b < a.batch;
     unsigned char* base = cbsmem + (size_t)grp * g.group_bytes;
     const CImage<R> S{reinterpret_cast<typename CVec<R>::type*>(base), g.ld};
     const CImage<R> X{reinterpret_cast<typename CVec<R>::type*>(base + g.off_x), g.ld};
-    const CImage<R> D{reinterpret_cast<typename CVec<R>::type*>(base + g.off_d), 0};   // [n]: reciprocal of the diagonal
-    int* sperm = reinterpret_cast<int*>(base + g.off_int);   // [n]: row i of P*B is row sperm[i] of B
+    const CImage<R> D{reinterpret_cast<typename CVec<R>::type*>(base + g.off_a), 0};   // [n]: reciprocal of the diagonal
+    int* sperm = reinterpret_cast<int*>(base + g.off_b);   // [n]: row i of P*B is row sperm[i] of B
     const int64_t bb = valid ? b : 0;
     const Cx<R>* F = a.F + bb * a.strideF;
     Cx<R>* B = a.B + bb * a.strideB;
@@ -378,9 +312,9 @@ __global__ void __launch_bounds__(CBT) cgetrs_batched_kernel(CSolveArgs<R> a)
 
     const Cx<R> zero{R(0), R(0)};
     const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
-    const int rr = t & (CBNR - 1), ri0 = t >> 3, ris = g.tpm >> 3;   // row-major right-hand sides: lanes along a row of B
-    for (int64_t j0 = 0; j0 < a.nrhs; j0 += CBNR) {
-        const int nr = (int)(a.nrhs - j0 < CBNR ? a.nrhs - j0 : CBNR);
+    const int rr = t & (BNR - 1), ri0 = t >> 3, ris = g.tpm >> 3;   // row-major right-hand sides: lanes along a row of B
+    for (int64_t j0 = 0; j0 < a.nrhs; j0 += BNR) {
+        const int nr = (int)(a.nrhs - j0 < BNR ? a.nrhs - j0 : BNR);
         // row i of the pass: from row perm[i] of B (forward solve: P B), or row i (transposed: the interchanges come last)
         if (!a.row_major) {
             if (r < n) {
@@ -414,16 +348,6 @@ __global__ void __launch_bounds__(CBT) cgetrs_batched_kernel(CSolveArgs<R> a)
     }
 }
 
-template <typename K>
-int cbatched_lds_attr(bool* done, K kernel, size_t lds)
-{
-    if (lds > 64 * 1024 && !*done) {   // above the default limit a kernel has to ask once (160 KiB per CU on gfx950)
-        RFLU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        *done = true;
-    }
-    return RFLU_OK;
-}
-
 }  // namespace
 
 template <typename R>
@@ -440,16 +364,9 @@ int launch_cgetrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, R* A, 
     a.A = reinterpret_cast<Cx<R>*>(A); a.ipiv = ipiv; a.info = info;
     a.lda = lda; a.strideA = strideA; a.stride_ipiv = stride_ipiv; a.batch = batch;
     a.m = (int)m; a.n = (int)n; a.row_major = row_major; a.pivot = pivot;
-    a.g = cbatched_geo(m, n, sizeof(Cx<R>), false);
-    const int groups = CBT / a.g.tpm;
-    const size_t lds = (size_t)groups * a.g.group_bytes;
-    RFLU_TRY(cbatched_lds_attr(&h->cbatched_attr_set[0][sizeof(R) == 4], &cgetrf_batched_kernel<R>, lds));
-    const int64_t wgs = (batch + groups - 1) / groups;
-    ProfScope ps(h, RFLU_K_PANEL, 4.0 * (double)batch * (double)m * (double)n * (double)std::min(m, n),
-                 2.0 * (double)batch * (double)m * (double)n * sizeof(Cx<R>));
-    hipLaunchKernelGGL((cgetrf_batched_kernel<R>), dim3((unsigned)wgs), dim3(CBT), lds, h->stream, a);
-    RFLU_HIP(hipGetLastError());
-    return RFLU_OK;
+    a.g = batched_geo(m, n, sizeof(Cx<R>), false, true);
+    return launch_batched(h, 0, 2 + (sizeof(R) == 4), &cgetrf_batched_kernel<R>, a, batch, RFLU_K_PANEL, 4.0 * (double)batch * (double)m * (double)n * (double)std::min(m, n),
+                          2.0 * (double)batch * (double)m * (double)n * sizeof(Cx<R>));
 }
 
 template <typename R>
@@ -460,16 +377,9 @@ int launch_cgetrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, con
     a.F = reinterpret_cast<const Cx<R>*>(F); a.ipiv = ipiv; a.B = reinterpret_cast<Cx<R>*>(B);
     a.lda = lda; a.strideF = strideF; a.stride_ipiv = stride_ipiv; a.ldb = ldb; a.strideB = strideB; a.batch = batch; a.nrhs = nrhs;
     a.n = (int)n; a.row_major = row_major; a.trans = trans;
-    a.g = cbatched_geo(n, n, sizeof(Cx<R>), true);
-    const int groups = CBT / a.g.tpm;
-    const size_t lds = (size_t)groups * a.g.group_bytes;
-    RFLU_TRY(cbatched_lds_attr(&h->cbatched_attr_set[1][sizeof(R) == 4], &cgetrs_batched_kernel<R>, lds));
-    const int64_t wgs = (batch + groups - 1) / groups;
-    ProfScope ps(h, RFLU_K_TRSM, 8.0 * (double)batch * (double)n * (double)n * (double)nrhs,
-                 (double)batch * ((double)n * (double)n + 2.0 * (double)n * (double)nrhs) * sizeof(Cx<R>));
-    hipLaunchKernelGGL((cgetrs_batched_kernel<R>), dim3((unsigned)wgs), dim3(CBT), lds, h->stream, a);
-    RFLU_HIP(hipGetLastError());
-    return RFLU_OK;
+    a.g = batched_geo(n, n, sizeof(Cx<R>), true, true);
+    return launch_batched(h, 1, 2 + (sizeof(R) == 4), &cgetrs_batched_kernel<R>, a, batch, RFLU_K_TRSM, 8.0 * (double)batch * (double)n * (double)n * (double)nrhs,
+                          (double)batch * ((double)n * (double)n + 2.0 * (double)n * (double)nrhs) * sizeof(Cx<R>));
 }
 
 template bool cbatched_fits<double>(int64_t, int64_t);

@@ -369,24 +369,61 @@ static int gemm_public(Handle* h, int64_t M, int64_t N, int64_t K, const T* A, i
 
 // ---- batched entries (include/rflu.h): `batch` independent matrices, strided.  max(m, n) <= BATCHED_MAX_DIM: one launch of the
 // batched kernels (batched.hip); larger: a loop over the single-matrix device path on the same stream -- correct, not fast, no size cliff.
+// The argument rules are the same for real and complex elements (`who` = the entry's name in the error text; lda / ldb / strides in
+// elements).  true: there is work to do; false: return *rc -- RFLU_ERR_ARG, or RFLU_OK for an empty batch, whose pointers nobody checks.
+static bool check_batched_factor_args(const char* who, int64_t batch, int64_t m, int64_t n, const void* A, int64_t lda, int64_t strideA,
+                                     int row_major, const int64_t* ipiv, int64_t stride_ipiv, int pivot, const int64_t* info_dev, int* rc)
+{
+    *rc = RFLU_ERR_ARG;
+    if (batch < 0 || m < 0 || n < 0) {
+        set_error("%s: negative size batch=%lld m=%lld n=%lld", who, (long long)batch, (long long)m, (long long)n);
+        return false;
+    }
+    if (batch == 0 || m == 0 || n == 0) { *rc = RFLU_OK; return false; }
+    const int64_t mn = std::min(m, n), rows = row_major ? n : m, cols = row_major ? m : n;   // rows = the contiguous dimension
+    if (A == nullptr || info_dev == nullptr) { set_error("%s: null matrix or info pointer", who); return false; }
+    if (pivot && ipiv == nullptr) { set_error("%s: pivot != 0 needs an ipiv buffer", who); return false; }
+    if (lda < rows || (batch > 1 && strideA < (cols - 1) * lda + rows)) {
+        set_error("%s: lda=%lld strideA=%lld too small for %lld x %lld (%s)", who, (long long)lda, (long long)strideA, (long long)m,
+                  (long long)n, row_major ? "row-major" : "column-major");
+        return false;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < mn) { set_error("%s: stride_ipiv=%lld < min(m, n)", who, (long long)stride_ipiv); return false; }
+    return true;
+}
+
+// trans3: trans has to be 0, 1 or 2 (the complex entries; the real ones read any non-zero value as "transposed")
+static bool check_batched_solve_args(const char* who, int64_t batch, int64_t n, int64_t nrhs, const void* F, int64_t lda, int64_t strideF,
+                                    int row_major, const int64_t* ipiv, int64_t stride_ipiv, const void* B, int64_t ldb, int64_t strideB,
+                                    int trans, bool trans3, int* rc)
+{
+    *rc = RFLU_ERR_ARG;
+    if (batch < 0 || n < 0 || nrhs < 0) {
+        set_error("%s: negative size batch=%lld n=%lld nrhs=%lld", who, (long long)batch, (long long)n, (long long)nrhs);
+        return false;
+    }
+    if (trans3 && (trans < 0 || trans > 2)) {
+        set_error("%s: trans must be 0 (A), 1 (transpose) or 2 (adjoint), got %d", who, trans);
+        return false;
+    }
+    if (batch == 0 || n == 0 || nrhs == 0) { *rc = RFLU_OK; return false; }
+    if (F == nullptr || B == nullptr) { set_error("%s: null pointer", who); return false; }
+    const int64_t brows = row_major ? nrhs : n, bcols = row_major ? n : nrhs;   // brows = the contiguous dimension of B
+    if (lda < n || ldb < brows || (batch > 1 && (strideF < (n - 1) * lda + n || strideB < (bcols - 1) * ldb + brows))) {
+        set_error("%s: lda=%lld strideF=%lld ldb=%lld strideB=%lld too small for n=%lld nrhs=%lld (%s)", who, (long long)lda,
+                  (long long)strideF, (long long)ldb, (long long)strideB, (long long)n, (long long)nrhs, row_major ? "row-major" : "column-major");
+        return false;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("%s: stride_ipiv=%lld < n", who, (long long)stride_ipiv); return false; }
+    return true;
+}
+
 template <typename T>
 static int getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, int64_t lda, int64_t strideA, int row_major,
                          int64_t* ipiv, int64_t stride_ipiv, int pivot, int64_t* info_dev)
 {
-    if (batch < 0 || m < 0 || n < 0) {
-        set_error("getrf_batched: negative size batch=%lld m=%lld n=%lld", (long long)batch, (long long)m, (long long)n);
-        return RFLU_ERR_ARG;
-    }
-    if (batch == 0 || m == 0 || n == 0) return RFLU_OK;
-    const int64_t mn = std::min(m, n), rows = row_major ? n : m, cols = row_major ? m : n;   // rows = the contiguous dimension
-    if (A == nullptr || info_dev == nullptr) { set_error("getrf_batched: null matrix or info pointer"); return RFLU_ERR_ARG; }
-    if (pivot && ipiv == nullptr) { set_error("getrf_batched: pivot != 0 needs an ipiv buffer"); return RFLU_ERR_ARG; }
-    if (lda < rows || (batch > 1 && strideA < (cols - 1) * lda + rows)) {
-        set_error("getrf_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", (long long)lda, (long long)strideA, (long long)m,
-                  (long long)n, row_major ? "row-major" : "column-major");
-        return RFLU_ERR_ARG;
-    }
-    if (ipiv && batch > 1 && stride_ipiv < mn) { set_error("getrf_batched: stride_ipiv=%lld < min(m, n)", (long long)stride_ipiv); return RFLU_ERR_ARG; }
+    int rc;
+    if (!check_batched_factor_args("getrf_batched", batch, m, n, A, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info_dev, &rc)) return rc;
     if (batched_fits(m, n)) {
         RFLU_TRY(launch_getrf_batched<T>(h, batch, m, n, A, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info_dev));
         RFLU_HIP(hipStreamSynchronize(h->stream));
@@ -409,19 +446,8 @@ template <typename T>
 static int getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const T* F, int64_t lda, int64_t strideF, int row_major,
                          const int64_t* ipiv, int64_t stride_ipiv, T* B, int64_t ldb, int64_t strideB, int trans)
 {
-    if (batch < 0 || n < 0 || nrhs < 0) {
-        set_error("getrs_batched: negative size batch=%lld n=%lld nrhs=%lld", (long long)batch, (long long)n, (long long)nrhs);
-        return RFLU_ERR_ARG;
-    }
-    if (batch == 0 || n == 0 || nrhs == 0) return RFLU_OK;
-    if (F == nullptr || B == nullptr) { set_error("getrs_batched: null pointer"); return RFLU_ERR_ARG; }
-    const int64_t brows = row_major ? nrhs : n, bcols = row_major ? n : nrhs;   // brows = the contiguous dimension of B
-    if (lda < n || ldb < brows || (batch > 1 && (strideF < (n - 1) * lda + n || strideB < (bcols - 1) * ldb + brows))) {
-        set_error("getrs_batched: lda=%lld strideF=%lld ldb=%lld strideB=%lld too small for n=%lld nrhs=%lld (%s)", (long long)lda,
-                  (long long)strideF, (long long)ldb, (long long)strideB, (long long)n, (long long)nrhs, row_major ? "row-major" : "column-major");
-        return RFLU_ERR_ARG;
-    }
-    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("getrs_batched: stride_ipiv=%lld < n", (long long)stride_ipiv); return RFLU_ERR_ARG; }
+    int rc;
+    if (!check_batched_solve_args("getrs_batched", batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb, strideB, trans, false, &rc)) return rc;
     if (batched_fits(n, n)) {
         RFLU_TRY(launch_getrs_batched<T>(h, batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb, strideB, trans ? 1 : 0));
         RFLU_HIP(hipStreamSynchronize(h->stream));
@@ -439,42 +465,30 @@ static int getrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, cons
     return RFLU_OK;
 }
 
-// ---- complex batched entries (include/rflu.h; kernels: batched_complex.hip).  The argument rules of the real
-// entries above, lda / ldb / strides in complex elements.  Above the one-launch limit: column-major batches loop over the single-matrix
-// complex device path; row-major ones are refused, because that path is column-major only.
+// ---- complex batched entries (include/rflu.h; kernels: batched_complex.hip).  Above the one-launch limit:
+// column-major batches loop over the single-matrix complex device path; row-major ones are refused, because that path is column-major only.
+template <typename R>
+static int refuse_large_row_major(const char* who)
+{
+    const int lim = sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32;
+    set_error("%s: row-major matrices larger than %d x %d are not served (the single-matrix complex path that "
+              "larger batches loop over is column-major only)", who, lim, lim);
+    return RFLU_ERR_ARG;
+}
+
 template <typename R>
 static int cgetrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, R* A, int64_t lda, int64_t strideA, int row_major,
                           int64_t* ipiv, int64_t stride_ipiv, int pivot, int64_t* info_dev)
 {
-    if (batch < 0 || m < 0 || n < 0) {
-        set_error("complex getrf_batched: negative size batch=%lld m=%lld n=%lld", (long long)batch, (long long)m, (long long)n);
-        return RFLU_ERR_ARG;
-    }
-    if (batch == 0 || m == 0 || n == 0) return RFLU_OK;
-    const int64_t mn = std::min(m, n), rows = row_major ? n : m, cols = row_major ? m : n;   // rows = the contiguous dimension
-    if (A == nullptr || info_dev == nullptr) { set_error("complex getrf_batched: null matrix or info pointer"); return RFLU_ERR_ARG; }
-    if (pivot && ipiv == nullptr) { set_error("complex getrf_batched: pivot != 0 needs an ipiv buffer"); return RFLU_ERR_ARG; }
-    if (lda < rows || (batch > 1 && strideA < (cols - 1) * lda + rows)) {
-        set_error("complex getrf_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", (long long)lda, (long long)strideA,
-                  (long long)m, (long long)n, row_major ? "row-major" : "column-major");
-        return RFLU_ERR_ARG;
-    }
-    if (ipiv && batch > 1 && stride_ipiv < mn) {
-        set_error("complex getrf_batched: stride_ipiv=%lld < min(m, n)", (long long)stride_ipiv);
-        return RFLU_ERR_ARG;
-    }
+    int rc;
+    if (!check_batched_factor_args("complex getrf_batched", batch, m, n, A, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info_dev, &rc)) return rc;
     if (cbatched_fits<R>(m, n)) {
         RFLU_TRY(launch_cgetrf_batched<R>(h, batch, m, n, A, lda, strideA, row_major, ipiv, stride_ipiv, pivot, info_dev));
         RFLU_HIP(hipStreamSynchronize(h->stream));
         h->last_path = RFLU_PATH_HIP_BATCHED;
         return RFLU_OK;
     }
-    if (row_major) {
-        set_error("complex getrf_batched: row-major matrices larger than %d x %d are not served (the single-matrix complex path that "
-                  "larger batches loop over is column-major only)", sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32,
-                  sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32);
-        return RFLU_ERR_ARG;
-    }
+    if (row_major) return refuse_large_row_major<R>("complex getrf_batched");
     std::vector<int64_t> infos((size_t)batch, 0);
     for (int64_t b = 0; b < batch; ++b)
         RFLU_TRY(cgetrf_cm_dev<R>(h, m, n, A + 2 * b * strideA, lda, ipiv ? ipiv + b * stride_ipiv : nullptr, pivot, &infos[(size_t)b]));
@@ -487,38 +501,15 @@ template <typename R>
 static int cgetrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const R* F, int64_t lda, int64_t strideF, int row_major,
                           const int64_t* ipiv, int64_t stride_ipiv, R* B, int64_t ldb, int64_t strideB, int trans)
 {
-    if (batch < 0 || n < 0 || nrhs < 0) {
-        set_error("complex getrs_batched: negative size batch=%lld n=%lld nrhs=%lld", (long long)batch, (long long)n, (long long)nrhs);
-        return RFLU_ERR_ARG;
-    }
-    if (trans < 0 || trans > 2) {
-        set_error("complex getrs_batched: trans must be 0 (A), 1 (transpose) or 2 (adjoint), got %d", trans);
-        return RFLU_ERR_ARG;
-    }
-    if (batch == 0 || n == 0 || nrhs == 0) return RFLU_OK;
-    if (F == nullptr || B == nullptr) { set_error("complex getrs_batched: null pointer"); return RFLU_ERR_ARG; }
-    const int64_t brows = row_major ? nrhs : n, bcols = row_major ? n : nrhs;   // brows = the contiguous dimension of B
-    if (lda < n || ldb < brows || (batch > 1 && (strideF < (n - 1) * lda + n || strideB < (bcols - 1) * ldb + brows))) {
-        set_error("complex getrs_batched: lda=%lld strideF=%lld ldb=%lld strideB=%lld too small for n=%lld nrhs=%lld (%s)", (long long)lda,
-                  (long long)strideF, (long long)ldb, (long long)strideB, (long long)n, (long long)nrhs, row_major ? "row-major" : "column-major");
-        return RFLU_ERR_ARG;
-    }
-    if (ipiv && batch > 1 && stride_ipiv < n) {
-        set_error("complex getrs_batched: stride_ipiv=%lld < n", (long long)stride_ipiv);
-        return RFLU_ERR_ARG;
-    }
+    int rc;
+    if (!check_batched_solve_args("complex getrs_batched", batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb, strideB, trans, true, &rc)) return rc;
     if (cbatched_fits<R>(n, n)) {
         RFLU_TRY(launch_cgetrs_batched<R>(h, batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb, strideB, trans));
         RFLU_HIP(hipStreamSynchronize(h->stream));
         h->last_path = RFLU_PATH_HIP_BATCHED;
         return RFLU_OK;
     }
-    if (row_major) {
-        set_error("complex getrs_batched: row-major matrices larger than %d x %d are not served (the single-matrix complex path that "
-                  "larger batches loop over is column-major only)", sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32,
-                  sizeof(R) == 8 ? (int)CBATCHED_MAX_DIM_CF64 : (int)CBATCHED_MAX_DIM_CF32);
-        return RFLU_ERR_ARG;
-    }
+    if (row_major) return refuse_large_row_major<R>("complex getrs_batched");
     for (int64_t b = 0; b < batch; ++b) {
         const R* Fb = F + 2 * b * strideF;
         const int64_t* ip = ipiv ? ipiv + b * stride_ipiv : nullptr;

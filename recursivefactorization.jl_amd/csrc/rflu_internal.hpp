@@ -241,9 +241,7 @@ struct Handle {
     bool la_attr_set[2] = {false, false};     // dynamic-LDS opt-in of leaf_la_kernel (f64, f32)
     bool gemm_attr_set[2] = {false, false};   // dynamic-LDS opt-in of the GEMM kernels done on this handle's device (f64, f32)
     bool eng_attr_set[2] = {false, false};    // same for the persistent update engine (engine.hip)
-    bool batched_attr_set[2][2] = {};         // same for the batched kernels (batched.hip): [factorization|solve][Float64|Float32]
-    bool batched_inv_attr_set[2] = {};        // ... and the batched inverse: [Float64|Float32]
-    bool cbatched_attr_set[2][2] = {};        // ... and the complex batched kernels (batched_complex.hip): [factorization|solve][ComplexF64|ComplexF32]
+    bool batched_attr_set[3][4] = {};         // same for the batched kernels (batched_kernels.hpp): [getrf|getrs|getri][f64, f32, cf64, cf32]
     void* eng_state = nullptr;                // device: EngState (engine.hpp)
     void* eng_host = nullptr;                 // pinned host image of its initial value
     long long* eng_trace_buf = nullptr;       // device: RFLU_ENGINE_TRACE stamps + workgroup-time accounting (measurement only)
@@ -410,7 +408,7 @@ template <typename T>
 int launch_butterfly_mul(Handle* h, int64_t n, T* A, int64_t lda, const T* uv);
 template <typename T>
 int launch_butterfly_vec(Handle* h, int64_t n, int64_t nrhs, T* X, int64_t ldx, const T* uv, int mode);
-// batched.hip: `batch` independent matrices of max(m, n) <= BATCHED_MAX_DIM, one group of threads each, everything between the one
+// batched.hip (geometry, wave maximum and launch: batched_kernels.hpp): `batch` independent matrices of max(m, n) <= BATCHED_MAX_DIM, one group of threads each, everything between the one
 // load and the one store in LDS.  Matrix b at A + b*strideA, element (i, j) at [i + j*lda] or (row_major) [i*lda + j]; info: DEVICE
 // array of `batch` entries.  The solve: B in the orientation of F, any nrhs in passes of 8, trans = B <- A^-T B.
 constexpr int64_t BATCHED_MAX_DIM = 128;

@@ -1,7 +1,7 @@
 """The complex batched factorization and solve through the layers that can be checked without a GPU: the four
 rflu_get{rf,rs}_batched_cf{64,32}_dev symbols in include/rflu.h, their ctypes bindings, the exports of the built library, the Julia
 ccalls, the argument checks the Python mirror makes BEFORE it touches the library, the build list, the documents, and the structural
-promise of csrc/batched_complex.hip: matrices never wait for each other."""
+promise of csrc/batched_kernels.hpp and csrc/batched_complex.hip: matrices never wait for each other."""
 import os
 import re
 import subprocess
@@ -64,11 +64,12 @@ def test_julia_ccalls_exist_and_match_the_header():
 
 
 def test_build_list_limits_and_documents():
-    assert "batched_complex.hip" in build.SOURCES
-    assert sorted(build.EXTRA_DEPS["batched_complex.hip"]) == ["complex.hpp", "complex_dev.hpp"]
+    assert "batched_complex.hip" in build.SOURCES and "batched_kernels.hpp" in build.ALL_HEADERS
+    assert sorted(build.EXTRA_DEPS["batched_complex.hip"]) == ["batched_kernels.hpp", "complex.hpp", "complex_dev.hpp"]
+    assert build.EXTRA_DEPS["batched.hip"] == ["batched_kernels.hpp"]
     hdr = open(os.path.join(CSRC, "rflu_internal.hpp")).read()
     assert re.search(r"CBATCHED_MAX_DIM_CF32\s*=\s*128\b", hdr) and re.search(r"CBATCHED_MAX_DIM_CF64\s*=\s*64\b", hdr)
-    assert "cbatched_attr_set" in hdr
+    assert "batched_attr_set[3][4]" in hdr   # one array of dynamic-LDS flags: [getrf | getrs | getri][f64, f32, cf64, cf32]
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
         assert "rflu_getrf_batched_cf64_dev" in open(os.path.join(ROOT, doc)).read(), doc
     api = open(os.path.join(ROOT, "include", "rflu.h")).read()
@@ -78,19 +79,26 @@ def test_build_list_limits_and_documents():
 
 
 def test_the_real_batched_file_stays_real_only():
-    code = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "batched.hip")).read())
-    assert re.findall(r'#include\s+"([^"]+)"', code) == ["rflu_internal.hpp"] and "Cx<" not in code
+    """Geometry, wave maximum and launch are shared through batched_kernels.hpp; the complex element stays out of it and out of the real
+    file, so that a change to complex_dev.hpp does not rebuild the real kernels."""
+    for fn in ("batched.hip", "batched_kernels.hpp"):
+        code = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, fn)).read())
+        assert "Cx<" not in code, fn
+        assert not any("complex" in inc for inc in re.findall(r'#include\s+["<]([^">]+)[">]', code)), fn
 
 
 def test_complex_batched_kernels_wait_for_nobody():
-    """As tests/test_batched_glue.py asks of batched.hip: none of the project's helpers for waiting on another workgroup, no cooperative
-    launch, no read-modify-write on shared words, no loop without a trip count."""
-    text = open(os.path.join(CSRC, "batched_complex.hip")).read()
-    code = re.sub(r"//[^\n]*", "", text)
-    assert re.findall(r'#include\s+"([^"]+)"', code) == ["complex_dev.hpp"]
+    """As tests/test_batched_glue.py asks of the real elements: none of the project's helpers for waiting on another workgroup, no
+    cooperative launch, no read-modify-write on shared words, no loop without a trip count -- in batched_kernels.hpp, which holds what the
+    kernels share, and in batched_complex.hip, which holds the kernels of the complex elements."""
+    mine = ("batched_kernels.hpp", "batched_complex.hip")
+    codes = [re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, fn)).read()) for fn in mine]
+    assert re.findall(r'#include\s+"([^"]+)"', codes[0]) == ["rflu_internal.hpp"]
+    assert re.findall(r'#include\s+"([^"]+)"', codes[1]) == ["complex_dev.hpp", "batched_kernels.hpp"]
+    code = "\n".join(codes)
     helpers = set()
     for fn in os.listdir(CSRC):
-        if fn == "batched_complex.hip" or not fn.endswith((".hip", ".hpp", ".cpp")):
+        if fn in mine or fn == "batched.hip" or not fn.endswith((".hip", ".hpp", ".cpp")):
             continue
         helpers |= set(re.findall(r"\b(\w*(?:poll|spin|gate_wait|lds_wait)\w*)\s*\(", open(os.path.join(CSRC, fn)).read(), flags=re.I))
     assert helpers, "the scan for the poll helpers found nothing: the pattern is stale"
@@ -98,10 +106,13 @@ def test_complex_batched_kernels_wait_for_nobody():
         assert not re.search(rf"\b{re.escape(name)}\s*\(", code), name
     for needle in ("SPIN_LIMIT", "s_sleep", "hipLaunchCooperativeKernel", "atomic", "AUX_SC1", "__builtin_amdgcn_raw_buffer", "while (", "while("):
         assert needle not in code, needle
-    # one barrier per pivot column: the factorization loop holds exactly one
-    body = code[code.index("cgetrf_batched_kernel(CFactorArgs<R> a)"):code.index("struct CSolveArgs")]
-    loop = body[body.index("for (int k = 0; k < mn; ++k)"):body.index("if (updprev && c == 0) S.put(r, mn - 1, lprev);")]
-    assert loop.count("__syncthreads()") == 2   # the one inside the loop and the one that closes the last step
+    # one barrier per pivot column, for every element: each of the two factorization loops holds exactly one
+    real = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "batched.hip")).read())
+    for src, head, tail, last in ((real, "getrf_batched_kernel(BFactorArgs<T> a)", "struct BSolveArgs", "if (updprev && c == 0) s[r + (mn - 1) * ld] = lprev;"),
+                                  (codes[1], "cgetrf_batched_kernel(CFactorArgs<R> a)", "struct CSolveArgs", "if (updprev && c == 0) S.put(r, mn - 1, lprev);")):
+        body = src[src.index(head):src.index(tail)]
+        loop = body[body.index("for (int k = 0; k < mn; ++k)"):body.index(last)]
+        assert loop.count("__syncthreads()") == 2   # the one inside the loop and the one that closes the last step
 
 
 class _NoLibrary:
