@@ -260,7 +260,8 @@ int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, c
  *   - every kernel is an in-order launch on the handle's stream and NONE waits for another workgroup: no cooperative launch, no flag,
  *     no RFLU_ERR_TIMEOUT from these entries.  Work is complete on return;
  *   - rflu_getrs_*: ldiv!(F, B) for any nrhs, F / ipiv as the factorization left them; a singular U yields Inf/NaN, no error status.
- *     The batched form is rflu_get{rf,rs}_batched_cf64_dev / _cf32_dev below; there is no mixed / inverse form;
+ *     The batched form is rflu_get{rf,rs}_batched_cf64_dev / _cf32_dev below, inv! / det / logabsdet from these factors are
+ *     rflu_getri_c* / rflu_logabsdet_c* further below; there is no mixed-precision form;
  *   - rflu_getrs_trans_*: ldiv!(transpose(F), B) and ldiv!(F', B), which differ for these element types, so the entries take `conj`:
  *     conj = 0 solves transpose(A) x = b (LAPACK 'T', B <- P^T L^-T U^-T B), conj = 1 solves A' x = b (LAPACK 'C', B <- P^T L^-H U^-H B),
  *     any other value is RFLU_ERR_ARG.  Everything else is as rflu_getrs_*: storage, lda / ldb, NULL ipiv = NotIPIV, alignment, any
@@ -293,6 +294,48 @@ int rflu_getrs_trans_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, con
                               double* B_dev, int64_t ldb, int conj);
 int rflu_getrs_trans_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda, const int64_t* ipiv_dev,
                               float* B_dev, int64_t ldb, int conj);
+/* COMPLEX INVERSE, DETERMINANT: inv! / inv, det, logabsdet, logdet on a ComplexF64 / ComplexF32 LU (csrc/complex_inverse.hip, DESIGN.md
+ * section 4.8).  Storage as in the other complex entries: double* / float* to interleaved (re, im) pairs; lda / ld / strideF count
+ * COMPLEX elements; a pointer aligned to the real type is enough.  The contract is that of rflu_getri_* and rflu_logabsdet_* in the
+ * INVERSE, DETERMINANT block above, word for word: ipiv NULL = NotIPIV; in-order launches on the handle's stream, no kernel waits for
+ * another workgroup, no value is formed by read-modify-write on shared words, so results are bit-identical from run to run; n == 0
+ * succeeds with nothing launched; negative sizes, lda < n and NULL pointers give RFLU_ERR_ARG with a message; work is complete on return.
+ * There is no row-major entry: the single-matrix complex path is column-major only.
+ *   - rflu_getri_c*: F (packed L\U exactly as rflu_getrf_c* left it) is overwritten by A^-1.  *info (host, required): 0, or the 1-based
+ *     index of the first u_ii with BOTH parts zero -- then F is left UNTOUCHED and the return value is still RFLU_OK.  The sweeps of
+ *     DESIGN.md section 4.4 IN PLACE on F read as a row-major array with ld = lda, which is transpose(F) -- the plain transpose, nothing
+ *     is ever conjugated.  About 4n^3/3 complex multiply-adds through the complex MFMA GEMM against 2n^3 for rflu_getrs_c* on an explicit
+ *     identity; workspace owned by the handle: one buffer of 512 x n complex elements and 2 * ceil(n/64) * 4096 for the 64x64 diagonal
+ *     inverses, nothing of size n x n.  Any lda >= n; where the pointer is no multiple of 16 bytes (_cf32: or lda is odd) the GEMM loads
+ *     element by element, same arithmetic, same bits.  Entries of F beyond the n x n matrix are never written.  The host entry: H2D, the
+ *     device entry, D2H (not at all when info != 0);
+ *   - rflu_logabsdet_c*: *logabs_out = sum of log|u_ii| with |u| = hypot(re, im); (*sign_re_out, *sign_im_out) = det A / |det A| = the
+ *     product of u_ii / |u_ii| times (-1)^#{k : ipiv[k] != k+1}, renormalised to modulus 1 once at the end.  All three are host
+ *     pointers, required.  Float64 arithmetic for both element types, in the fixed order of rflu_logabsdet_*: chunks of 1024 entries,
+ *     four per thread in index order, a fixed tree, chunk results in index order (sums for the logs, products for the phases).  A u_ii
+ *     with both parts zero gives (-Inf, 0 + 0i), a NaN in either part gives NaN in all three, n == 0 gives (0, 1 + 0i).  The diagonal
+ *     sits at F[i*(ld+1)]; the host entry copies the diagonal and ipiv only;
+ *   - rflu_logabsdet_batched_c*: the same for every matrix of a batch (matrix b at F_dev + b*strideF complex elements, ipiv at ipiv_dev +
+ *     b*stride_ipiv); logabs_dev: DEVICE array of `batch` doubles, sign_dev: DEVICE array of `batch` interleaved (re, im) pairs.  One
+ *     launch, one workgroup per matrix, any n (only diagonals are read, so it serves both orientations of rflu_getrf_batched_c*'s
+ *     factors); bit-identical to the single-matrix entry on the same factors.
+ * Not here: a batched complex getri, row-major complex factors, complex mixed precision. */
+int rflu_getri_cf64_dev(rflu_handle_t handle, int64_t n, double* F_dev, int64_t lda, const int64_t* ipiv_dev, int64_t* info);
+int rflu_getri_cf32_dev(rflu_handle_t handle, int64_t n, float* F_dev, int64_t lda, const int64_t* ipiv_dev, int64_t* info);
+int rflu_getri_cf64(rflu_handle_t handle, int64_t n, double* F_host, int64_t lda, const int64_t* ipiv_host, int64_t* info);
+int rflu_getri_cf32(rflu_handle_t handle, int64_t n, float* F_host, int64_t lda, const int64_t* ipiv_host, int64_t* info);
+int rflu_logabsdet_cf64_dev(rflu_handle_t handle, int64_t n, const double* F_dev, int64_t ld, const int64_t* ipiv_dev,
+                            double* logabs_out, double* sign_re_out, double* sign_im_out);
+int rflu_logabsdet_cf32_dev(rflu_handle_t handle, int64_t n, const float* F_dev, int64_t ld, const int64_t* ipiv_dev,
+                            double* logabs_out, double* sign_re_out, double* sign_im_out);
+int rflu_logabsdet_cf64(rflu_handle_t handle, int64_t n, const double* F_host, int64_t ld, const int64_t* ipiv_host,
+                        double* logabs_out, double* sign_re_out, double* sign_im_out);
+int rflu_logabsdet_cf32(rflu_handle_t handle, int64_t n, const float* F_host, int64_t ld, const int64_t* ipiv_host,
+                        double* logabs_out, double* sign_re_out, double* sign_im_out);
+int rflu_logabsdet_batched_cf64_dev(rflu_handle_t handle, int64_t batch, int64_t n, const double* F_dev, int64_t lda, int64_t strideF,
+                                    const int64_t* ipiv_dev, int64_t stride_ipiv, double* logabs_dev, double* sign_dev);
+int rflu_logabsdet_batched_cf32_dev(rflu_handle_t handle, int64_t batch, int64_t n, const float* F_dev, int64_t lda, int64_t strideF,
+                                    const int64_t* ipiv_dev, int64_t stride_ipiv, double* logabs_dev, double* sign_dev);
 /* BATCHED COMPLEX: `batch` independent small ComplexF64 / ComplexF32 systems in one call (csrc/batched_complex.hip, DESIGN.md section
  * 4.7).  Storage as in the other complex entries: double* / float* to interleaved (re, im) pairs; lda, ldb, strideA / strideF / strideB
  * count COMPLEX elements.  Everything else is the contract of the BATCHED entries above, word for word: strided matrices (matrix b at

@@ -495,6 +495,97 @@ function logabsdet_batched_dev!(logabs::Ptr{Float64}, sign::Ptr{Float64}, F::Ptr
     return nothing
 end
 
+# ---- inv! / logabsdet from ComplexF64 / ComplexF32 factors (rflu_getri_c* / rflu_logabsdet_c*, csrc/complex_inverse.hip): the methods of
+# getri! / getri_dev! / logabsdet_dev / logabsdet_host / logabsdet_batched_dev! for the complex pointer and matrix types.  Column-major
+# only (there is no row-major complex entry); the sign is det / |det|, a ComplexF64 (batched: `sign` points at `batch` ComplexF64 values).
+function getri!(F::StridedMatrix{ComplexF64}, ipiv::Ptr{Int64})
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getri_cf64, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), size(F, 1), reinterpret(Ptr{Float64}, pointer(F)), stride(F, 2), ipiv, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return info[]
+end
+
+function getri_dev!(F::Ptr{ComplexF64}, n::Integer, ld::Integer, ipiv::Ptr{Int64})
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getri_cf64_dev, librflu), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), n, reinterpret(Ptr{Float64}, F), ld, ipiv, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return info[]
+end
+
+function logabsdet_dev(F::Ptr{ComplexF64}, n::Integer, ld::Integer, ipiv::Ptr{Int64})
+    out = zeros(Float64, 3)
+    st = GC.@preserve out ccall((:rflu_logabsdet_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               handle(), n, reinterpret(Ptr{Float64}, F), ld, ipiv, pointer(out, 1), pointer(out, 2), pointer(out, 3))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1], complex(out[2], out[3])
+end
+
+function logabsdet_host(F::StridedMatrix{ComplexF64}, ipiv::Ptr{Int64})
+    out = zeros(Float64, 3)
+    st = GC.@preserve out ccall((:rflu_logabsdet_cf64, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               handle(), size(F, 1), reinterpret(Ptr{Float64}, pointer(F)), stride(F, 2), ipiv, pointer(out, 1), pointer(out, 2), pointer(out, 3))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1], complex(out[2], out[3])
+end
+
+function logabsdet_batched_dev!(logabs::Ptr{Float64}, sign::Ptr{ComplexF64}, F::Ptr{ComplexF64}, batch::Integer, n::Integer, lda::Integer,
+                                strideF::Integer, ipiv::Ptr{Int64}, stride_ipiv::Integer)
+    st = ccall((:rflu_logabsdet_batched_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}),
+               handle(), batch, n, reinterpret(Ptr{Float64}, F), lda, strideF, ipiv, stride_ipiv, logabs, reinterpret(Ptr{Float64}, sign))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function getri!(F::StridedMatrix{ComplexF32}, ipiv::Ptr{Int64})
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getri_cf32, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), size(F, 1), reinterpret(Ptr{Float32}, pointer(F)), stride(F, 2), ipiv, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return info[]
+end
+
+function getri_dev!(F::Ptr{ComplexF32}, n::Integer, ld::Integer, ipiv::Ptr{Int64})
+    info = Ref{Int64}(0)
+    st = ccall((:rflu_getri_cf32_dev, librflu), Cint, (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ref{Int64}),
+               handle(), n, reinterpret(Ptr{Float32}, F), ld, ipiv, info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return info[]
+end
+
+function logabsdet_dev(F::Ptr{ComplexF32}, n::Integer, ld::Integer, ipiv::Ptr{Int64})
+    out = zeros(Float64, 3)
+    st = GC.@preserve out ccall((:rflu_logabsdet_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               handle(), n, reinterpret(Ptr{Float32}, F), ld, ipiv, pointer(out, 1), pointer(out, 2), pointer(out, 3))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1], complex(out[2], out[3])
+end
+
+function logabsdet_host(F::StridedMatrix{ComplexF32}, ipiv::Ptr{Int64})
+    out = zeros(Float64, 3)
+    st = GC.@preserve out ccall((:rflu_logabsdet_cf32, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               handle(), size(F, 1), reinterpret(Ptr{Float32}, pointer(F)), stride(F, 2), ipiv, pointer(out, 1), pointer(out, 2), pointer(out, 3))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1], complex(out[2], out[3])
+end
+
+function logabsdet_batched_dev!(logabs::Ptr{Float64}, sign::Ptr{ComplexF64}, F::Ptr{ComplexF32}, batch::Integer, n::Integer, lda::Integer,
+                                strideF::Integer, ipiv::Ptr{Int64}, stride_ipiv::Integer)
+    st = ccall((:rflu_logabsdet_batched_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}),
+               handle(), batch, n, reinterpret(Ptr{Float32}, F), lda, strideF, ipiv, stride_ipiv, logabs, reinterpret(Ptr{Float64}, sign))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
 # ---- dispatch: who serves a call (RecursiveFactorization src/lu.jl:92-93, 114-126) -------------------------------------------
 const GPUEltype = Union{Float32, Float64}                                  # every entry serves these
 const GPUAnyEltype = Union{Float32, Float64, ComplexF32, ComplexF64}       # lu! and ldiv!(F, B) serve the complex types as well
@@ -585,6 +676,30 @@ end
 
 "`det(F)` = sign * exp(logabs): equal to the stdlib's running product up to rounding, 0 for a singular `F`"
 function det(F::LU{T, <:StridedMatrix{T}}) where {T <: GPUEltype}
+    lu_on_gpu(F) || return LinearAlgebra.det(F)
+    la, sg = logabsdet(F)
+    return iszero(sg) ? zero(T) : sg * exp(la)
+end
+
+# the complex element types: the same three on the GPU.  The sign is the unit complex number det / |det|; adjoint / transpose wrappers of
+# an LU are left to the stdlib (det(F') is the conjugate, det(transpose(F)) the plain value: LinearAlgebra derives both from these).
+function inv!(F::LU{T, <:StridedMatrix{T}}) where {T <: GPUComplexEltype}
+    lu_on_gpu(F) || return LinearAlgebra.inv!(F)
+    checknonsingular(F.info)
+    p = F.ipiv isa NotIPIV ? Ptr{Int64}(C_NULL) : pointer(F.ipiv)
+    info = GC.@preserve F getri!(F.factors, p)
+    checknonsingular(info)
+    return F.factors
+end
+
+function logabsdet(F::LU{T, <:StridedMatrix{T}}) where {T <: GPUComplexEltype}
+    lu_on_gpu(F) || return LinearAlgebra.logabsdet(F)
+    p = F.ipiv isa NotIPIV ? Ptr{Int64}(C_NULL) : pointer(F.ipiv)
+    la, sg = GC.@preserve F logabsdet_host(F.factors, p)
+    return real(T)(la), T(sg)
+end
+
+function det(F::LU{T, <:StridedMatrix{T}}) where {T <: GPUComplexEltype}
     lu_on_gpu(F) || return LinearAlgebra.det(F)
     la, sg = logabsdet(F)
     return iszero(sg) ? zero(T) : sg * exp(la)

@@ -73,6 +73,23 @@ end
     S = rand(100, 100); S[:, 40] .= 0
     @test_throws SingularException RFLUAMD.inv!(RFLUAMD.lu(S; check = false))
 end
+@testset "RFLUAMD complex inv! / det / logabsdet from the factors" begin
+    RFLUAMD.GPU_MIN_N[] = 64
+    for _p in (true, false), T in (ComplexF64, ComplexF32), n in (64, 65, 300, 1000)
+        R = real(T)
+        A = rand(T, n, n) .- T(0.5 + 0.5im) + T(n) * I
+        F = RFLUAMD.lu(A, Val(_p))
+        la, sg = RFLUAMD.logabsdet(F)
+        la0, sg0 = logabsdet(ComplexF64.(A))
+        @test abs(sg - sg0) <= 16n * eps(R) && abs(la - la0) <= 8n * eps(R)
+        @test RFLUAMD.det(F) ≈ det(F)
+        X = RFLUAMD.inv!(F)                                   # F is invalid from here on
+        @test opnorm(A * X - I, 1) <= n * eps(R) * opnorm(A, 1) * opnorm(X, 1)
+        @test opnorm(X * A - I, 1) <= n * eps(R) * opnorm(A, 1) * opnorm(X, 1)
+    end
+    S = rand(ComplexF64, 130, 130); S[:, 70] .= 0
+    @test_throws SingularException RFLUAMD.inv!(RFLUAMD.lu(S; check = false))
+end
 # The batched entries take DEVICE pointers, so this block needs AMDGPU.jl for the buffers (not a dependency of the package: skipped
 # when it is not installed).  4096 systems of order 32, packed column-major: pivots and info against LAPACK, the reference's solve bound.
 if Base.find_package("AMDGPU") !== nothing

@@ -20,9 +20,13 @@ from .lu import (  # noqa: F401
     Val,
     det,
     det_batched,
+    det_complex,
+    det_complex_batched,
     inv,
     inv_,
     inv_batched,
+    inv_complex,
+    inv_complex_,
     last_path,
     ldiv_,
     ldiv_batched_,
@@ -33,7 +37,10 @@ from .lu import (  # noqa: F401
     ldiv_mixed,
     logabsdet,
     logabsdet_batched,
+    logabsdet_complex,
+    logabsdet_complex_batched,
     logdet,
+    logdet_complex,
     lu,
     lu_,
     lu_batched,
@@ -62,5 +69,6 @@ __all__ = [
     "lu_complex", "lu_complex_", "ldiv_complex_", "ldiv_complex_adjoint_", "ldiv_complex_transpose_",
     "lu_complex_batched", "lu_complex_batched_", "ldiv_complex_batched_",
     "inv", "inv_", "det", "logabsdet", "logdet", "inv_batched", "logabsdet_batched", "det_batched",
+    "inv_complex", "inv_complex_", "det_complex", "logabsdet_complex", "logdet_complex", "logabsdet_complex_batched", "det_complex_batched",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

@@ -96,6 +96,12 @@ _COMPLEX = {
     "rflu_gemm_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64]),
     "rflu_getrf_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_int, c_p]),
     "rflu_getrs_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int]),
+    # inv! / logabsdet from complex factors: the sign is a complex number, so it comes back as two doubles (batched: (re, im) pairs)
+    "rflu_getri_{s}_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "rflu_getri_{s}": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "rflu_logabsdet_{s}_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "rflu_logabsdet_{s}": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "rflu_logabsdet_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
 }
 
 EXPORTS = dict(_PLAIN)

@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(256) claswp_rev_kernel(R* __restrict__ A, int6
 }
 
 template <typename R>
-static int launch_claswp_rev(Handle* h, R* A, int64_t rs, int64_t cs, int64_t rows, int64_t ncols, const int64_t* ipiv)
+int launch_claswp_rev(Handle* h, R* A, int64_t rs, int64_t cs, int64_t rows, int64_t ncols, const int64_t* ipiv)
 {
     ProfScope ps(h, RFLU_K_LASWP, 8.0 * sizeof(R) * (double)ncols * (double)rows);
     hipLaunchKernelGGL(claswp_rev_kernel<R>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, h->stream, A, rs, cs, rows, ncols, ipiv,
@@ -304,5 +304,7 @@ int cgetrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t 
 
 template int cgetrs_trans_cm_dev<double>(Handle*, int64_t, int64_t, const double*, int64_t, const int64_t*, double*, int64_t, int);
 template int cgetrs_trans_cm_dev<float>(Handle*, int64_t, int64_t, const float*, int64_t, const int64_t*, float*, int64_t, int);
+template int launch_claswp_rev<double>(Handle*, double*, int64_t, int64_t, int64_t, int64_t, const int64_t*);
+template int launch_claswp_rev<float>(Handle*, float*, int64_t, int64_t, int64_t, int64_t, const int64_t*);
 
 }  // namespace rflu

@@ -782,7 +782,7 @@ static Handle* H(rflu_handle_t h) { return reinterpret_cast<Handle*>(h); }
 
 extern "C" {
 
-int rflu_version(void) { return 105; }
+int rflu_version(void) { return 106; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -1259,6 +1259,36 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
         CHECK_HANDLE(handle);                                                                                         \
         return cgetrs_batched<R>(H(handle), batch, n, nrhs, F, lda, strideF, row_major, ipiv, stride_ipiv, B, ldb,    \
                                  strideB, trans);                                                                     \
+    }                                                                                                                 \
+    int rflu_getri_##SFX##_dev(rflu_handle_t handle, int64_t n, R* F, int64_t lda, const int64_t* ipiv, int64_t* info) \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetri_cm_dev<R>(H(handle), n, F, lda, ipiv, info);                                                    \
+    }                                                                                                                 \
+    int rflu_getri_##SFX(rflu_handle_t handle, int64_t n, R* F, int64_t lda, const int64_t* ipiv, int64_t* info)      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetri_host<R>(H(handle), n, F, lda, ipiv, info);                                                      \
+    }                                                                                                                 \
+    int rflu_logabsdet_##SFX##_dev(rflu_handle_t handle, int64_t n, const R* F, int64_t ld, const int64_t* ipiv,      \
+                                   double* logabs_out, double* sign_re_out, double* sign_im_out)                      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return clogabsdet_dev<R>(H(handle), n, F, ld, ipiv, logabs_out, sign_re_out, sign_im_out);                    \
+    }                                                                                                                 \
+    int rflu_logabsdet_##SFX(rflu_handle_t handle, int64_t n, const R* F, int64_t ld, const int64_t* ipiv,            \
+                             double* logabs_out, double* sign_re_out, double* sign_im_out)                            \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return clogabsdet_host<R>(H(handle), n, F, ld, ipiv, logabs_out, sign_re_out, sign_im_out);                   \
+    }                                                                                                                 \
+    int rflu_logabsdet_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, const R* F, int64_t lda,   \
+                                           int64_t strideF, const int64_t* ipiv, int64_t stride_ipiv,                 \
+                                           double* logabs_dev, double* sign_dev)                                      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return clogabsdet_batched_dev<R>(H(handle), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs_dev,         \
+                                         sign_dev);                                                                   \
     }
 DEFINE_COMPLEX(cf64, double)
 DEFINE_COMPLEX(cf32, float)

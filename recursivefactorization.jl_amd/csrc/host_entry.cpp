@@ -486,6 +486,46 @@ int cgetrs_trans_host(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t ld
     return RFLU_OK;
 }
 
+// inv!(F) and logabsdet from complex host factors: as getri_host / logabsdet_host (the diagonal and ipiv travel alone for the latter)
+template <typename R>
+int cgetri_host(Handle* h, int64_t n, R* F, int64_t lda, const int64_t* ipiv, int64_t* info)
+{
+    typedef HostCx<R> Z;
+    RFLU_TRY(cgetri_check_args(n, F, lda, info));
+    *info = 0;
+    if (n == 0) return RFLU_OK;
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(Z)));
+    Z* dF = static_cast<Z*>(h->hostA_dev);
+    const int64_t* dipiv;
+    RFLU_TRY(copy_in(dF, reinterpret_cast<const Z*>(F), lda, n, n, h->stream));
+    RFLU_TRY(stage_ipiv(h, ipiv, n, &dipiv));
+    RFLU_TRY(cgetri_cm_dev<R>(h, n, reinterpret_cast<R*>(dF), n, dipiv, info));
+    if (*info != 0) return RFLU_OK;   // F stays as it is
+    RFLU_TRY(copy_out(reinterpret_cast<Z*>(F), lda, dF, n, n, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+template <typename R>
+int clogabsdet_host(Handle* h, int64_t n, const R* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign_re, double* sign_im)
+{
+    typedef HostCx<R> Z;
+    RFLU_TRY(clogabsdet_check_args(n, F, ld, logabs, sign_re, sign_im));
+    *logabs = 0.0;
+    *sign_re = 1.0;
+    *sign_im = 0.0;
+    if (n == 0) return RFLU_OK;
+    const Z* Fz = reinterpret_cast<const Z*>(F);
+    std::vector<Z> diag((size_t)n);
+    for (int64_t i = 0; i < n; ++i) diag[(size_t)i] = Fz[i * (ld + 1)];
+    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * sizeof(Z)));
+    const int64_t* dipiv;
+    RFLU_HIP(hipMemcpyAsync(h->hostB_dev, diag.data(), (size_t)n * sizeof(Z), hipMemcpyHostToDevice, h->stream));
+    RFLU_TRY(stage_ipiv(h, ipiv, n, &dipiv));
+    RFLU_HIP(hipStreamSynchronize(h->stream));   // `diag` is pageable and leaves scope
+    return launch_clogabsdet<R>(h, n, static_cast<const R*>(h->hostB_dev), 1, dipiv, logabs, sign_re, sign_im, nullptr);
+}
+
 #define RFLU_INSTANTIATE_HOST(T)                                                                                                      \
     template int getrf_host<T>(Handle*, int64_t, int64_t, T*, int64_t, int64_t*, int, int64_t, int64_t*);                             \
     template int getrs_host<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t, bool);                      \
@@ -496,7 +536,9 @@ RFLU_INSTANTIATE_HOST(float)
 #define RFLU_INSTANTIATE_HOST_COMPLEX(R)                                                                                              \
     template int cgetrf_host<R>(Handle*, int64_t, int64_t, R*, int64_t, int64_t*, int, int64_t*);                                     \
     template int cgetrs_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t);                           \
-    template int cgetrs_trans_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t, int);
+    template int cgetrs_trans_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t, int);             \
+    template int cgetri_host<R>(Handle*, int64_t, R*, int64_t, const int64_t*, int64_t*);                                             \
+    template int clogabsdet_host<R>(Handle*, int64_t, const R*, int64_t, const int64_t*, double*, double*, double*);
 RFLU_INSTANTIATE_HOST_COMPLEX(double)
 RFLU_INSTANTIATE_HOST_COMPLEX(float)
 

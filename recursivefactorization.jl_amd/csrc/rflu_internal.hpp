@@ -242,6 +242,7 @@ struct Handle {
     bool gemm_attr_set[2] = {false, false};   // dynamic-LDS opt-in of the GEMM kernels done on this handle's device (f64, f32)
     bool eng_attr_set[2] = {false, false};    // same for the persistent update engine (engine.hip)
     bool batched_attr_set[3][4] = {};         // same for the batched kernels (batched_kernels.hpp): [getrf|getrs|getri][f64, f32, cf64, cf32]
+    bool cinv_attr_set[2] = {false, false};   // same for the 64x64 triangular inverses of the complex getri (complex_inverse.hip): [cf64, cf32]
     void* eng_state = nullptr;                // device: EngState (engine.hpp)
     void* eng_host = nullptr;                 // pinned host image of its initial value
     long long* eng_trace_buf = nullptr;       // device: RFLU_ENGINE_TRACE stamps + workgroup-time accounting (measurement only)

@@ -634,6 +634,135 @@ def logdet(F, *, handle=None) -> float:
     return la
 
 
+def _complex_trans(F, trans, what: str):
+    """The plain factorization and which of the three matrices is meant: "N" (A), "T" (transpose(A)) or "C" (A', the conjugate
+    transpose) -- LAPACK's letters, as in ``ldiv_complex_batched_``.  ``Transpose is Adjoint`` in this package, so a wrapper cannot say
+    "T"; ``Adjoint(F)`` means "C" and takes no ``trans`` besides the default."""
+    if not isinstance(trans, str) or trans not in _CBATCHED_TRANS:
+        raise ValueError(f'{what}: trans must be "N", "T" or "C", got {trans!r}')
+    if isinstance(F, Adjoint):
+        F = F.parent
+        if isinstance(F, Adjoint):
+            raise TypeError(f"{what} of a doubly wrapped factorization: unwrap it first")
+        if trans != "N":
+            raise ValueError(f'{what}: Adjoint(F) already means trans="C": pass the plain factorization together with trans')
+        trans = "C"
+    return F, trans
+
+
+def _complex_square_factors(F, what: str):
+    """``_square_factors`` for the complex functions -- before anything touches the library.  Returns (A, n, sfx, kind, ld) with kind
+    "cm" (a column-major CUDA tensor) or "host" (a column-major NumPy array)."""
+    if not isinstance(F, LU):
+        raise TypeError(f"{what} needs the LU that lu_complex / lu_complex_ returned")
+    A = F.factors
+    if A is None:
+        raise ValueError(f"{what}: this factorization is no longer valid (inv_complex_ overwrote its factors with the inverse)")
+    if getattr(A, "ndim", None) != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError(f"{what} needs a square factorization")
+    name = str(A.dtype).replace("torch.", "")
+    if name not in ("complex128", "complex64"):
+        raise TypeError(f"{what} serves ComplexF64/ComplexF32 factors only (got {A.dtype}); real factors go to inv / inv_ / det / "
+                        "logabsdet / logdet")
+    sfx = "cf64" if name == "complex128" else "cf32"
+    n = int(A.shape[0])
+    if _is_torch(A):
+        if not A.is_cuda:
+            raise _ffi.RfluError("torch factors must live on the MI355X (device='cuda'); host data goes in as NumPy")
+        if not isinstance(F.ipiv, NotIPIV) and not (_is_torch(F.ipiv) and F.ipiv.is_cuda and str(F.ipiv.dtype) == "torch.int64"
+                                                      and F.ipiv.numel() >= n and (n <= 1 or F.ipiv.stride(0) == 1)):
+            raise TypeError("ipiv of GPU factors must be a contiguous int64 CUDA tensor of length n (or NotIPIV)")
+        if n <= 1 or (A.stride(0) == 1 and A.stride(1) >= n):
+            return A, n, sfx, "cm", (int(A.stride(1)) if n > 1 else 1)
+        raise ValueError(f"{what}: the complex path is column-major only: the factors must be a column-major tensor (stride(0) == 1), as "
+                         "lu_complex_ leaves them; row-major complex factors are not served")
+    if not isinstance(A, np.ndarray):
+        raise TypeError("factors must be a numpy.ndarray or a CUDA torch.Tensor")
+    if not A.flags.f_contiguous:
+        raise ValueError(f"{what}: the complex path is column-major only: host factors must be Fortran-ordered, as lu_complex_ leaves them")
+    return A, n, sfx, "host", max(n, 1)
+
+
+def _complex_view(X, trans: str):
+    if trans == "N":
+        return X
+    if trans == "T":
+        return X.T
+    return X.T.conj()   # torch: a lazy conjugate view; NumPy has no such view, so a conjugated copy of the transposed view
+
+
+def inv_complex_(F, *, trans="N", handle=None):
+    """``LinearAlgebra.inv!(F::LU)`` for ``complex128`` / ``complex64`` factors: overwrite them with ``inv(A)`` (``rflu_getri_cf64`` /
+    ``_cf32`` and their ``_dev`` forms) and return the array that held them.  About 4n^3/3 complex multiply-adds and no n x n workspace,
+    against 2n^3 and an n x n identity for ``ldiv_complex_(F, I)``.
+
+    ``F`` IS INVALID AFTERWARDS, exactly as after ``inv_``: ``F.factors`` is set to ``None``; use ``inv_complex`` to keep it.  The
+    factors: a column-major CUDA tensor or a Fortran-ordered NumPy array; row-major complex factors are refused (the complex path is
+    column-major only).  Raises ``SingularException(info)`` when ``F.info != 0`` or the library finds a ``u_ii`` with both parts zero
+    -- the factors are then untouched and ``F`` stays valid.
+
+    For complex matrices the adjoint and the transpose differ, and ``Transpose is Adjoint`` in this package, so which one is meant is
+    said in LAPACK's letters as in ``ldiv_complex_batched_``: ``trans="T"`` returns the transposed view of the result
+    (inv(transpose(A)) = transpose(inv(A))), ``trans="C"`` -- or ``Adjoint(F)`` -- the conjugate-transposed one (inv(A') = inv(A)')."""
+    F, trans = _complex_trans(F, trans, "inv_complex_")
+    A, n, sfx, kind, ld = _complex_square_factors(F, "inv_complex_")
+    if F.info != 0:
+        raise SingularException(abs(F.info))
+    if n > 0:
+        keep, ip = _ipiv_arg(F, kind)
+        h, ap = _handle_for(A, kind, handle)
+        info = ctypes.c_int64(0)
+        h.call(f"rflu_getri_{sfx}" + ("" if kind == "host" else "_dev"), n, ap, ld, ip, ctypes.byref(info))
+        del keep
+        if info.value != 0:
+            raise SingularException(int(info.value))
+    F.factors = None
+    return _complex_view(A, trans)
+
+
+def inv_complex(F, *, trans="N", handle=None):
+    """``inv(F::LU)`` for complex factors: ``inv_complex_`` on a copy of the factors; ``F`` stays intact.  ``trans`` / ``Adjoint(F)`` as
+    there."""
+    G, trans = _complex_trans(F, trans, "inv_complex")
+    A = _complex_square_factors(G, "inv_complex")[0]
+    C = A.clone() if _is_torch(A) else np.array(A, order="F", copy=True)
+    return _complex_view(inv_complex_(LU(C, G.ipiv, G.info), handle=handle), trans)
+
+
+def logabsdet_complex(F, *, trans="N", handle=None):
+    """``logabsdet(F::LU)`` for complex factors -> ``(log|det A|, det A / |det A|)`` as a Python ``float`` and ``complex``
+    (``rflu_logabsdet_cf64`` / ``_cf32`` and their ``_dev`` forms): the sum of ``log(hypot(re, im))`` over the diagonal and the product of
+    its unit phases times the parity of the interchanges, in Float64 and in a fixed order for both element types.  Only the diagonal and
+    ``ipiv`` are read.  A ``u_ii`` with both parts zero gives ``(-inf, 0j)``, a NaN ``(nan, nan+nanj)``; ``n == 0`` gives ``(0.0, 1+0j)``.
+    ``trans="T"``: the same value (det(transpose(A)) = det(A)); ``trans="C"`` or ``Adjoint(F)``: the conjugate phase (det(A') is the
+    conjugate of det(A))."""
+    F, trans = _complex_trans(F, trans, "logabsdet_complex")
+    A, n, sfx, kind, ld = _complex_square_factors(F, "logabsdet_complex")
+    if n == 0:
+        return 0.0, complex(1.0, 0.0)
+    keep, ip = _ipiv_arg(F, kind)
+    h, ap = _handle_for(A, kind, handle)
+    la, sr, si = ctypes.c_double(0.0), ctypes.c_double(1.0), ctypes.c_double(0.0)
+    h.call(f"rflu_logabsdet_{sfx}" + ("" if kind == "host" else "_dev"), n, ap, ld, ip, ctypes.byref(la), ctypes.byref(sr), ctypes.byref(si))
+    del keep
+    sign = complex(sr.value, si.value)
+    return float(la.value), (sign.conjugate() if trans == "C" else sign)
+
+
+def det_complex(F, *, trans="N", handle=None) -> complex:
+    """``det(F::LU)`` for complex factors = ``sign * exp(logabs)`` of ``logabsdet_complex``; ``0j`` for a singular ``F``."""
+    la, sg = logabsdet_complex(F, trans=trans, handle=handle)
+    with np.errstate(over="ignore"):
+        return complex(0.0, 0.0) if sg == 0 else sg * float(np.exp(np.float64(la)))
+
+
+def logdet_complex(F, *, trans="N", handle=None) -> complex:
+    """``logdet(F::LU)`` for complex factors: ``complex(logabs, angle(sign))`` of ``logabsdet_complex`` (Julia's ``log(det(F))`` on its
+    principal branch; no domain error, a complex logarithm has none)."""
+    la, sg = logabsdet_complex(F, trans=trans, handle=handle)
+    return complex(la, float(np.angle(sg)))
+
+
 class NotConvergedError(ArithmeticError):
     """``ldiv_mixed(..., fallback=False)``: the refinement did not reach Float64 backward error within ``max_iter`` steps."""
 
@@ -1054,6 +1183,47 @@ def ldiv_complex_batched_(F, B, *, trans="N", check=True, handle=None):
             raise ValueError('Adjoint(F) already means trans="C": pass the plain BatchedLU together with trans')
         trans = "C"
     return _ldiv_batched_call(F, B, _CBATCHED_TRANS[trans], check, handle, "ldiv_complex_batched_", "lu_complex_batched_", _cbatched_sfx)
+
+
+def logabsdet_complex_batched(F, *, trans="N", handle=None):
+    """``logabsdet_complex`` of every matrix of the ``BatchedLU`` that ``lu_complex_batched_`` returned
+    (``rflu_logabsdet_batched_cf64_dev`` / ``_cf32_dev``, one launch, any n, both orientations of the factors -- only diagonals are
+    read): ``(logabs, sign)``, a Float64 and a ``complex128`` CUDA tensor of length ``batch``; entry b is bit-identical to
+    ``logabsdet_complex`` on matrix b's factors.  ``trans`` / ``Adjoint(F)`` as in ``logabsdet_complex``."""
+    F, trans = _complex_trans(F, trans, "logabsdet_complex_batched")
+    if not isinstance(F, BatchedLU):
+        raise TypeError("logabsdet_complex_batched needs the BatchedLU that lu_complex_batched_ returned")
+    A = F.factors
+    if not (_is_torch(A) and A.is_cuda) or A.ndim != 3:
+        raise TypeError("logabsdet_complex_batched: the factors must be a 3-D CUDA tensor")
+    if A.shape[1] != A.shape[2]:
+        raise ValueError("logabsdet_complex_batched needs square factorizations")
+    sfx = _cbatched_sfx(A.dtype, "logabsdet_complex_batched")
+    row_major, ld, stride_f = _batched_layout(A, "logabsdet_complex_batched")
+    import torch
+
+    batch, n = int(A.shape[0]), int(A.shape[1])
+    la = torch.zeros(batch, dtype=torch.float64, device=A.device)
+    sg = torch.zeros((batch, 2), dtype=torch.float64, device=A.device)
+    sg[:, 0] = 1.0
+    if batch > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        nopiv = isinstance(F.ipiv, NotIPIV)
+        stride_ip = 0 if nopiv else (int(F.ipiv.stride(0)) if batch > 1 else max(n, 1))
+        h.call(f"rflu_logabsdet_batched_{sfx}_dev", batch, n, ctypes.c_void_p(A.data_ptr()), ld, stride_f,
+               ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), stride_ip, ctypes.c_void_p(la.data_ptr()), ctypes.c_void_p(sg.data_ptr()))
+    sign = torch.view_as_complex(sg)
+    return la, (sign.conj().resolve_conj() if trans == "C" else sign)
+
+
+def det_complex_batched(F, *, trans="N", handle=None):
+    """``det_complex`` of every matrix of a complex batch: ``sign * exp(logabs)`` of ``logabsdet_complex_batched`` (0 for a singular
+    matrix), a ``complex128`` CUDA tensor of length ``batch``."""
+    import torch
+
+    la, sg = logabsdet_complex_batched(F, trans=trans, handle=handle)
+    return torch.where(sg == 0, torch.zeros_like(sg), sg * torch.exp(la))
 
 
 def last_path(device: int = 0) -> str:
