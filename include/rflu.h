@@ -319,7 +319,8 @@ int rflu_getrs_trans_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, con
  *     b*stride_ipiv); logabs_dev: DEVICE array of `batch` doubles, sign_dev: DEVICE array of `batch` interleaved (re, im) pairs.  One
  *     launch, one workgroup per matrix, any n (only diagonals are read, so it serves both orientations of rflu_getrf_batched_c*'s
  *     factors); bit-identical to the single-matrix entry on the same factors.
- * Not here: a batched complex getri, row-major complex factors, complex mixed precision. */
+ * The batched inverse is rflu_getri_batched_c*_dev in the BATCHED COMPLEX block below.  Not here: row-major complex factors of a
+ * single matrix, complex mixed precision. */
 int rflu_getri_cf64_dev(rflu_handle_t handle, int64_t n, double* F_dev, int64_t lda, const int64_t* ipiv_dev, int64_t* info);
 int rflu_getri_cf32_dev(rflu_handle_t handle, int64_t n, float* F_dev, int64_t lda, const int64_t* ipiv_dev, int64_t* info);
 int rflu_getri_cf64(rflu_handle_t handle, int64_t n, double* F_host, int64_t lda, const int64_t* ipiv_host, int64_t* info);
@@ -355,7 +356,25 @@ int rflu_logabsdet_batched_cf32_dev(rflu_handle_t handle, int64_t batch, int64_t
  *   - above that limit a COLUMN-MAJOR batch is looped over the single-matrix complex device path (rflu_getrf_c*_dev, rflu_getrs_c*_dev /
  *     rflu_getrs_trans_c*_dev), each matrix's info written into info_dev: correct, NOT fast, no size cliff, and rflu_last_path reports
  *     what that path reports.  A ROW-MAJOR batch above the limit is RFLU_ERR_ARG with a message that says so: the single-matrix
- *     complex path is column-major only. */
+ *     complex path is column-major only;
+ *   - rflu_getri_batched_c*: Ainv_b <- inv(op(A_b)) from the factors, op by trans = 0 (A), 1 (transpose(A), LAPACK 'T') or 2 (A', LAPACK
+ *     'C'); any other value is RFLU_ERR_ARG.  The contract is that of rflu_getri_batched_f64_dev: out of place (Ainv must not overlap F;
+ *     F and ipiv are only read), Ainv in the ORIENTATION OF F with its own ldi >= n / strideI in complex elements, ipiv NULL = NotIPIV,
+ *     info_dev (device, batch entries, required): 0 or the 1-based index of the first u_ii with BOTH parts zero (one zero part is not
+ *     singular), whose output is then Inf/NaN in its own matrix only; batch == 0 or n == 0 succeed with nothing launched.  ONE launch
+ *     up to n <= 64 (ComplexF64) / n <= 128 (ComplexF32): the factors in LDS once, the columns of P * I made in LDS and never read
+ *     from HBM, one reciprocal per u_ii and then multiplies; since inv(transpose(A)) = transpose(inv(A)), the three values of trans
+ *     share every flop and differ only in how the result is stored (and 'C' in the sign of the imaginary part), so the 'T' result IS
+ *     the transposed 'N' result bit for bit.  Above the limit a COLUMN-MAJOR batch is looped: a device copy of F_b into Ainv_b, the
+ *     single-matrix rflu_getri_c*_dev in place, a singular matrix's output filled with NaN, and for trans != 0 one layout change of the
+ *     result through an n x n buffer of the handle -- correct, NOT fast; a ROW-MAJOR batch above the limit is RFLU_ERR_ARG (the
+ *     single-matrix complex path is column-major only). */
+int rflu_getri_batched_cf64_dev(rflu_handle_t handle, int64_t batch, int64_t n, const double* F_dev, int64_t lda, int64_t strideF,
+                                int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, double* Ainv_dev, int64_t ldi,
+                                int64_t strideI, int trans, int64_t* info_dev);
+int rflu_getri_batched_cf32_dev(rflu_handle_t handle, int64_t batch, int64_t n, const float* F_dev, int64_t lda, int64_t strideF,
+                                int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* Ainv_dev, int64_t ldi,
+                                int64_t strideI, int trans, int64_t* info_dev);
 int rflu_getrf_batched_cf64_dev(rflu_handle_t handle, int64_t batch, int64_t m, int64_t n, double* A_dev, int64_t lda, int64_t strideA,
                                 int row_major, int64_t* ipiv_dev, int64_t stride_ipiv, int pivot, int64_t* info_dev);
 int rflu_getrf_batched_cf32_dev(rflu_handle_t handle, int64_t batch, int64_t m, int64_t n, float* A_dev, int64_t lda, int64_t strideA,

@@ -586,6 +586,26 @@ function logabsdet_batched_dev!(logabs::Ptr{Float64}, sign::Ptr{ComplexF64}, F::
     return nothing
 end
 
+# the batched complex inverse (rflu_getri_batched_cf64_dev / _cf32_dev, csrc/batched_complex.hip): the real methods' arguments and a
+# trailing `trans`: Ainv_b <- inv(A_b) ('N'), inv(transpose(A_b)) ('T') or inv(A_b') ('C'), out of place in the orientation of `F`
+function getri_batched_dev!(Ainv::Ptr{ComplexF64}, ldi::Integer, strideI::Integer, F::Ptr{ComplexF64}, batch::Integer, n::Integer, lda::Integer,
+                            strideF::Integer, row_major::Bool, ipiv::Ptr{Int64}, stride_ipiv::Integer, info::Ptr{Int64}, trans::AbstractChar)
+    st = ccall((:rflu_getri_batched_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Int64}),
+               handle(), batch, n, reinterpret(Ptr{Float64}, F), lda, strideF, Cint(row_major), ipiv, stride_ipiv, reinterpret(Ptr{Float64}, Ainv), ldi, strideI, batched_trans_code(trans), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return Ainv
+end
+
+function getri_batched_dev!(Ainv::Ptr{ComplexF32}, ldi::Integer, strideI::Integer, F::Ptr{ComplexF32}, batch::Integer, n::Integer, lda::Integer,
+                            strideF::Integer, row_major::Bool, ipiv::Ptr{Int64}, stride_ipiv::Integer, info::Ptr{Int64}, trans::AbstractChar)
+    st = ccall((:rflu_getri_batched_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Int64}, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Int64}),
+               handle(), batch, n, reinterpret(Ptr{Float32}, F), lda, strideF, Cint(row_major), ipiv, stride_ipiv, reinterpret(Ptr{Float32}, Ainv), ldi, strideI, batched_trans_code(trans), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return Ainv
+end
+
 # ---- dispatch: who serves a call (RecursiveFactorization src/lu.jl:92-93, 114-126) -------------------------------------------
 const GPUEltype = Union{Float32, Float64}                                  # every entry serves these
 const GPUAnyEltype = Union{Float32, Float64, ComplexF32, ComplexF64}       # lu! and ldiv!(F, B) serve the complex types as well

@@ -141,6 +141,34 @@ if Base.find_package("AMDGPU") !== nothing
             end
         end
     end
+    # complex batched inverse: one launch, the three letters, a singular matrix alone with its info
+    @testset "RFLUAMD complex batched getri ($T)" for T in (ComplexF64, ComplexF32)
+        n, batch = 32, 1024
+        A = rand(T, n, n, batch); A[:, 5, 7] .= 0
+        dA, dX = ROCArray(A), ROCArray(zeros(T, n, n, batch))
+        dipiv, dinfo = ROCArray(zeros(Int64, n, batch)), ROCArray(fill(Int64(-1), batch))
+        GC.@preserve dA dipiv dinfo begin
+            RFLUAMD.getrf_batched_dev!(Ptr{T}(UInt(pointer(dA))), batch, n, n, n, n * n, false, Ptr{Int64}(UInt(pointer(dipiv))), n, true,
+                                       Ptr{Int64}(UInt(pointer(dinfo))))
+        end
+        F = Array(dA)
+        for (trans, op) in (('N', identity), ('T', transpose), ('C', adjoint))
+            GC.@preserve dA dX dipiv dinfo begin
+                RFLUAMD.getri_batched_dev!(Ptr{T}(UInt(pointer(dX))), n, n * n, Ptr{T}(UInt(pointer(dA))), batch, n, n, n * n, false,
+                                           Ptr{Int64}(UInt(pointer(dipiv))), n, Ptr{Int64}(UInt(pointer(dinfo))), trans)
+                @test RFLUAMD.last_path() == 5
+            end
+            X, info = Array(dX), Array(dinfo)
+            @test info[7] == 5 && count(!iszero, info) == 1
+            @test !all(isfinite, X[:, :, 7])
+            @test Array(dA) == F                                   # the factors are only read
+            for k in (1, 2, 1000, batch)
+                M = op(A[:, :, k])
+                @test all(isfinite, X[:, :, k])
+                @test opnorm(M * X[:, :, k] - I, 1) < 1000n * eps(real(T)) * opnorm(M, 1) * opnorm(X[:, :, k], 1)
+            end
+        end
+    end
     # mixed precision: Float32 factors, Float64 refinement; A and b untouched, dsgesv's rule met, the residual kernel alone
     @testset "RFLUAMD mixed-precision solve" begin
         n, nrhs = 1000, 9

@@ -27,6 +27,7 @@ from .lu import (  # noqa: F401
     inv_batched,
     inv_complex,
     inv_complex_,
+    inv_complex_batched,
     last_path,
     ldiv_,
     ldiv_batched_,
@@ -70,5 +71,6 @@ __all__ = [
     "lu_complex_batched", "lu_complex_batched_", "ldiv_complex_batched_",
     "inv", "inv_", "det", "logabsdet", "logdet", "inv_batched", "logabsdet_batched", "det_batched",
     "inv_complex", "inv_complex_", "det_complex", "logabsdet_complex", "logdet_complex", "logabsdet_complex_batched", "det_complex_batched",
+    "inv_complex_batched",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

@@ -102,6 +102,8 @@ _COMPLEX = {
     "rflu_logabsdet_{s}_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "rflu_logabsdet_{s}": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "rflu_logabsdet_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
+    # the batched inverse: the real entry's arguments with `trans` (0 / 1 / 2) before info_dev
+    "rflu_getri_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p]),
 }
 
 EXPORTS = dict(_PLAIN)

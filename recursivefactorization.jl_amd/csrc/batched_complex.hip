@@ -33,6 +33,8 @@
 // a complex division per right-hand side and thread would cost more than the whole rank-1 step it feeds, and the extra rounding
 // (a few eps per element) is far inside the 20 n eps backward-error bar of the tests.  A zero on the diagonal gives Inf / NaN in that
 // matrix's own right-hand sides only.
+// Inverse (cgetri_batched_kernel, at the end of the file): the forward solve on the columns of P * I made in LDS;
+// inv(transpose(A)) and inv(A') come from the store alone.
 // Geometry, the DPP maximum and the launch are shared with batched.hip: batched_kernels.hpp.
 #include "complex_dev.hpp"
 #include "batched_kernels.hpp"
@@ -390,5 +392,130 @@ template int launch_cgetrs_batched<double>(Handle*, int64_t, int64_t, int64_t, c
                                            double*, int64_t, int64_t, int);
 template int launch_cgetrs_batched<float>(Handle*, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, int, const int64_t*, int64_t,
                                           float*, int64_t, int64_t, int);
+
+// ---- the batched inverse.  It stands behind everything above on purpose: the two kernels above keep their
+// place in the code object, and moved code alone has cost them up to 2.5 % before (profiles/batched_unified_ab.txt).
+namespace {
+
+template <typename R>
+struct CInvArgs {
+    const Cx<R>* F;
+    const int64_t* ipiv;
+    Cx<R>* Ainv;
+    int64_t* info;
+    int64_t lda, strideF, stride_ipiv, ldi, strideI, batch;
+    int n, row_major, trans;
+    BGeo g;
+};
+
+// cgetrs_batched_kernel's forward solve (cbsubstitute<R, 0>, unchanged) on the columns of P * I, which are made in LDS -- row i of a
+// pass is {1, 0} in column sperm[i] -- and never read from HBM; info from the diagonal held in LDS.  Ainv holds inv(op(A)) in the
+// orientation of the factors, and op costs nothing: inv(A^T) = (A^-1)^T, and a transposed column-major store has the addresses of a
+// plain row-major one, so 'T' (trans = 1) takes the OTHER of the two store branches and 'C' (trans = 2) also negates the imaginary
+// part as the element leaves LDS.  The lanes run along the contiguous direction of the output in all six combinations.
+template <typename R>
+__global__ void __launch_bounds__(BT) cgetri_batched_kernel(CInvArgs<R> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char cbsmem[];
+    const BGeo g = a.g;
+    const int n = a.n;
+    const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1), lane = t & 63;
+    const int64_t b = (int64_t)blockIdx.x * (BT >> g.tpm_log) + grp;
+    const bool valid = b < a.batch;
+    unsigned char* base = cbsmem + (size_t)grp * g.group_bytes;
+    const CImage<R> S{reinterpret_cast<typename CVec<R>::type*>(base), g.ld};
+    const CImage<R> X{reinterpret_cast<typename CVec<R>::type*>(base + g.off_x), g.ld};
+    const CImage<R> D{reinterpret_cast<typename CVec<R>::type*>(base + g.off_a), 0};   // [n]: reciprocal of the diagonal
+    int* sperm = reinterpret_cast<int*>(base + g.off_b);   // [n]: row i of P*I is row sperm[i] of I
+    const int64_t bb = valid ? b : 0;
+    const Cx<R>* F = a.F + bb * a.strideF;
+    Cx<R>* Y = a.Ainv + bb * a.strideI;
+
+    cbload_matrix<R>(S, F, a.lda, a.row_major, n, n, g, t, valid);
+    if (t < 64) {
+        // the interchanges composed into one permutation, as in cgetrs_batched_kernel
+        int p0 = lane, p1 = lane + 64, i0 = lane, i1 = lane + 64;
+        if (a.ipiv && valid) {
+            const int64_t* ip = a.ipiv + b * a.stride_ipiv;
+            if (lane < n) i0 = (int)(ip[lane] - 1);
+            if (lane + 64 < n) i1 = (int)(ip[lane + 64] - 1);
+        }
+        if (a.ipiv) {
+            for (int k = 0; k < n; ++k) {
+                const int ku = __builtin_amdgcn_readfirstlane(k);
+                int p = ku < 64 ? __builtin_amdgcn_readlane(i0, ku) : __builtin_amdgcn_readlane(i1, ku - 64);
+                if (p <= ku || p >= n) continue;
+                const int vk = ku < 64 ? __builtin_amdgcn_readlane(p0, ku) : __builtin_amdgcn_readlane(p1, ku - 64);
+                const int vp = p < 64 ? __builtin_amdgcn_readlane(p0, p) : __builtin_amdgcn_readlane(p1, p - 64);
+                if (lane == (ku & 63)) { if (ku < 64) p0 = vp; else p1 = vp; }
+                if (lane == (p & 63)) { if (p < 64) p0 = vk; else p1 = vk; }
+            }
+        }
+        if (lane < n) sperm[lane] = p0;
+        if (lane + 64 < n) sperm[lane + 64] = p1;
+    }
+    __syncthreads();
+    if (t < 64 && valid) {   // first u_ii of this matrix with BOTH parts zero
+        bool z0 = false, z1 = false;
+        if (lane < n) { const Cx<R> d = S.get(lane, lane); z0 = d.re == R(0) && d.im == R(0); }
+        if (lane + 64 < n) { const Cx<R> d = S.get(lane + 64, lane + 64); z1 = d.re == R(0) && d.im == R(0); }
+        const bu64 m0 = __ballot(z0), m1 = __ballot(z1);
+        if (lane == 0) a.info[b] = m0 ? (int64_t)__ffsll((long long)m0) : (m1 ? (int64_t)(64 + __ffsll((long long)m1)) : (int64_t)0);
+    }
+    if (t < n) D.put(t, 0, cdiv(Cx<R>{R(1), R(0)}, S.get(t, t)));   // one reciprocal per column for the whole inverse
+    __syncthreads();
+
+    const Cx<R> zero{R(0), R(0)}, one{R(1), R(0)};
+    const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+    const int rr = t & (BNR - 1), ri0 = t >> 3, ris = g.tpm >> 3;   // lanes along a row of the pass
+    const bool by_columns = (a.row_major != 0) == (a.trans != 0);   // the store with the lanes along a column of the pass
+    const bool conj = a.trans == 2;
+    for (int j0 = 0; j0 < n; j0 += BNR) {
+        const int nr = n - j0 < BNR ? n - j0 : BNR;
+        if (r < n) {
+            const int hot = sperm[r] - j0;
+            for (int j = c; j < nr; j += cs) X.put(r, j, (j == hot) ? one : zero);
+        }
+        __syncthreads();
+        cbsubstitute<R, 0>(S, X, D, n, nr, r, c, cs);
+        if (valid) {
+            if (by_columns) {
+                if (r < n)
+                    for (int j = c; j < nr; j += cs) {
+                        Cx<R> z = X.get(r, j);
+                        if (conj) z.im = -z.im;
+                        Y[r + (int64_t)(j0 + j) * a.ldi] = z;
+                    }
+            } else if (rr < nr) {
+                for (int i = ri0; i < n; i += ris) {
+                    Cx<R> z = X.get(i, rr);
+                    if (conj) z.im = -z.im;
+                    Y[(int64_t)i * a.ldi + j0 + rr] = z;
+                }
+            }
+        }
+        __syncthreads();   // the pass has left LDS before the next one is made
+    }
+}
+
+}  // namespace
+
+template <typename R>
+int launch_cgetri_batched(Handle* h, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,
+                          int64_t stride_ipiv, R* Ainv, int64_t ldi, int64_t strideI, int trans, int64_t* info)
+{
+    CInvArgs<R> a;
+    a.F = reinterpret_cast<const Cx<R>*>(F); a.ipiv = ipiv; a.Ainv = reinterpret_cast<Cx<R>*>(Ainv); a.info = info;
+    a.lda = lda; a.strideF = strideF; a.stride_ipiv = stride_ipiv; a.ldi = ldi; a.strideI = strideI; a.batch = batch;
+    a.n = (int)n; a.row_major = row_major; a.trans = trans;
+    a.g = batched_geo(n, n, sizeof(Cx<R>), true, true);
+    return launch_batched(h, 2, 2 + (sizeof(R) == 4), &cgetri_batched_kernel<R>, a, batch, RFLU_K_TRSM, 8.0 * (double)batch * (double)n * (double)n * (double)n,
+                          2.0 * (double)batch * (double)n * (double)n * sizeof(Cx<R>));
+}
+
+template int launch_cgetri_batched<double>(Handle*, int64_t, int64_t, const double*, int64_t, int64_t, int, const int64_t*, int64_t, double*,
+                                           int64_t, int64_t, int, int64_t*);
+template int launch_cgetri_batched<float>(Handle*, int64_t, int64_t, const float*, int64_t, int64_t, int, const int64_t*, int64_t, float*,
+                                          int64_t, int64_t, int, int64_t*);
 
 }  // namespace rflu

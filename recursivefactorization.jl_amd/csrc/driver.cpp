@@ -636,6 +636,62 @@ static int getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_
     return RFLU_OK;
 }
 
+// the complex batched inverse (kernel: batched_complex.hip): Ainv_b <- inv(op(A_b)), op by trans = 0 / 1 / 2.
+// Above the one-launch limit, column-major only: the real loop's steps on the single-matrix complex getri, then for 'T' / 'C' one layout
+// change of the result through the handle's workspace (conjugating for 'C') and a copy back -- correct, not fast.
+template <typename R>
+static int cgetri_batched(Handle* h, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,
+                          int64_t stride_ipiv, R* Ainv, int64_t ldi, int64_t strideI, int trans, int64_t* info_dev)
+{
+    if (batch < 0 || n < 0) {
+        set_error("complex getri_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (trans < 0 || trans > 2) {
+        set_error("complex getri_batched: trans must be 0 (A), 1 (transpose) or 2 (adjoint), got %d", trans);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0 || n == 0) return RFLU_OK;
+    if (F == nullptr || Ainv == nullptr || info_dev == nullptr) { set_error("complex getri_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (lda < n || ldi < n || (batch > 1 && (strideF < (n - 1) * lda + n || strideI < (n - 1) * ldi + n))) {
+        set_error("complex getri_batched: lda=%lld strideF=%lld ldi=%lld strideI=%lld too small for n=%lld", (long long)lda,
+                  (long long)strideF, (long long)ldi, (long long)strideI, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (ipiv && batch > 1 && stride_ipiv < n) {
+        set_error("complex getri_batched: stride_ipiv=%lld < n", (long long)stride_ipiv);
+        return RFLU_ERR_ARG;
+    }
+    if (cbatched_fits<R>(n, n)) {
+        RFLU_TRY(launch_cgetri_batched<R>(h, batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi, strideI, trans, info_dev));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        h->last_path = RFLU_PATH_HIP_BATCHED;
+        return RFLU_OK;
+    }
+    if (row_major) return refuse_large_row_major<R>("complex getri_batched");
+    const size_t esize = 2 * sizeof(R);
+    const int64_t ldw = cworkspace_ld(n);
+    std::vector<int64_t> infos((size_t)batch, 0);
+    for (int64_t b = 0; b < batch; ++b) {
+        R* Xb = Ainv + 2 * b * strideI;
+        RFLU_HIP(hipMemcpy2DAsync(Xb, (size_t)ldi * esize, F + 2 * b * strideF, (size_t)lda * esize, (size_t)n * esize, (size_t)n,
+                                  hipMemcpyDeviceToDevice, h->stream));
+        RFLU_TRY(cgetri_cm_dev<R>(h, n, Xb, ldi, ipiv ? ipiv + b * stride_ipiv : nullptr, &infos[(size_t)b]));
+        if (infos[(size_t)b] != 0) {   // a singular matrix: its output is NaN, as the one-launch path's division by zero leaves it non-finite
+            RFLU_HIP(hipMemset2DAsync(Xb, (size_t)ldi * esize, 0xff, (size_t)n * esize, (size_t)n, h->stream));
+        } else if (trans) {
+            RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldw * esize));
+            R* W = static_cast<R*>(h->work);
+            RFLU_TRY(launch_ctranspose<R>(h, n, n, Xb, ldi, W, ldw, trans == 2));
+            RFLU_HIP(hipMemcpy2DAsync(Xb, (size_t)ldi * esize, W, (size_t)ldw * esize, (size_t)n * esize, (size_t)n, hipMemcpyDeviceToDevice,
+                                      h->stream));
+        }
+    }
+    RFLU_HIP(hipMemcpyAsync(info_dev, infos.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 // ---- mixed precision: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme; kernels: mixed.hip) ----
 // The Float32 factors stay in the row-major layout getrf_rm<float> leaves them in and every solve of the loop is getrs_rm<float> on
 // them: no n x n layout change after the first (getrs_cm_dev would pay one per solve).
@@ -782,7 +838,7 @@ static Handle* H(rflu_handle_t h) { return reinterpret_cast<Handle*>(h); }
 
 extern "C" {
 
-int rflu_version(void) { return 106; }
+int rflu_version(void) { return 107; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -1269,6 +1325,14 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
         return cgetri_host<R>(H(handle), n, F, lda, ipiv, info);                                                      \
+    }                                                                                                                 \
+    int rflu_getri_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, const R* F, int64_t lda,       \
+                                       int64_t strideF, int row_major, const int64_t* ipiv, int64_t stride_ipiv,      \
+                                       R* Ainv, int64_t ldi, int64_t strideI, int trans, int64_t* info_dev)           \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgetri_batched<R>(H(handle), batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi,       \
+                                 strideI, trans, info_dev);                                                           \
     }                                                                                                                 \
     int rflu_logabsdet_##SFX##_dev(rflu_handle_t handle, int64_t n, const R* F, int64_t ld, const int64_t* ipiv,      \
                                    double* logabs_out, double* sign_re_out, double* sign_im_out)                      \

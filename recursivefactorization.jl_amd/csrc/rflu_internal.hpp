@@ -433,6 +433,11 @@ int launch_cgetrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, R* A, 
 template <typename R>
 int launch_cgetrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, const R* F, int64_t lda, int64_t strideF, int row_major,
                           const int64_t* ipiv, int64_t stride_ipiv, R* B, int64_t ldb, int64_t strideB, int trans);
+// the batched complex inverse: Ainv_b <- inv(op(A_b)) from the factors, out of place, Ainv in the orientation of F (op by `trans` as
+// above: the three differ in the store only); info[b] = first u_ii with both parts zero, or 0
+template <typename R>
+int launch_cgetri_batched(Handle* h, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,
+                          int64_t stride_ipiv, R* Ainv, int64_t ldi, int64_t strideI, int trans, int64_t* info);
 
 // the batched inverse: Ainv_b <- A_b^-1 from the factors, out of place, Ainv in the orientation of F; info[b] = first zero u_ii or 0
 template <typename T>

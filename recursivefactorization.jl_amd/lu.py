@@ -1226,6 +1226,50 @@ def det_complex_batched(F, *, trans="N", handle=None):
     return torch.where(sg == 0, torch.zeros_like(sg), sg * torch.exp(la))
 
 
+def inv_complex_batched(F, *, trans="N", check=True, handle=None):
+    """``inv`` of every matrix of the ``BatchedLU`` that ``lu_complex_batched_`` returned (``rflu_getri_batched_cf64_dev`` /
+    ``_cf32_dev``; one launch up to n = 64 for ``complex128`` and n = 128 for ``complex64``, no identity tensor anywhere): returns a NEW
+    dense (batch, n, n) CUDA tensor in the orientation of the factors that holds ``inv(A_b)`` (``trans="N"``), ``inv(transpose(A_b))``
+    (``"T"``) or ``inv(A_b')`` (``"C"``, or ``Adjoint(F)``; LAPACK's letters as in ``ldiv_complex_batched_``).  The three cost the
+    same: the kernel stores the one result transposed, and conjugated for ``"C"``, so what comes back is plain memory and never a lazily
+    conjugated view (``is_conj()`` is false).  ``F`` stays intact.  ``check=True`` raises ``SingularException`` (with ``batch_index``)
+    when some ``F.info`` is non-zero or the library finds a ``u_ii`` with both parts zero; with ``check=False`` only the singular
+    matrices' own inverses come back non-finite.  Larger column-major matrices are looped over the single-matrix complex path, larger
+    row-major ones are refused by the library (that path is column-major only)."""
+    F, trans = _complex_trans(F, trans, "inv_complex_batched")
+    if not isinstance(F, BatchedLU):
+        raise TypeError("inv_complex_batched needs the BatchedLU that lu_complex_batched_ returned")
+    A = F.factors
+    if not (_is_torch(A) and A.is_cuda) or A.ndim != 3:
+        raise TypeError("inv_complex_batched: the factors must be a 3-D CUDA tensor")
+    if A.shape[1] != A.shape[2]:
+        raise ValueError("inv_complex_batched needs square factorizations")
+    sfx = _cbatched_sfx(A.dtype, "inv_complex_batched")
+    row_major, ld, stride_f = _batched_layout(A, "inv_complex_batched")
+    import torch
+
+    nopiv = isinstance(F.ipiv, NotIPIV)
+    if not nopiv and not (_is_torch(F.ipiv) and F.ipiv.is_cuda and F.ipiv.dtype == torch.int64):
+        raise TypeError("ipiv of a batch must be an int64 CUDA tensor (or NotIPIV)")
+    batch, n = int(A.shape[0]), int(A.shape[1])
+    if _as_bool(check):
+        _check_batched_info(F.info, True)
+    X = torch.empty((batch, n, n), dtype=A.dtype, device=A.device)
+    if not row_major:
+        X = X.transpose(1, 2)
+    if batch > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        stride_ip = 0 if nopiv else (int(F.ipiv.stride(0)) if batch > 1 else max(n, 1))
+        info_t = torch.zeros(batch, dtype=torch.int64, device=A.device)
+        h.call(f"rflu_getri_batched_{sfx}_dev", batch, n, ctypes.c_void_p(A.data_ptr()), ld, stride_f, row_major,
+               ctypes.c_void_p(0 if nopiv else F.ipiv.data_ptr()), stride_ip, ctypes.c_void_p(X.data_ptr()), n, n * n,
+               _CBATCHED_TRANS[trans], ctypes.c_void_p(info_t.data_ptr()))
+        if _as_bool(check):
+            _check_batched_info(info_t, True)
+    return X
+
+
 def last_path(device: int = 0) -> str:
     """Which implementation served the last factorization on ``device`` (``enum rflu_path`` of include/rflu.h: "hip-recursive" /
     "hip-blocked" / "hip-lookahead" / "hip-engine" / "hip-batched" / "none")."""
