@@ -261,7 +261,7 @@ int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, c
  *     no RFLU_ERR_TIMEOUT from these entries.  Work is complete on return;
  *   - rflu_getrs_*: ldiv!(F, B) for any nrhs, F / ipiv as the factorization left them; a singular U yields Inf/NaN, no error status.
  *     The batched form is rflu_get{rf,rs}_batched_cf64_dev / _cf32_dev below, inv! / det / logabsdet from these factors are
- *     rflu_getri_c* / rflu_logabsdet_c* further below; there is no mixed-precision form;
+ *     rflu_getri_c* / rflu_logabsdet_c* further below, the mixed-precision form is rflu_mixed_get{rf,rs}_cf64_dev;
  *   - rflu_getrs_trans_*: ldiv!(transpose(F), B) and ldiv!(F', B), which differ for these element types, so the entries take `conj`:
  *     conj = 0 solves transpose(A) x = b (LAPACK 'T', B <- P^T L^-T U^-T B), conj = 1 solves A' x = b (LAPACK 'C', B <- P^T L^-H U^-H B),
  *     any other value is RFLU_ERR_ARG.  Everything else is as rflu_getrs_*: storage, lda / ldb, NULL ipiv = NotIPIV, alignment, any
@@ -320,7 +320,7 @@ int rflu_getrs_trans_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, con
  *     launch, one workgroup per matrix, any n (only diagonals are read, so it serves both orientations of rflu_getrf_batched_c*'s
  *     factors); bit-identical to the single-matrix entry on the same factors.
  * The batched inverse is rflu_getri_batched_c*_dev in the BATCHED COMPLEX block below.  Not here: row-major complex factors of a
- * single matrix, complex mixed precision. */
+ * single matrix. */
 int rflu_getri_cf64_dev(rflu_handle_t handle, int64_t n, double* F_dev, int64_t lda, const int64_t* ipiv_dev, int64_t* info);
 int rflu_getri_cf32_dev(rflu_handle_t handle, int64_t n, float* F_dev, int64_t lda, const int64_t* ipiv_dev, int64_t* info);
 int rflu_getri_cf64(rflu_handle_t handle, int64_t n, double* F_host, int64_t lda, const int64_t* ipiv_host, int64_t* info);
@@ -414,6 +414,43 @@ int rflu_mixed_getrs_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, cons
 /* building block: R <- B - A X, all column-major Float64, A n x n (R must not overlap A, X or B).  Bit-identical from run to run. */
 int rflu_residual_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const double* X_dev,
                           int64_t ldx, const double* B_dev, int64_t ldb, double* R_dev, int64_t ldr);
+
+/* ---- COMPLEX MIXED PRECISION: ComplexF32 factors of a ComplexF64 matrix, ComplexF64 iterative refinement (LAPACK zcgesv's scheme;
+ * csrc/complex_mixed.hip) ----
+ * A ComplexF64 factorization costs four times the real flops, so this is the element type where the Float32 rate matters most.  The
+ * contracts are those of rflu_mixed_getrf_f64_dev / rflu_mixed_getrs_f64_dev / rflu_residual_f64_dev above, word for word, except:
+ *   - storage and leading dimensions follow the other complex entries: double* / float* to interleaved (re, im) pairs, lda / ldf / ldb /
+ *     ldx / ldr count COMPLEX elements, a pointer aligned to the real type is enough;
+ *   - there is no blocksize; the pivot rule (largest modulus hypot(re, im), strict '>' from 0, lowest row on ties, a NaN modulus never
+ *     wins) and the zero-pivot rule (BOTH parts zero sets info once, the elimination carries on) are those of rflu_getrf_cf32_dev, and
+ *     info is that of the ComplexF32 factorization;
+ *   - F32_dev: caller-owned n x n ROW-MAJOR ComplexF32 (ldf >= n), receives L\U as the complex recursion leaves it;
+ *   - *anorm_out = ||A||_inf = the largest row sum of MODULI hypot(re, im) (LAPACK zlange('I')), summed in a fixed order in Float64;
+ *     the norms of the convergence rule are largest moduli.
+ * Carried over unchanged: A and B are only read; converged when for every column k ||r_k||_inf <= ||x_k||_inf * anorm * eps64 * sqrt(n),
+ * tested so that a NaN or Inf is never convergence; *iters >= 0 = steps taken, converged, < 0 = -(steps + 1), not converged within
+ * max_iter (<= 0 means 30); RFLU_OK in both cases, the library never falls back; an entry of A that overflows Float32 is no special case: it
+ * becomes Inf in F32, where the elimination turns it into NaN (Inf - Inf, 0 * Inf) the solve ends as non-convergence, and where it is
+ * taken as a pivot (multipliers 0, no NaN) convergence is still only reported when the rule, which then scales with ||A||_inf >= 1e38,
+ * is met; n == 0 or nrhs == 0 succeed with nothing launched; the argument checks; the handle's buffers.  Results are
+ * bit-identical from run to run and whatever the alignment of A / F32 and the values of lda / ldf.  The residual of up to
+ * RFLU_MIXED_GEMV_MAX_RHS right-hand sides streams A once per 8 of them, more go through the ComplexF64 GEMM on the transposed views
+ * (that crossover is the real path's value: a structural starting value here).  Every solve of the loop works on the row-major factors
+ * as they lie: no n x n copy, no workspace of size n^2. */
+int rflu_mixed_getrf_cf64_dev(rflu_handle_t handle, int64_t n, const double* A_dev, int64_t lda, float* F32_dev, int64_t ldf,
+                              int64_t* ipiv_dev, int pivot, double* anorm_out, int64_t* info);
+int rflu_mixed_getrs_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const float* F32_dev,
+                              int64_t ldf, const int64_t* ipiv_dev, double anorm, const double* B_dev, int64_t ldb, double* X_dev,
+                              int64_t ldx, int max_iter, int* iters);
+/* building block: R <- B - A X, all column-major ComplexF64, A n x n (R must not overlap A, X or B).  Bit-identical from run to run. */
+int rflu_residual_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const double* X_dev,
+                           int64_t ldx, const double* B_dev, int64_t ldb, double* R_dev, int64_t ldr);
+/* building block: B <- U^-1 L^-1 P B with F32_dev the ROW-MAJOR packed ComplexF32 factors (as rflu_mixed_getrf_cf64_dev leaves them)
+ * and B column-major (ldb >= n); ipiv NULL = NotIPIV.  F32 is only read, in place.  Up to 8 right-hand sides are solved in B's own
+ * columns, more go through a row-major image of B and the complex GEMM.  A zero u_ii gives Inf/NaN, no error status.  Argument checks
+ * and empty problems as rflu_getrs_cf32_dev.  Bit-identical from run to run and whatever the alignment of F32 and ldf. */
+int rflu_mixed_solve_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F32_dev, int64_t ldf,
+                              const int64_t* ipiv_dev, float* B_dev, int64_t ldb);
 
 /* ---- building blocks on the INTERNAL row-major layout: element (i,j) at R[i*ld + j] (device pointers).
  * These are the four kernels of the path plus the bookkeeping the multi-GPU block-column driver and the parity

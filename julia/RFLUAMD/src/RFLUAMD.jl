@@ -867,6 +867,96 @@ function ldiv_mixed!(X::Ptr{Float64}, ldx::Integer, F::MixedLU, B::Ptr{Float64},
     return F.iters >= 0
 end
 
+# ---- complex mixed precision: ComplexF32 factors of a ComplexF64 matrix + ComplexF64 refinement (rflu_mixed_*_cf64_dev) ----
+# The C entries take double* / float* to interleaved (re, im) pairs, which is the storage of Complex{T}: the pointers are reinterpreted.
+# Leading dimensions count complex elements.  There is no blocksize.
+"raw entry: ComplexF32 row-major factors of the column-major ComplexF64 `A` into `F32` (ldf >= n); returns `(info, anorm)`"
+function mixed_getrf_dev!(A::Ptr{ComplexF64}, n::Integer, lda::Integer, F32::Ptr{ComplexF32}, ldf::Integer, ipiv::Ptr{Int64}, pivot::Bool)
+    info = Ref{Int64}(0)
+    anorm = Ref{Float64}(0.0)
+    st = GC.@preserve anorm ccall((:rflu_mixed_getrf_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Cint, Ptr{Float64}, Ref{Int64}),
+               handle(), n, Ptr{Float64}(A), lda, Ptr{Float32}(F32), ldf, ipiv, Cint(pivot), Base.unsafe_convert(Ptr{Float64}, anorm), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return BlasInt(info[]), anorm[]
+end
+
+"raw entry: `X <- A \\ B` by refinement in ComplexF64; returns `iters` (>= 0 converged, < 0 not converged: do not use `X`)"
+function mixed_getrs_dev!(A::Ptr{ComplexF64}, n::Integer, nrhs::Integer, lda::Integer, F32::Ptr{ComplexF32}, ldf::Integer, ipiv::Ptr{Int64},
+                          anorm::Float64, B::Ptr{ComplexF64}, ldb::Integer, X::Ptr{ComplexF64}, ldx::Integer, max_iter::Integer)
+    iters = Ref{Cint}(0)
+    st = GC.@preserve iters ccall((:rflu_mixed_getrs_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Cdouble, Ptr{Float64}, Int64, Ptr{Float64},
+                Int64, Cint, Ptr{Cint}),
+               handle(), n, nrhs, Ptr{Float64}(A), lda, Ptr{Float32}(F32), ldf, ipiv, anorm, Ptr{Float64}(B), ldb, Ptr{Float64}(X), ldx,
+               Cint(max_iter), Base.unsafe_convert(Ptr{Cint}, iters))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return Int(iters[])
+end
+
+"raw entry: `R <- B - A X` in ComplexF64, everything column-major in HBM"
+function residual_dev!(R::Ptr{ComplexF64}, ldr::Integer, A::Ptr{ComplexF64}, n::Integer, nrhs::Integer, lda::Integer, X::Ptr{ComplexF64},
+                       ldx::Integer, B::Ptr{ComplexF64}, ldb::Integer)
+    st = ccall((:rflu_residual_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+               handle(), n, nrhs, Ptr{Float64}(A), lda, Ptr{Float64}(X), ldx, Ptr{Float64}(B), ldb, Ptr{Float64}(R), ldr)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return R
+end
+
+"raw entry (building block): `B <- U^-1 L^-1 P B` with the row-major ComplexF32 factors `F32`, `B` column-major in HBM"
+function mixed_solve_dev!(B::Ptr{ComplexF32}, ldb::Integer, F32::Ptr{ComplexF32}, n::Integer, nrhs::Integer, ldf::Integer, ipiv::Ptr{Int64})
+    st = ccall((:rflu_mixed_solve_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float32}, Int64),
+               handle(), n, nrhs, Ptr{Float32}(F32), ldf, ipiv, Ptr{Float32}(B), ldb)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return B
+end
+
+"""
+    ComplexMixedLU
+
+`MixedLU` for a ComplexF64 matrix: `A` (device pointer, untouched), its ComplexF32 factors `F32` (row-major, `ldf`), `ipiv`, `info` of the
+ComplexF32 factorization, `anorm = ||A||_inf` (row sums of moduli) and the `iters` of the last `ldiv_mixed!`.
+"""
+mutable struct ComplexMixedLU
+    A::Ptr{ComplexF64}
+    n::Int
+    lda::Int
+    F32::Ptr{ComplexF32}
+    ldf::Int
+    ipiv::Ptr{Int64}
+    info::BlasInt
+    anorm::Float64
+    iters::Int
+end
+
+"""
+    lu_mixed(A::Ptr{ComplexF64}, n, lda, F32::Ptr{ComplexF32}, ldf, ipiv, pivot = Val(true)) -> ComplexMixedLU
+
+The complex form of `lu_mixed` (LAPACK `zcgesv`'s scheme): a ComplexF32 copy of `A` is factored into the caller's `F32` (`n x ldf`,
+row-major).  `A` is not modified.  A zero pivot of the ComplexF32 factorization is reported in `info`, never thrown.
+"""
+function lu_mixed(A::Ptr{ComplexF64}, n::Integer, lda::Integer, F32::Ptr{ComplexF32}, ldf::Integer, ipiv::Ptr{Int64}, pivot = Val(true))
+    pivot = normalize_pivot(pivot)
+    info, anorm = mixed_getrf_dev!(A, n, lda, F32, ldf, ipiv, pivot === Val(true))
+    (pivot === Val(false) && NOPIVOT_NEGATIVE_INFO) && (info = -info)
+    return ComplexMixedLU(A, Int(n), Int(lda), F32, Int(ldf), ipiv, info, anorm, 0)
+end
+
+"""
+    ldiv_mixed!(X::Ptr{ComplexF64}, ldx, F::ComplexMixedLU, B::Ptr{ComplexF64}, ldb, nrhs; max_iter = 30) -> Bool
+
+`X <- A \\ B` by ComplexF32 solves and ComplexF64 residuals; `false` means `X` must not be used (zero pivot or no convergence) and the
+caller solves with the ComplexF64 factorization instead.
+"""
+function ldiv_mixed!(X::Ptr{ComplexF64}, ldx::Integer, F::ComplexMixedLU, B::Ptr{ComplexF64}, ldb::Integer, nrhs::Integer;
+                     max_iter::Integer = 30)
+    F.info == 0 || return false
+    F.iters = mixed_getrs_dev!(F.A, F.n, nrhs, F.lda, F.F32, F.ldf, F.ipiv, F.anorm, B, ldb, X, ldx, max_iter)
+    return F.iters >= 0
+end
+
 """
     device_pointer(x) -> Ptr
 

@@ -34,6 +34,7 @@ from .lu import (  # noqa: F401
     ldiv_complex_,
     ldiv_complex_adjoint_,
     ldiv_complex_batched_,
+    ldiv_complex_mixed,
     ldiv_complex_transpose_,
     ldiv_mixed,
     logabsdet,
@@ -50,6 +51,7 @@ from .lu import (  # noqa: F401
     lu_complex_,
     lu_complex_batched,
     lu_complex_batched_,
+    lu_complex_mixed,
     lu_mixed,
     normalize_pivot,
 )
@@ -68,7 +70,7 @@ __all__ = [
     "ButterflyWorkspace", "butterfly_workspace", "butterfly_solve_", "butterfly_mul_",
     "lu", "lu_", "ldiv_", "LU", "lu_batched", "lu_batched_", "ldiv_batched_", "BatchedLU", "lu_mixed", "ldiv_mixed", "MixedLU", "NotConvergedError", "NotIPIV", "RowMaximum", "NoPivot", "Val", "Adjoint", "Transpose", "SingularException",
     "lu_complex", "lu_complex_", "ldiv_complex_", "ldiv_complex_adjoint_", "ldiv_complex_transpose_",
-    "lu_complex_batched", "lu_complex_batched_", "ldiv_complex_batched_",
+    "lu_complex_batched", "lu_complex_batched_", "ldiv_complex_batched_", "lu_complex_mixed", "ldiv_complex_mixed",
     "inv", "inv_", "det", "logabsdet", "logdet", "inv_batched", "logabsdet_batched", "det_batched",
     "inv_complex", "inv_complex_", "det_complex", "logabsdet_complex", "logdet_complex", "logabsdet_complex_batched", "det_complex_batched",
     "inv_complex_batched",

@@ -80,6 +80,11 @@ _PLAIN = {
     "rflu_mixed_getrf_f64_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_i64, c_p, c_p]),
     "rflu_mixed_getrs_f64_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_dbl, c_p, c_i64, c_p, c_i64, c_int, c_p]),
     "rflu_residual_f64_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64]),
+    # complex mixed precision (ComplexF32 factors of a ComplexF64 matrix, ComplexF64 refinement): no blocksize
+    "rflu_mixed_getrf_cf64_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_int, c_p, c_p]),
+    "rflu_mixed_getrs_cf64_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_dbl, c_p, c_i64, c_p, c_i64, c_int, c_p]),
+    "rflu_residual_cf64_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64]),
+    "rflu_mixed_solve_cf32_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64]),
     "rflu_profile_enable": (c_int, [c_p, c_int]),
     "rflu_profile_get": (c_int, [c_p, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64), ctypes.POINTER(c_dbl)]),
     "rflu_profile_get_bytes": (c_int, [c_p, c_int, ctypes.POINTER(c_dbl)]),

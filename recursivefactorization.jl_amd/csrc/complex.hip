@@ -332,6 +332,21 @@ int cgetrf_cm_dev(Handle* h, int64_t m, int64_t n, R* A, int64_t lda, int64_t* i
     return RFLU_OK;
 }
 
+// the factorization on the caller's row-major n x n array, for the mixed-precision driver (arguments checked there)
+template <typename R>
+int cgetrf_rm_dev(Handle* h, int64_t n, R* F, int64_t ldf, int64_t* ipiv, int pivot, int64_t* info)
+{
+    *info = 0;
+    if (n == 0) return RFLU_OK;
+    RFLU_HIP(hipMemsetAsync(h->info_dev, 0, 2 * sizeof(int64_t), h->stream));
+    RFLU_TRY(cgetrf_rm<R>(h, n, n, F, ldf, ipiv, pivot));
+    RFLU_HIP(hipMemcpyAsync(h->info_pinned, h->info_dev, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    *info = h->info_pinned[0];
+    h->last_path = RFLU_PATH_HIP_RECURSIVE;
+    return RFLU_OK;
+}
+
 // ldiv!(F, B): B <- U^-1 L^-1 P B; F (n x n, lda) and B (n x nrhs, ldb) column-major, ipiv NULL = NotIPIV
 template <typename R>
 int cgetrs_cm_dev(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, const int64_t* ipiv, R* B, int64_t ldb)
@@ -369,6 +384,7 @@ int cgemm_public(Handle* h, int64_t M, int64_t N, int64_t K, const R* A, int64_t
 
 #define RFLU_INSTANTIATE_COMPLEX(R)                                                                                                  \
     template int cgetrf_cm_dev<R>(Handle*, int64_t, int64_t, R*, int64_t, int64_t*, int, int64_t*);                                  \
+    template int cgetrf_rm_dev<R>(Handle*, int64_t, R*, int64_t, int64_t*, int, int64_t*);                                           \
     template int cgetrs_cm_dev<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t);                        \
     template int cgemm_public<R>(Handle*, int64_t, int64_t, int64_t, const R*, int64_t, const R*, int64_t, R*, int64_t);                \
     template int launch_ctranspose<R>(Handle*, int64_t, int64_t, const R*, int64_t, R*, int64_t, bool);                                 \

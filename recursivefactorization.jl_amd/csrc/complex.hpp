@@ -81,6 +81,34 @@ int cgetrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t 
 template <typename R>
 int launch_claswp_rev(Handle* h, R* A, int64_t rs, int64_t cs, int64_t rows, int64_t ncols, const int64_t* ipiv);
 
+// ---- complex mixed precision: ComplexF32 factors in the ROW-MAJOR layout, ComplexF64 refinement ----------------
+// complex.hip: factor the n x n row-major F in place (cgetrf_rm with the info word zeroed before and copied back after; waits for the
+// stream).  Pivot and zero-pivot rules are cgetrf_cm_dev's.
+template <typename R>
+int cgetrf_rm_dev(Handle* h, int64_t n, R* F, int64_t ldf, int64_t* ipiv, int pivot, int64_t* info);
+// complex_solve.hip: B <- U^-1 L^-1 P B with W the row-major packed factors, no n x n copy.  csolve_fwd_narrow works on the columns of a
+// column-major B (nrhs <= CNARROW), csolve_fwd_image on a row-major n x nrhs image X; neither waits for the stream.  cgetrs_fwd_rm_dev
+// is the checked entry on a column-major B (any nrhs; wider blocks go through the image in Handle::rhs_work) and waits.
+template <typename R>
+int csolve_fwd_narrow(Handle* h, int64_t n, int nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* B, int64_t ldb);
+template <typename R>
+int csolve_fwd_image(Handle* h, int64_t n, int64_t nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* X, int64_t ldx);
+template <typename R>
+int cgetrs_fwd_rm_dev(Handle* h, int64_t n, int64_t nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* B, int64_t ldb);
+// complex_mixed.hip.  A, X, B, R column-major ComplexF64; F row-major ComplexF32; every ld in complex elements.
+// F <- ComplexF32(A) in row-major, *anorm_dev (device) <- ||A||_inf (row sums of moduli); partial sums in Handle::mixed_part
+int launch_cdemote_relayout(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, double* anorm_dev);
+// R <- B - A X for nrhs <= RESIDUAL_PASS; A is read once
+int launch_cresidual_few(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
+                         int64_t ldb, double* R, int64_t ldr);
+// out (+)= (TO) in on column-major n x nrhs blocks / out[r][c] (+)= (TO) in[c][r]
+template <typename TI, typename TO>
+int launch_cconvert(Handle* h, int64_t n, int64_t nrhs, const TI* in, int64_t ld_in, TO* out, int64_t ld_out, bool add);
+template <typename TI, typename TO>
+int launch_cconvert_transpose(Handle* h, int64_t rows_out, int64_t cols_out, const TI* in, int64_t ld_in, TO* out, int64_t ld_out, bool add);
+// norms[2k] = max_i |R[i, k]|, norms[2k + 1] = max_i |X[i, k]| (moduli, NaN-keeping)
+int launch_ccolnorms(Handle* h, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* X, int64_t ldx, double* norms);
+
 // complex_inverse.hip: inv!(F) in place on column-major factors (*info: the first u_ii with both parts zero, F is
 // then untouched), and logabsdet as (log|det|, det / |det|); dstride counts complex elements between diagonal entries
 inline int cgetri_check_args(int64_t n, const void* F, int64_t lda, const int64_t* info)

@@ -18,12 +18,6 @@
 
 namespace rflu {
 
-// acc + v * x as four fused multiply-adds in a fixed order (spelled out so that no two call sites can be contracted differently)
-template <typename R>
-__device__ __forceinline__ Cx<R> cfma(Cx<R> v, Cx<R> x, Cx<R> acc)
-{
-    return Cx<R>{fma(-v.im, x.im, fma(v.re, x.re, acc.re)), fma(v.im, x.re, fma(v.re, x.im, acc.im))};
-}
 template <typename R>
 __device__ __forceinline__ Cx<R> cload(const R* p) { return Cx<R>{p[0], p[1]}; }
 
@@ -302,6 +296,101 @@ int cgetrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t 
     return RFLU_OK;
 }
 
+// ---- the forward solve on ROW-MAJOR factors: B <- U^-1 L^-1 P B, W = the packed L\U as cgetrf_rm leaves it ------
+// The same two paths with the other two triangle kinds: the lower triangle of W is L (unit), its upper one U (stored diagonal), and a row
+// of W is contiguous like a row of V above.  Nothing is conjugated.  The interchanges come first and ascend.
+
+// x = P b: the interchanges k <-> ipiv[k] - 1 applied first first, k = k0 ... k1 - 1; claswp_rev_kernel's addressing, claswp_kernel's order
+template <typename R>
+__global__ void __launch_bounds__(256) claswp_fwd_kernel(R* __restrict__ A, int64_t rs, int64_t cs, int64_t rows, int64_t ncols,
+                                                          const int64_t* __restrict__ ipiv, int64_t k0, int64_t k1)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ncols) return;
+    R* col = A + 2 * (c * cs);
+    for (int64_t k = k0; k < k1; ++k) {
+        const int64_t p = ipiv[k] - 1;
+        if (p != k && p >= 0 && p < rows) {   // (a caller's ipiv outside the matrix is not followed)
+            R* a = col + 2 * k * rs;
+            R* b = col + 2 * p * rs;
+            const R ar = a[0], ai = a[1], br = b[0], bi = b[1];
+            a[0] = br; a[1] = bi;
+            b[0] = ar; b[1] = ai;
+        }
+    }
+}
+
+template <typename R>
+static int launch_claswp_fwd(Handle* h, R* A, int64_t rs, int64_t cs, int64_t rows, int64_t ncols, const int64_t* ipiv)
+{
+    ProfScope ps(h, RFLU_K_LASWP, 8.0 * sizeof(R) * (double)ncols * (double)rows);
+    hipLaunchKernelGGL(claswp_fwd_kernel<R>, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, h->stream, A, rs, cs, rows, ncols, ipiv,
+                       (int64_t)0, rows);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+// lower with a unit diagonal (L, forward) or upper with the stored one (U, backward)
+template <typename R, bool UPPER>
+static int launch_ctrsv_block_fwd(Handle* h, const R* T, int64_t ld, int64_t nb, int nrhs, R* Y, int64_t ldb)
+{
+    ProfScope ps(h, RFLU_K_TRSM, 4.0 * (double)nb * nb * nrhs);
+    hipLaunchKernelGGL((ctrsv_block_kernel<R, UPPER, !UPPER, false>), dim3(1), dim3(CTRSV_THREADS), 0, h->stream, T, ld, (int)nb, nrhs, Y, ldb);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+template <typename R>
+int csolve_fwd_narrow(Handle* h, int64_t n, int nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* B, int64_t ldb)
+{
+    if (n <= 0 || nrhs <= 0) return RFLU_OK;
+    const int64_t cnb = block_rows();
+    if (ipiv) RFLU_TRY(launch_claswp_fwd<R>(h, B, 1, ldb, n, nrhs, ipiv));
+    for (int64_t j0 = 0; j0 < n; j0 += cnb) {   // L y = P b, top down; the band left of the block holds what is already solved
+        const int64_t nb = std::min(cnb, n - j0);
+        RFLU_TRY(launch_cgemv_sub<R>(h, W, ldw, j0, nb, 0, j0, nrhs, B, ldb, false));
+        RFLU_TRY((launch_ctrsv_block_fwd<R, false>(h, W + 2 * (j0 * ldw + j0), ldw, nb, nrhs, B + 2 * j0, ldb)));
+    }
+    for (int64_t j0 = (n - 1) / cnb * cnb; j0 >= 0; j0 -= cnb) {   // U x = y, bottom up; the band right of the block
+        const int64_t nb = std::min(cnb, n - j0);
+        RFLU_TRY(launch_cgemv_sub<R>(h, W, ldw, j0, nb, j0 + nb, n, nrhs, B, ldb, false));
+        RFLU_TRY((launch_ctrsv_block_fwd<R, true>(h, W + 2 * (j0 * ldw + j0), ldw, nb, nrhs, B + 2 * j0, ldb)));
+    }
+    return RFLU_OK;
+}
+
+template <typename R>
+int csolve_fwd_image(Handle* h, int64_t n, int64_t nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* X, int64_t ldx)
+{
+    if (n <= 0 || nrhs <= 0) return RFLU_OK;
+    if (ipiv) RFLU_TRY(launch_claswp_fwd<R>(h, X, ldx, 1, n, nrhs, ipiv));
+    RFLU_TRY(ctri_lower_rec<R>(h, n, nrhs, W, ldw, X, ldx, true));
+    return ctri_upper_rec<R>(h, n, nrhs, W, ldw, X, ldx, false);
+}
+
+template <typename R>
+int cgetrs_fwd_rm_dev(Handle* h, int64_t n, int64_t nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* B, int64_t ldb)
+{
+    RFLU_TRY(cgetrs_check_args(n, nrhs, W, ldw, B, ldb));
+    if (n > INT32_MAX || nrhs > INT32_MAX) { set_error("complex mixed solve: n or nrhs beyond 2^31 - 1"); return RFLU_ERR_ARG; }
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    if (nrhs <= narrow_limit()) {
+        RFLU_TRY(csolve_fwd_narrow<R>(h, n, (int)nrhs, W, ldw, ipiv, B, ldb));
+    } else {
+        const int64_t ldx = cworkspace_ld(nrhs);
+        RFLU_TRY(ensure_buffer(&h->rhs_work, &h->rhs_work_bytes, (size_t)n * (size_t)ldx * 2 * sizeof(R)));
+        R* X = static_cast<R*>(h->rhs_work);
+        RFLU_TRY(launch_ctranspose<R>(h, n, nrhs, B, ldb, X, ldx, false));
+        RFLU_TRY(csolve_fwd_image<R>(h, n, nrhs, W, ldw, ipiv, X, ldx));
+        RFLU_TRY(launch_ctranspose<R>(h, nrhs, n, X, ldx, B, ldb, false));
+    }
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+template int csolve_fwd_narrow<float>(Handle*, int64_t, int, const float*, int64_t, const int64_t*, float*, int64_t);
+template int csolve_fwd_image<float>(Handle*, int64_t, int64_t, const float*, int64_t, const int64_t*, float*, int64_t);
+template int cgetrs_fwd_rm_dev<float>(Handle*, int64_t, int64_t, const float*, int64_t, const int64_t*, float*, int64_t);
 template int cgetrs_trans_cm_dev<double>(Handle*, int64_t, int64_t, const double*, int64_t, const int64_t*, double*, int64_t, int);
 template int cgetrs_trans_cm_dev<float>(Handle*, int64_t, int64_t, const float*, int64_t, const int64_t*, float*, int64_t, int);
 template int launch_claswp_rev<double>(Handle*, double*, int64_t, int64_t, int64_t, int64_t, const int64_t*);

@@ -810,6 +810,124 @@ static int mixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int6
     }
 }
 
+// ---- complex mixed precision: ComplexF32 factors of a ComplexF64 matrix, ComplexF64 refinement (LAPACK zcgesv's scheme; kernels:
+// complex_mixed.hip, the solve on the row-major factors: complex_solve.hip) -----------------------------------------
+// The loop, the rule and the buffers are those of mixed_getrf / mixed_getrs above; norms are moduli, leading dimensions count complex
+// elements.  Up to CNARROW right-hand sides the ComplexF32 right-hand sides stay column-major (the narrow solve works on columns: an
+// element-wise conversion, no transpose), more go through a row-major image.
+static int cmixed_getrf(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, int64_t* ipiv, int pivot,
+                        double* anorm_out, int64_t* info)
+{
+    if (n < 0 || n > INT32_MAX || lda < std::max<int64_t>(n, 1) || ldf < std::max<int64_t>(n, 1)) {
+        set_error("complex mixed_getrf: bad arguments n=%lld lda=%lld ldf=%lld", (long long)n, (long long)lda, (long long)ldf);
+        return RFLU_ERR_ARG;
+    }
+    if (anorm_out == nullptr || info == nullptr) { set_error("complex mixed_getrf: null anorm_out or info pointer"); return RFLU_ERR_ARG; }
+    if (n > 0 && (A == nullptr || F == nullptr)) { set_error("complex mixed_getrf: null matrix pointer"); return RFLU_ERR_ARG; }
+    if (pivot && ipiv == nullptr && n > 0) { set_error("complex mixed_getrf: pivot != 0 needs an ipiv buffer"); return RFLU_ERR_ARG; }
+    *anorm_out = 0.0;
+    *info = 0;
+    if (n == 0) return RFLU_OK;
+    RFLU_TRY(ensure_mixed_norms(h, 2));
+    RFLU_TRY(launch_cdemote_relayout(h, n, A, lda, F, ldf, static_cast<double*>(h->mixed_norms)));
+    RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, h->mixed_norms, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RFLU_TRY(cgetrf_rm_dev<float>(h, n, F, ldf, ipiv, pivot, info));   // waits for the stream: the norm has arrived
+    *anorm_out = static_cast<const double*>(h->mixed_norms_host)[0];
+    return RFLU_OK;
+}
+
+// R <- B - A X.  Few right-hand sides: cresidual_few in passes of RESIDUAL_PASS.  Many: R <- B, then the row-major complex GEMM
+// C -= A B with C = R^T (nrhs x n), A = X^T, B = A^T (plain transposes, nothing conjugated), in place on the column-major buffers.
+// The crossover is tune.mixed_gemv_max_rhs, the real path's value: a structural starting value for complex, not measured.
+static int cmixed_residual(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
+                           int64_t ldb, double* R, int64_t ldr)
+{
+    if (n <= 0 || nrhs <= 0) return RFLU_OK;
+    if (nrhs <= h->tune.mixed_gemv_max_rhs) {
+        for (int64_t k0 = 0; k0 < nrhs; k0 += RESIDUAL_PASS)
+            RFLU_TRY(launch_cresidual_few(h, n, std::min<int64_t>(RESIDUAL_PASS, nrhs - k0), A, lda, X + 2 * k0 * ldx, ldx, B + 2 * k0 * ldb, ldb,
+                                          R + 2 * k0 * ldr, ldr));
+        return RFLU_OK;
+    }
+    RFLU_HIP(hipMemcpy2DAsync(R, (size_t)ldr * 2 * sizeof(double), B, (size_t)ldb * 2 * sizeof(double), (size_t)n * 2 * sizeof(double),
+                              (size_t)nrhs, hipMemcpyDeviceToDevice, h->stream));
+    return launch_cgemm<double>(h, nrhs, n, n, X, ldx, A, lda, R, ldr);
+}
+
+static int cresidual_public(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
+                            int64_t ldb, double* R, int64_t ldr)
+{
+    const int64_t n1 = std::max<int64_t>(n, 1);
+    if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldx < n1 || ldb < n1 || ldr < n1) {
+        set_error("complex residual: bad arguments n=%lld nrhs=%lld lda=%lld ldx=%lld ldb=%lld ldr=%lld", (long long)n, (long long)nrhs,
+                  (long long)lda, (long long)ldx, (long long)ldb, (long long)ldr);
+        return RFLU_ERR_ARG;
+    }
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    if (A == nullptr || X == nullptr || B == nullptr || R == nullptr) { set_error("complex residual: null pointer"); return RFLU_ERR_ARG; }
+    RFLU_TRY(cmixed_residual(h, n, nrhs, A, lda, X, ldx, B, ldb, R, ldr));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+// W <- F32^-1 W on the ComplexF32 right-hand sides in the form the width chose (column-major, ld = ldw, or the row-major image)
+static int cmixed_solve_work(Handle* h, bool narrow, int64_t n, int64_t nrhs, const float* F, int64_t ldf, const int64_t* ipiv, float* W,
+                             int64_t ldw)
+{
+    return narrow ? csolve_fwd_narrow<float>(h, n, (int)nrhs, F, ldf, ipiv, W, ldw) : csolve_fwd_image<float>(h, n, nrhs, F, ldf, ipiv, W, ldw);
+}
+
+static int cmixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const float* F, int64_t ldf, const int64_t* ipiv,
+                        double anorm, const double* B, int64_t ldb, double* X, int64_t ldx, int max_iter, int* iters)
+{
+    const int64_t n1 = std::max<int64_t>(n, 1);
+    if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldf < n1 || ldb < n1 || ldx < n1) {
+        set_error("complex mixed_getrs: bad arguments n=%lld nrhs=%lld lda=%lld ldf=%lld ldb=%lld ldx=%lld", (long long)n, (long long)nrhs,
+                  (long long)lda, (long long)ldf, (long long)ldb, (long long)ldx);
+        return RFLU_ERR_ARG;
+    }
+    if (iters == nullptr) { set_error("complex mixed_getrs: null iters pointer"); return RFLU_ERR_ARG; }
+    *iters = 0;
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    if (A == nullptr || F == nullptr || B == nullptr || X == nullptr) { set_error("complex mixed_getrs: null pointer"); return RFLU_ERR_ARG; }
+    if (max_iter <= 0) max_iter = 30;
+    const bool narrow = nrhs <= CNARROW;
+    const int64_t ldw = narrow ? cworkspace_ld(n) : cworkspace_ld(nrhs);
+    RFLU_TRY(ensure_buffer(&h->mixed_rhs, &h->mixed_rhs_bytes, (size_t)(narrow ? nrhs : n) * (size_t)ldw * 2 * sizeof(float)));
+    RFLU_TRY(ensure_buffer(&h->mixed_r, &h->mixed_r_bytes, (size_t)n * (size_t)nrhs * 2 * sizeof(double)));
+    RFLU_TRY(ensure_mixed_norms(h, 2 * nrhs));
+    float* W = static_cast<float*>(h->mixed_rhs);
+    double* R = static_cast<double*>(h->mixed_r);
+    double* norms_dev = static_cast<double*>(h->mixed_norms);
+    const double* norms = static_cast<const double*>(h->mixed_norms_host);
+    const double scale = anorm * DBL_EPSILON * std::sqrt((double)n);
+    // W <- demote(S), W <- F32^-1 W, X (+)= promote(W)
+    auto correct = [&](const double* S, int64_t lds, bool add) -> int {
+        if (narrow) {
+            RFLU_TRY((launch_cconvert<double, float>(h, n, nrhs, S, lds, W, ldw, false)));
+            RFLU_TRY(cmixed_solve_work(h, true, n, nrhs, F, ldf, ipiv, W, ldw));
+            return launch_cconvert<float, double>(h, n, nrhs, W, ldw, X, ldx, add);
+        }
+        RFLU_TRY((launch_cconvert_transpose<double, float>(h, n, nrhs, S, lds, W, ldw, false)));
+        RFLU_TRY(cmixed_solve_work(h, false, n, nrhs, F, ldf, ipiv, W, ldw));
+        return launch_cconvert_transpose<float, double>(h, nrhs, n, W, ldw, X, ldx, add);
+    };
+
+    RFLU_TRY(correct(B, ldb, false));
+    for (int step = 0;; ++step) {
+        RFLU_TRY(cmixed_residual(h, n, nrhs, A, lda, X, ldx, B, ldb, R, n));
+        RFLU_TRY(launch_ccolnorms(h, n, nrhs, R, n, X, ldx, norms_dev));
+        RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, norms_dev, (size_t)(2 * nrhs) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        bool converged = true;
+        for (int64_t k = 0; k < nrhs && converged; ++k)
+            if (!(norms[2 * k] <= norms[2 * k + 1] * scale)) converged = false;
+        if (converged) { *iters = step; return RFLU_OK; }
+        if (step >= max_iter) { *iters = -(step + 1); return RFLU_OK; }
+        RFLU_TRY(correct(R, n, true));
+    }
+}
+
 // ---- what the other host sources call (driver.hpp) -------------------------------------------------------------------------------------
 #define RFLU_INSTANTIATE_DRIVER(T)                                                                                                    \
     template int trsm_rec<T>(Handle*, int64_t, int64_t, const T*, int64_t, T*, int64_t, const T*);                                    \
@@ -838,7 +956,7 @@ static Handle* H(rflu_handle_t h) { return reinterpret_cast<Handle*>(h); }
 
 extern "C" {
 
-int rflu_version(void) { return 107; }
+int rflu_version(void) { return 108; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -1356,6 +1474,35 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
     }
 DEFINE_COMPLEX(cf64, double)
 DEFINE_COMPLEX(cf32, float)
+
+int rflu_mixed_getrf_cf64_dev(rflu_handle_t handle, int64_t n, const double* A_dev, int64_t lda, float* F32_dev, int64_t ldf,
+                              int64_t* ipiv_dev, int pivot, double* anorm_out, int64_t* info)
+{
+    CHECK_HANDLE(handle);
+    return cmixed_getrf(H(handle), n, A_dev, lda, F32_dev, ldf, ipiv_dev, pivot, anorm_out, info);
+}
+
+int rflu_mixed_getrs_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const float* F32_dev,
+                              int64_t ldf, const int64_t* ipiv_dev, double anorm, const double* B_dev, int64_t ldb, double* X_dev,
+                              int64_t ldx, int max_iter, int* iters)
+{
+    CHECK_HANDLE(handle);
+    return cmixed_getrs(H(handle), n, nrhs, A_dev, lda, F32_dev, ldf, ipiv_dev, anorm, B_dev, ldb, X_dev, ldx, max_iter, iters);
+}
+
+int rflu_residual_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const double* X_dev,
+                           int64_t ldx, const double* B_dev, int64_t ldb, double* R_dev, int64_t ldr)
+{
+    CHECK_HANDLE(handle);
+    return cresidual_public(H(handle), n, nrhs, A_dev, lda, X_dev, ldx, B_dev, ldb, R_dev, ldr);
+}
+
+int rflu_mixed_solve_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F32_dev, int64_t ldf,
+                              const int64_t* ipiv_dev, float* B_dev, int64_t ldb)
+{
+    CHECK_HANDLE(handle);
+    return cgetrs_fwd_rm_dev<float>(H(handle), n, nrhs, F32_dev, ldf, ipiv_dev, B_dev, ldb);
+}
 
 int rflu_profile_enable(rflu_handle_t handle, int enable)
 {

@@ -12,24 +12,9 @@
 // through a workspace of partial sums (Handle::mixed_part) and are combined in a fixed order by a second kernel; the split depends on
 // n alone.  The vector (16-byte) and the element-wise forms of a kernel add the same numbers in the same order.
 // Roofline: HBM for the two matrix passes (algorithmic bytes 12 n^2 and 8 n^2); the small kernels are latency.
-#include "rflu_internal.hpp"
+#include "mixed_dev.hpp"
 
 namespace rflu {
-
-// max that keeps a NaN once it has seen one (fmax drops it): a NaN or Inf anywhere must reach the host's convergence test
-__device__ __forceinline__ double nanmax(double m, double v) { return (v > m || v != v) ? v : m; }
-
-// all 256 threads of the workgroup call it; thread 0 holds the result (fixed tree: the same order every run)
-__device__ __forceinline__ double block_nanmax(double v, double* sh)
-{
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] = nanmax(sh[threadIdx.x], sh[threadIdx.x + s]);
-        __syncthreads();
-    }
-    return sh[0];
-}
 
 // ---- demote_relayout -------------------------------------------------------------------------------------------------------------
 // One workgroup = one tile of DM_TI rows x DM_TJ columns of A.  Load: a lane owns two rows (VIN: the adjacent rows 2l, 2l+1 as one
@@ -122,6 +107,16 @@ __global__ void __launch_bounds__(256) final_max_kernel(int nb, const double* __
     if (threadIdx.x == 0) out[0] = m;
 }
 
+int launch_rowsum_max(Handle* h, int64_t n, int64_t ntj, const double* part, double* blockmax, double* out)
+{
+    const int64_t nb = (n + 255) / 256;
+    hipLaunchKernelGGL(rowsum_max_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, (int)n, (int)ntj, part, blockmax);
+    RFLU_HIP(hipGetLastError());
+    hipLaunchKernelGGL(final_max_kernel, dim3(1), dim3(256), 0, h->stream, (int)nb, blockmax, out);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
 int launch_demote_relayout(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, double* anorm_dev)
 {
     if (n <= 0) return RFLU_OK;
@@ -141,11 +136,7 @@ int launch_demote_relayout(Handle* h, int64_t n, const double* A, int64_t lda, f
         else             hipLaunchKernelGGL((demote_relayout_kernel<false, false>), grid, dim3(256), 0, h->stream, (int)n, A, lda, F, ldf, part);
         RFLU_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(rowsum_max_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, (int)n, (int)ntj, part, blockmax);
-    RFLU_HIP(hipGetLastError());
-    hipLaunchKernelGGL(final_max_kernel, dim3(1), dim3(256), 0, h->stream, (int)nb, blockmax, anorm_dev);
-    RFLU_HIP(hipGetLastError());
-    return RFLU_OK;
+    return launch_rowsum_max(h, n, ntj, part, blockmax, anorm_dev);
 }
 
 // ---- residual_few ----------------------------------------------------------------------------------------------------------------

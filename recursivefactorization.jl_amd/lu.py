@@ -13,6 +13,8 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
     NoPivot failures carry a NEGATIVE info on Julia >= 1.11                        :25,250,324 -> ``NOPIVOT_NEGATIVE_INFO``
     (no counterpart here; LinearSolve.jl's RF32MixedLUFactorization: Float32 factors,      -> ``lu_mixed`` / ``ldiv_mixed`` / ``MixedLU``
      Float64 iterative refinement)
+    (no counterpart: the same for ComplexF64, LAPACK zcgesv's scheme)                       -> ``lu_complex_mixed`` /
+                                                                                             ``ldiv_complex_mixed``
     lu / lu! / ldiv! with T = ComplexF64 / ComplexF32 (test/runtests.jl:33-84)              -> ``lu_complex`` / ``lu_complex_`` /
                                                                                              ``ldiv_complex_`` (names of their own: ``lu``
                                                                                              keeps raising ``TypeError`` on complex input)
@@ -792,24 +794,27 @@ class MixedLU:
         return self.info == 0
 
 
-def _check_mixed_matrix(A):
-    """Shape, element type and layout of ``lu_mixed``'s matrix -- before anything touches the library."""
+def _check_mixed_matrix(A, cplx=False):
+    """Shape, element type and layout of ``lu_mixed``'s / ``lu_complex_mixed``'s matrix -- before anything touches the library."""
+    name = "lu_complex_mixed" if cplx else "lu_mixed"
     if getattr(A, "ndim", None) != 2:
-        raise ValueError("lu_mixed needs a matrix")
-    if str(A.dtype).replace("torch.", "") != "float64":
+        raise ValueError(f"{name} needs a matrix")
+    dt = str(A.dtype).replace("torch.", "")
+    if cplx and dt != "complex128":
+        raise TypeError(f"lu_complex_mixed factors a ComplexF64 matrix in ComplexF32 and refines in ComplexF64 (got {A.dtype}); "
+                        "a ComplexF32 matrix goes to lu_complex / lu_complex_ directly, a Float64 one to lu_mixed")
+    if not cplx and dt != "float64":
         raise TypeError(f"lu_mixed factors a Float64 matrix in Float32 and refines in Float64 (got {A.dtype}); "
-                        "a Float32 matrix goes to lu / lu_ directly")
+                        "a Float32 matrix goes to lu / lu_ directly, a ComplexF64 one to lu_complex_mixed / ldiv_complex_mixed")
     if A.shape[0] != A.shape[1]:
-        raise ValueError("lu_mixed needs a square matrix")
+        raise ValueError(f"{name} needs a square matrix")
 
 
-def lu_mixed(A, pivot=True, *, blocksize=None, handle=None) -> MixedLU:
-    """Factor a Float32 copy of the Float64 matrix ``A`` (``rflu_mixed_getrf_f64_dev``): one pass demotes ``A`` into the library's
-    row-major layout and yields ||A||_inf, the Float32 factorization runs in place there.  ``A`` is NOT modified and is kept by
-    reference.  ``A``: a CUDA Float64 tensor, column-major (``stride(0) == 1``) like the other device entries; a NumPy array is staged
-    through a torch tensor.  A zero pivot of the Float32 factorization is reported in ``info``, never raised: ``ldiv_mixed`` decides."""
+def _lu_mixed_call(A, pivot, blocksize, handle, cplx: bool) -> MixedLU:
+    """``lu_mixed`` (``cplx`` false) and ``lu_complex_mixed``: the same checks, staging and call; the complex entry has no blocksize."""
+    name = "lu_complex_mixed" if cplx else "lu_mixed"
     piv = normalize_pivot(pivot)
-    _check_mixed_matrix(A)
+    _check_mixed_matrix(A, cplx)
     import torch
 
     if not _is_torch(A):
@@ -820,22 +825,42 @@ def lu_mixed(A, pivot=True, *, blocksize=None, handle=None) -> MixedLU:
         raise _ffi.RfluError("torch input must live on the MI355X (device='cuda'); host data goes in as NumPy")
     n = int(A.shape[0])
     if n > 1 and not (A.stride(0) == 1 and A.stride(1) >= n):
-        raise ValueError("lu_mixed: the matrix must be dense column-major (stride(0) == 1, stride(1) >= n)")
+        raise ValueError(f"{name}: the matrix must be dense column-major (stride(0) == 1, stride(1) >= n)")
     lda = int(A.stride(1)) if n > 1 else max(n, 1)
     ldf = (max(n, 1) + 15) // 16 * 16
-    F32 = torch.empty((n, ldf), dtype=torch.float32, device=A.device)[:, :n]
+    F32 = torch.empty((n, ldf), dtype=torch.complex64 if cplx else torch.float32, device=A.device)[:, :n]
     ipiv_t = torch.empty(n, dtype=torch.int64, device=A.device) if piv else None
     info, anorm = ctypes.c_int64(0), ctypes.c_double(0.0)
     if n > 0:
         h = handle or _ffi.default_handle(A.device.index or 0)
         h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
-        h.call("rflu_mixed_getrf_f64_dev", n, ctypes.c_void_p(A.data_ptr()), lda, ctypes.c_void_p(F32.data_ptr()), ldf,
-               ctypes.c_void_p(ipiv_t.data_ptr() if ipiv_t is not None else 0), int(piv), int(blocksize or 0), ctypes.byref(anorm),
-               ctypes.byref(info))
+        head = (n, ctypes.c_void_p(A.data_ptr()), lda, ctypes.c_void_p(F32.data_ptr()), ldf,
+                ctypes.c_void_p(ipiv_t.data_ptr() if ipiv_t is not None else 0), int(piv))
+        if cplx:
+            h.call("rflu_mixed_getrf_cf64_dev", *head, ctypes.byref(anorm), ctypes.byref(info))
+        else:
+            h.call("rflu_mixed_getrf_f64_dev", *head, int(blocksize or 0), ctypes.byref(anorm), ctypes.byref(info))
     inf = int(info.value)
     if not piv and NOPIVOT_NEGATIVE_INFO:
         inf = -inf
     return MixedLU(A, F32, ipiv_t if ipiv_t is not None else NotIPIV(n), inf, float(anorm.value))
+
+
+def lu_mixed(A, pivot=True, *, blocksize=None, handle=None) -> MixedLU:
+    """Factor a Float32 copy of the Float64 matrix ``A`` (``rflu_mixed_getrf_f64_dev``): one pass demotes ``A`` into the library's
+    row-major layout and yields ||A||_inf, the Float32 factorization runs in place there.  ``A`` is NOT modified and is kept by
+    reference.  ``A``: a CUDA Float64 tensor, column-major (``stride(0) == 1``) like the other device entries; a NumPy array is staged
+    through a torch tensor.  A zero pivot of the Float32 factorization is reported in ``info``, never raised: ``ldiv_mixed`` decides.
+    A complex matrix raises ``TypeError``: it goes to ``lu_complex_mixed``."""
+    return _lu_mixed_call(A, pivot, blocksize, handle, False)
+
+
+def lu_complex_mixed(A, pivot=True, *, handle=None) -> MixedLU:
+    """``lu_mixed`` for a ComplexF64 matrix (``rflu_mixed_getrf_cf64_dev``, LAPACK ``zcgesv``'s scheme): one pass demotes ``A`` into a
+    ComplexF32 row-major image and yields ||A||_inf (the largest row sum of moduli), the ComplexF32 recursion factors it in place.
+    Returns the same ``MixedLU``: ``F32`` is a complex64 row-major tensor, ``info`` that of the ComplexF32 factorization (the pivot is
+    the row of largest modulus, as in ``lu_complex_``).  ``A`` is NOT modified and is kept by reference; there is no ``blocksize``."""
+    return _lu_mixed_call(A, pivot, None, handle, True)
 
 
 def ldiv_mixed(F: MixedLU, B, *, max_iter=30, fallback=True, handle=None):
@@ -846,17 +871,36 @@ def ldiv_mixed(F: MixedLU, B, *, max_iter=30, fallback=True, handle=None):
     When the Float32 factorization hit a zero pivot (``F.info != 0``) or the refinement does not converge within ``max_iter`` steps:
     ``fallback=True`` solves with the Float64 ``lu`` / ``ldiv_`` of a copy of ``A`` (kept in ``F`` for later calls) and sets
     ``F.fell_back``; a matrix that is singular in Float64 too raises ``SingularException`` as ``lu`` does.  ``fallback=False`` raises
-    ``SingularException`` / ``NotConvergedError`` instead.  The library itself never falls back."""
+    ``SingularException`` / ``NotConvergedError`` instead.  The library itself never falls back.  Complex factors (from
+    ``lu_complex_mixed``) raise ``TypeError``: they go to ``ldiv_complex_mixed``."""
+    return _ldiv_mixed_call(F, B, max_iter, fallback, handle, False)
+
+
+def ldiv_complex_mixed(F: MixedLU, B, *, max_iter=30, fallback=True, handle=None):
+    """``ldiv_mixed`` with the ComplexF32 factors ``lu_complex_mixed`` returned (``rflu_mixed_getrs_cf64_dev``): the same loop, rule and
+    return value, the norms as largest moduli.  Every ComplexF32 solve works on the row-major factors as they lie.  ``fallback=True``
+    goes through ``lu_complex`` / ``ldiv_complex_`` in ComplexF64 (also when an entry of ``A`` overflows Float32 and the Inf it becomes
+    turns into NaN in the elimination, which ends as non-convergence); ``fallback=False`` raises ``SingularException`` /
+    ``NotConvergedError``."""
+    return _ldiv_mixed_call(F, B, max_iter, fallback, handle, True)
+
+
+def _ldiv_mixed_call(F, B, max_iter, fallback, handle, cplx: bool):
+    """``ldiv_mixed`` (``cplx`` false) and ``ldiv_complex_mixed``: the same checks, staging, call and fallback rule."""
+    name, maker, want = ("ldiv_complex_mixed", "lu_complex_mixed", "complex128") if cplx else ("ldiv_mixed", "lu_mixed", "float64")
     if not isinstance(F, MixedLU):
-        raise TypeError("ldiv_mixed needs the MixedLU that lu_mixed returned")
+        raise TypeError(f"{name} needs the MixedLU that {maker} returned")
     A = F.A
+    if str(A.dtype).replace("torch.", "") != want:
+        raise TypeError(f"{name} needs the MixedLU that {maker} returned; these factors belong to "
+                        f"{'ldiv_mixed' if cplx else 'ldiv_complex_mixed'}")
     n = int(A.shape[0])
     if getattr(B, "ndim", 0) not in (1, 2):
         raise ValueError("B must be a vector or a matrix")
     if B.shape[0] != n:
         raise ValueError("right-hand side has the wrong number of rows")
-    if str(B.dtype).replace("torch.", "") != "float64":
-        raise TypeError("B must be Float64 like A")
+    if str(B.dtype).replace("torch.", "") != want:
+        raise TypeError("B must be ComplexF64 like A" if cplx else "B must be Float64 like A")
     import torch
 
     host = not _is_torch(B)
@@ -877,7 +921,7 @@ def ldiv_mixed(F: MixedLU, B, *, max_iter=30, fallback=True, handle=None):
         if n > 1 and not (Bd.stride(0) == 1 and (nrhs <= 1 or Bd.stride(1) >= n)):
             raise ValueError("B must be column-major like A")
         ldb = int(Bd.stride(1)) if (nrhs > 1 and n > 1) else max(n, 1)
-    X = torch.empty(n, dtype=torch.float64, device=A.device) if Bd.ndim == 1 else torch.empty((nrhs, n), dtype=torch.float64, device=A.device).T
+    X = torch.empty(n, dtype=A.dtype, device=A.device) if Bd.ndim == 1 else torch.empty((nrhs, n), dtype=A.dtype, device=A.device).T
     F.fell_back = False
     F.iters = 0
     ok = F.info == 0
@@ -885,7 +929,7 @@ def ldiv_mixed(F: MixedLU, B, *, max_iter=30, fallback=True, handle=None):
         h = handle or _ffi.default_handle(A.device.index or 0)
         h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
         iters = ctypes.c_int(0)
-        h.call("rflu_mixed_getrs_f64_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), int(A.stride(1)) if n > 1 else 1,
+        h.call("rflu_mixed_getrs_cf64_dev" if cplx else "rflu_mixed_getrs_f64_dev", n, nrhs, ctypes.c_void_p(A.data_ptr()), int(A.stride(1)) if n > 1 else 1,
                ctypes.c_void_p(F.F32.data_ptr()), int(F.F32.stride(0)) if n > 1 else 1,
                ctypes.c_void_p(0 if isinstance(F.ipiv, NotIPIV) else F.ipiv.data_ptr()), float(F.anorm), ctypes.c_void_p(Bd.data_ptr()), ldb,
                ctypes.c_void_p(X.data_ptr()), max(n, 1), int(max_iter), ctypes.byref(iters))
@@ -896,10 +940,10 @@ def ldiv_mixed(F: MixedLU, B, *, max_iter=30, fallback=True, handle=None):
             if F.info != 0:
                 raise SingularException(abs(F.info))
             raise NotConvergedError(F.iters)
-        if F._f64 is None:
-            F._f64 = lu(A, not isinstance(F.ipiv, NotIPIV), handle=handle)   # check=True: SingularException when Float64 is singular too
+        if F._f64 is None:   # check=True: SingularException when Float64 is singular too
+            F._f64 = (lu_complex if cplx else lu)(A, not isinstance(F.ipiv, NotIPIV), handle=handle)
         X.copy_(Bd)
-        ldiv_(F._f64, X, handle=handle)
+        (ldiv_complex_ if cplx else ldiv_)(F._f64, X, handle=handle)
         F.fell_back = True
     return X.cpu().numpy() if host else X
 
