@@ -1,23 +1,26 @@
 """-m gpu: inv / det / logabsdet from the LU factors (rflu_getri_* / rflu_logabsdet_* and their batched forms, csrc/inverse.hip and
 csrc/batched.hip) through inv_ / inv / logabsdet / det / inv_batched / logabsdet_batched and the raw C ABI.
 
-Inputs: rand_matrix(n, n, seed=SEEDS.get(n, 91000 + n), dtype) (+ 10 I for NoPivot); matrix b of a batch is rand_matrix(n, n, seed=93000 + b, dtype).
+Inputs (tests/inv_cases.py): rand_matrix(n, n, seed=SEEDS.get(n, 91000 + n), dtype) (+ 10 I for NoPivot); matrix b of a batch is
+rand_matrix(n, n, seed=93000 + b, dtype).  The module prints one summary line with the worst ratio per kind of check at its end (-s).
 
 Bars.
   * Inverse: with everything promoted to Float64 on the host, rho_R = ||A X - I||_1 / (n eps_T ||A||_1 ||X||_1) and rho_L the same with
     X A; rho <= 1 for every size (LAPACK's xGET03 ratio, whose own acceptance threshold is 30).  numpy.linalg.inv (LAPACK getri) on
     exactly these inputs, both sides: worst rho 0.13 (n = 2, Float64) and 0.071 (n = 2, Float32), for n >= 63 0.0070 (n = 65, Float64)
     and 0.00060 (Float32); on the batch inputs (200 matrices each, n = 1 .. 128) worst 0.50 (n = 1); scripts/inv_cpu_bars.py prints
-    the table.
+    the table.  Measured on an MI355X: 0.13 (n = 2, Float64) and 0.071 (Float32), for n >= 63 at most 0.011 (n = 200, Float64) and
+    0.012 (n = 129, Float32); batched 0.50 (n = 1), 0.31 (n = 2), 0.11 (n = 7), at most 0.07 from n = 8 on.  The bar hides two orders of
+    magnitude: tests/test_gpu_inv_exact.py holds the same entries to exact references.
   * logabsdet, tight (the reduction): against math.fsum(log|u_ii|) over the device's own downloaded factors,
     |d| <= (2 + ceil(log2 n)) eps64 sum|log|u_ii||  (one ulp per log, plus the pairwise-summation bound); sign exactly equal.
   * logabsdet, loose (ties it to A): against numpy.linalg.slogdet of the Float64-promoted A, 8 n eps_T absolute, equal sign.
     oracle.lu factors (the GPU's elimination order) of these inputs stay within 2.0 n eps64 (worst at n = 512: one ulp of the value)
-    and 1.9 n eps32 (n = 1025) of the Float64 value (scripts/inv_cpu_bars.py; see SEEDS below for the four sizes whose default seed
+    and 1.9 n eps32 (n = 1025) of the Float64 value (scripts/inv_cpu_bars.py; see SEEDS in tests/inv_cases.py for the four sizes whose default seed
     gives a matrix on which the oracle itself misses this absolute bar)."""
 import ctypes
-import functools
 import math
+import re
 
 import numpy as np
 import pytest
@@ -25,44 +28,28 @@ import torch
 
 import recursivefactorization.jl_amd as rf
 from gpu_util import handle, ptr, sfx, tdtype, to_dev_cm
-from helpers import rand_matrix
+from inv_cases import BATCH_CASES, SIZES, VARIANT_SIZES, header_constants, host_batch, matrix   # the inputs: one definition, tests/inv_cases.py
 
 pytestmark = pytest.mark.gpu
 
-W = 512                                                   # GETRI_W of csrc/rflu_internal.hpp
-SIZES = [1, 2, 63, 64, 65, 127, 128, 129, 200, 511, 512, 513, 1025, 1100, 2112]   # the issue's list and W-1, W, W+1, 2W+1
-VARIANT_SIZES = [65, 200, 513]
-BATCH_CASES = [(n, 200) for n in (1, 2, 7, 8, 33, 64, 65, 100, 128)] + [(64, 1), (64, 257)]
+W = header_constants()["GETRI_W"]                         # GETRI_W of csrc/rflu_internal.hpp; SIZES holds W-1, W, W+1 and 2W+1
+assert {W - 1, W, W + 1, 2 * W + 1} <= set(SIZES)
 DTYPES = [np.float64, np.float32]
 SENTINEL = -7.25
-# seed of the n x n input: 91000 + n, except where that matrix is too ill-conditioned for the ABSOLUTE logabsdet bar 8 n eps_T to mean
-# anything -- there the CPU oracle's own factors miss it (n = 2: cond 551, off by 10 n eps in both element types; 511, 512, 1025:
-# 13 .. 15 n eps64); the next seed in steps of 3000 at which oracle.lu stays within 2 n eps_T is taken (scripts/inv_cpu_bars.py)
-SEEDS = {2: 94002, 511: 97511, 512: 97512, 1025: 98025}
+WORST = {}                                                # kind of check -> (worst rho, where): one summary line per run
 
 
-@functools.lru_cache(maxsize=None)
-def _matrix(n, dtype, diag):
-    A = np.array(rand_matrix(n, n, seed=SEEDS.get(n, 91000 + n), dtype=dtype), order="F")
-    if diag:
-        A += dtype(10) * np.eye(n, dtype=dtype)
-    A.setflags(write=False)
-    return A
+@pytest.fixture(scope="module", autouse=True)
+def _summary():
+    yield
+    if WORST:
+        print("\ntest_gpu_inv worst rho (bar 1.0): " + "; ".join(f"{k}: {v[0]:.4f} ({v[1]})" for k, v in sorted(WORST.items())))
 
 
-def matrix(n, dtype, diag=False):
-    return _matrix(n, np.dtype(dtype).type, diag)
-
-
-@functools.lru_cache(maxsize=None)
-def _batch(n, batch, dtype):
-    out = np.stack([rand_matrix(n, n, seed=93000 + b, dtype=dtype) for b in range(batch)])
-    out.setflags(write=False)
-    return out
-
-
-def host_batch(n, batch, dtype):
-    return _batch(n, batch, np.dtype(dtype).type)
+def record(what, dtype, value):
+    key = re.sub(r"\d+", "#", what.replace(np.dtype(dtype).name, "").strip()) + " " + np.dtype(dtype).name
+    if value >= WORST.get(key, (-1.0, ""))[0]:
+        WORST[key] = (value, what)
 
 
 def host(t):
@@ -83,6 +70,7 @@ def rho(A, X, dtype):
 def check_inverse(A, X, dtype, what):
     r, l = rho(A, X, dtype)
     print(f"{what}: rho_R = {r:.3e}, rho_L = {l:.3e}")
+    record(what, dtype, max(r, l))
     assert r <= 1.0 and l <= 1.0, (what, r, l)
 
 
@@ -247,6 +235,7 @@ def check_batch_inverse(A, X, dtype, what, skip=()):
         r, l = rho(A64[b], X64[b], dtype)
         worst = max(worst, r, l)
     print(f"{what}: worst rho = {worst:.3e} (n = {n}, {A.shape[0]} matrices)")
+    record(f"{what} n={n}", dtype, worst)
     assert worst <= 1.0, (what, worst)
 
 
