@@ -7,7 +7,9 @@ tests/test_gpu_inv_exact.py).  Pure numpy (and the CPU oracle for the factors of
     complex_inv_cases.partial_sum_bits (with |M| = |re|) bounds the bits of every partial sum of any blocked inverse of them;
   * getri_transcription (imported from complex_inv_cases: getri_view<T> of csrc/inverse.hip has the steps of cgetri_view, and the
     transcription does not care about the element type): the two sweeps in numpy with the index arithmetic of the drivers;
-  * batched_restatement: getri_batched_kernel of csrc/batched.hip in numpy, in the kernel's own order and in the element's precision."""
+  * batched_restatement: getri_batched_kernel of csrc/batched.hip in numpy, in the kernel's own order and in the element's precision;
+    compose_interchanges and bsubstitute (column- and row-reading) also serve the restatement of the batched SOLVE in
+    tests/batched_solve_cases.py."""
 import functools
 import math
 import os
@@ -220,20 +222,31 @@ def compose_interchanges(ipiv, n, ignore_p1=False):
     return np.concatenate(half)[:n]
 
 
-def bsubstitute(F, x):
+def bsubstitute(F, x, trans=False, mutation=None):
     """bsubstitute<T, false> of csrc/batched.hip on the columns of x, in place: L (unit) forward, column-oriented -- after step k every
     row below takes f * x_k out of itself; U backward -- every row above takes f * (x_k / u_kk) out of itself, a DIVISION per use, the
     stored x_k staying undivided; then every row is divided by its own diagonal entry.  The precision is that of F; whether a product and
     a difference are contracted into one fused operation is the compiler's choice and is not restated (it moves single roundings, and
-    nothing where every operation is exact)."""
+    nothing where every operation is exact).
+    trans=True is bsubstitute<T, true>: the same image read by rows, bf(i, k) = F[k, i] -- U^T, a NON-unit lower triangle, forward with
+    the division per use and the stored x_k undivided, then every row divided by its diagonal entry, then L^T (unit) backward.
+    mutation (tests/test_batched_solve_cases.py): "backward_skips_last_column" starts the backward sweep at column n - 2,
+    "no_final_division" leaves every row undivided."""
     n = F.shape[0]
+    T = F.T if trans else F                               # T[i, k] = bf<T, TRANS>(s, ld, i, k)
+    diag = np.diagonal(F)
+    top = n - 2 if mutation == "backward_skips_last_column" else n - 1
     with np.errstate(all="ignore"):
         for k in range(n):
-            x[k + 1:] -= F[k + 1:, k:k + 1] * x[k:k + 1]
-        for k in range(n - 1, -1, -1):
-            xk = x[k:k + 1] / F[k, k]
-            x[:k] -= F[:k, k:k + 1] * xk
-        x /= np.diagonal(F)[:, None]
+            xk = x[k:k + 1] / diag[k] if trans else x[k:k + 1]
+            x[k + 1:] -= T[k + 1:, k:k + 1] * xk
+        if trans and mutation != "no_final_division":
+            x /= diag[:, None]
+        for k in range(top, -1, -1):
+            xk = x[k:k + 1] if trans else x[k:k + 1] / diag[k]
+            x[:k] -= T[:k, k:k + 1] * xk
+        if not trans and mutation != "no_final_division":
+            x /= diag[:, None]
 
 
 def batched_restatement(F, ipiv, row_major=False, passes=True, inverse_perm=False, swap_store=False, ignore_p1=False):

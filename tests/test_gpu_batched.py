@@ -8,7 +8,8 @@ reference bound -- no input sits on a rounding fork).  Factors: check_against_or
 test/runtests.jl:19-20; factors within 50x that, scaled; NoPivot on rand + 10 I: 10 sqrt(E)).  max |l_ij| <= 1 exactly with pivoting.
 Solves: rand + 10 I: ||A x - b|| < 1000 n eps(T), test/runtests.jl:124-126; plain rand, Float64: both bounds of
 test_gpu_ldiv_adjoint.py::test_adjoint_solve_against_numpy -- LAPACK dgetrs on the same inputs (n = 8 .. 128, 200 matrices, nrhs 1
-and 5, both directions): worst residual 5.2e-5 of its bound, worst solution error 1.9e-12 against 1e-6."""
+and 5, both directions): worst residual 5.2e-5 of its bound, worst solution error 1.9e-12 against 1e-6.
+The solves are held to exact and rounding-level references, padded storage included, in tests/test_gpu_batched_solve_exact.py."""
 import ctypes
 import functools
 import time
