@@ -244,6 +244,69 @@ int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, c
                                int row_major, const int64_t* ipiv_dev, int64_t stride_ipiv, float* Ainv_dev, int64_t ldi,
                                int64_t strideI, int64_t* info_dev);
 
+/* ---- NORMS, CONDITION: what LAPACK pairs with getrf (lange + gecon) and Julia's cond(A, 1) / cond(A, Inf) is made of: the operator
+ * norm of A BEFORE the factorization overwrites it, then an estimate of rcond = 1 / (||A|| ||A^-1||) from the packed factors alone.
+ * Float64 / Float32 only (not complex).  Kernels: csrc/condest.hip and gecon_batched_kernel in csrc/batched.hip; DESIGN.md section 4.11.
+ * Every sum is formed in Float64 for both element types, in a fixed order -- no read-modify-write on shared words, partial sums per
+ * chunk, the chunks combined in index order -- so results are bit-identical from run to run.  Work goes on the handle's stream and is
+ * complete on return (the batched lange entry included).
+ *
+ * rflu_lange_*: norm = RFLU_NORM_ONE (largest column sum of |a_ij|) or RFLU_NORM_INF (largest row sum); any other value is
+ * RFLU_ERR_ARG.  A is m x n, element (i, j) at [i + j*lda] (row_major = 0, lda >= m) or [i*lda + j] (row_major = 1, lda >= n); it is
+ * read once, lanes along the contiguous dimension, in 16-byte loads where the pointer and lda allow and element by element otherwise --
+ * the same sums either way.  Padding behind a column / row is never read.  A NaN anywhere gives NaN (LAPACK lange), an Inf gives Inf;
+ * m == 0 or n == 0 gives 0.  *out: host, required.  The batched entry (matrix b at A_dev + b*strideA; out_dev: DEVICE array of `batch`
+ * doubles) runs one workgroup per matrix up to max(m, n) <= 128 and the single entry's kernels per matrix above, and agrees with the
+ * single entry on the same matrix bit for bit. */
+enum rflu_norm { RFLU_NORM_ONE = 1, RFLU_NORM_INF = 2 };
+int rflu_lange_f64_dev(rflu_handle_t handle, int norm, int64_t m, int64_t n, const double* A_dev, int64_t lda, int row_major,
+                       double* out);
+int rflu_lange_f32_dev(rflu_handle_t handle, int norm, int64_t m, int64_t n, const float* A_dev, int64_t lda, int row_major,
+                       double* out);
+int rflu_lange_batched_f64_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t m, int64_t n, const double* A_dev, int64_t lda,
+                               int64_t strideA, int row_major, double* out_dev);
+int rflu_lange_batched_f32_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t m, int64_t n, const float* A_dev, int64_t lda,
+                               int64_t strideA, int row_major, double* out_dev);
+/* rflu_gecon_*: *rcond_out (host, required) = 1 / (anorm * est), est an estimate (a lower bound up to rounding) of ||A^-1|| in the norm
+ * `norm`; anorm = that norm of A, from rflu_lange_* before the factorization.  There is no ipiv argument, as in LAPACK: with A = P^T L U,
+ * ||A^-1||_1 = ||U^-1 L^-1 P||_1 = ||U^-1 L^-1||_1, and the same holds for the Inf norm.  F is ONLY READ (packed L\U as rflu_getrf_* /
+ * rflu_getrf_rm_* left it; the host entry: H2D, then the device entry).
+ *   - The estimator is Higham's (LAPACK xLACN2, at most 5 iterations) on M = U^-1 L^-1, with TWO DELIBERATE DIFFERENCES from LAPACK that
+ *     make every vector entering a solve a vector of small integers: (1) the start vector is all ones and the first estimate is
+ *     sum|v_i| / n (LAPACK starts from 1/n); (2) the closing alternating vector is x_i = (-1)^i (n - 1 + i), i = 0 .. n-1, and its bound
+ *     2 sum|v_i| / (3 n (n - 1)) (LAPACK: 1 + i/(n-1) and 2 sum / (3n)).  n = 1: the estimate is |v_0| of the first solve.  The control
+ *     flow is xLACN2's: sign(v) = v >= 0 ? +1 : -1; stop on a repeated sign vector; stop when est <= est_old; j = the FIRST index of
+ *     max|x_i|; stop when |x_jlast| == |x_j|; the result is the larger of the iteration's estimate and the alternating-vector bound.
+ *     For RFLU_NORM_INF, M and M^T swap roles.  At most 11 solves with one right-hand side, 2n^2 flops each.
+ *   - One layout change per call: the row-major image of column-major factors (the transposed image of row-major ones) is made once in
+ *     the handle's workspace; every M x runs on the row-major image and every M^T x on the transposed view through the cooperative chain
+ *     kernels of rflu_getrs_* / rflu_getrs_trans_* with ipiv = NULL.  Between two solves: fixed-order vector kernels (chunks of 1024, a
+ *     fixed tree, chunks in index order) and one read of a few scalars by the host.
+ *   - No scaling as in xLATRS: a non-finite estimate (overflow in the substitution) gives rcond = 0.
+ *   - n == 0: 1.  anorm NaN: NaN.  anorm == 0: 0.  An exactly zero u_ii: 0, before any solve is launched.  A NaN in the factors: NaN.
+ *     Where several apply the first in this order decides: factors with an exactly zero u_ii AND a NaN give 0, not NaN (single and
+ *     batched entries alike).
+ *     anorm < 0, norm not 1 / 2, lda < n, NULL pointers: RFLU_ERR_ARG.  n > 65536 (the transposed chain's limit): RFLU_ERR_ARG with a
+ *     message.
+ *   - The handle's workspaces are shared with the other entries and refilled by each of them: a solve, an inverse or a factorization
+ *     after rflu_gecon_* on the same handle is bit-identical to one on a fresh handle.
+ * rflu_gecon_batched_*: the same for every matrix of a batch (matrix b at F_dev + b*strideF in either orientation; anorm_dev, rcond_dev:
+ * DEVICE arrays of `batch` doubles).  n <= 128: ONE launch, the factors in LDS once, the whole estimator inside the kernel (the
+ * batched substitutions of rflu_getrs_batched_* on one right-hand side), every group of a workgroup running the same number of rounds.
+ * Larger n: a loop over the single entry -- correct, NOT fast, no size cliff.  Special values per member as above, except that a
+ * member's anorm < 0 gives NaN in its own output; one member's NaN or singularity touches its own output only.  batch == 0: success;
+ * n == 0: every rcond is 1. */
+int rflu_gecon_f64_dev(rflu_handle_t handle, int norm, int64_t n, const double* F_dev, int64_t lda, double anorm, double* rcond_out);
+int rflu_gecon_f32_dev(rflu_handle_t handle, int norm, int64_t n, const float* F_dev, int64_t lda, double anorm, double* rcond_out);
+int rflu_gecon_rm_f64_dev(rflu_handle_t handle, int norm, int64_t n, const double* R_dev, int64_t ld, double anorm, double* rcond_out);
+int rflu_gecon_rm_f32_dev(rflu_handle_t handle, int norm, int64_t n, const float* R_dev, int64_t ld, double anorm, double* rcond_out);
+int rflu_gecon_f64(rflu_handle_t handle, int norm, int64_t n, const double* F_host, int64_t lda, double anorm, double* rcond_out);
+int rflu_gecon_f32(rflu_handle_t handle, int norm, int64_t n, const float* F_host, int64_t lda, double anorm, double* rcond_out);
+int rflu_gecon_batched_f64_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t n, const double* F_dev, int64_t lda,
+                               int64_t strideF, int row_major, const double* anorm_dev, double* rcond_dev);
+int rflu_gecon_batched_f32_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t n, const float* F_dev, int64_t lda,
+                               int64_t strideF, int row_major, const double* anorm_dev, double* rcond_dev);
+
 /* ---- COMPLEX: lu! / ldiv! for ComplexF64 / ComplexF32 (suffixes _cf64 / _cf32; csrc/complex.hip, csrc/complex_gemm.hip,
  * csrc/complex_solve.hip, DESIGN.md sections 4.5 and 4.6).  The reference's lu! with a complex element type (src/lu.jl:97-130, :189-263, :290-338; test/runtests.jl:33-84).
  * A complex array crosses the boundary as double* / float* pointing at INTERLEAVED (re, im) pairs, the storage of Julia's Complex{T}

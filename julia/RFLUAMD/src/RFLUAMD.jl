@@ -495,6 +495,127 @@ function logabsdet_batched_dev!(logabs::Ptr{Float64}, sign::Ptr{Float64}, F::Ptr
     return nothing
 end
 
+# `p` of the norm entries as the C enum rflu_norm
+function norm_code(p::Real)
+    p == 1 && return Cint(1)
+    p == Inf && return Cint(2)
+    throw(ArgumentError("p must be 1 or Inf, got $p"))
+end
+
+"""
+    lange_dev(A, m, n, lda; p = 1, row_major = false) -> Float64
+    gecon_dev!(F, n, ld, anorm; p = 1, row_major = false) -> Float64
+    gecon_host(F, anorm; p = 1) -> Float64
+    gecon_batched_dev!(rcond, F, batch, n, lda, strideF, row_major, anorm; p = 1)
+
+Operator norm and reciprocal condition number on device memory (`rflu_lange_*_dev`, `rflu_gecon_*`): `p` is `1` or `Inf`; `anorm` is the
+norm of `A` in the same `p`, taken BEFORE the factorization.  Float64 sums in a fixed order for both element types.  The estimator is
+Higham's (LAPACK `gecon`) with an all-ones start vector and an integer closing vector (include/rflu.h); the factors are only read.
+The batched form takes DEVICE pointers to `batch` Float64 values for `anorm` and `rcond`.
+"""
+function lange_dev(A::Ptr{Float64}, m::Integer, n::Integer, lda::Integer; p::Real = 1, row_major::Bool = false)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_lange_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float64}, Int64, Cint, Ptr{Float64}),
+               handle(), norm_code(p), m, n, A, lda, Cint(row_major), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function lange_dev(A::Ptr{Float32}, m::Integer, n::Integer, lda::Integer; p::Real = 1, row_major::Bool = false)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_lange_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float32}, Int64, Cint, Ptr{Float64}),
+               handle(), norm_code(p), m, n, A, lda, Cint(row_major), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+"`lange_batched_dev!(out, A, batch, m, n, lda, strideA, row_major; p = 1)`: the norm of every matrix of a batch into the DEVICE array `out`"
+function lange_batched_dev!(out::Ptr{Float64}, A::Ptr{Float64}, batch::Integer, m::Integer, n::Integer, lda::Integer, strideA::Integer,
+                            row_major::Bool; p::Real = 1)
+    st = ccall((:rflu_lange_batched_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Float64}),
+               handle(), norm_code(p), batch, m, n, A, lda, strideA, Cint(row_major), out)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function lange_batched_dev!(out::Ptr{Float64}, A::Ptr{Float32}, batch::Integer, m::Integer, n::Integer, lda::Integer, strideA::Integer,
+                            row_major::Bool; p::Real = 1)
+    st = ccall((:rflu_lange_batched_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Float64}),
+               handle(), norm_code(p), batch, m, n, A, lda, strideA, Cint(row_major), out)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function gecon_dev!(F::Ptr{Float64}, n::Integer, ld::Integer, anorm::Real; p::Real = 1, row_major::Bool = false)
+    out = zeros(Float64, 1)
+    st = if row_major
+        GC.@preserve out ccall((:rflu_gecon_rm_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float64}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), n, F, ld, Cdouble(anorm), pointer(out, 1))
+    else
+        GC.@preserve out ccall((:rflu_gecon_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float64}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), n, F, ld, Cdouble(anorm), pointer(out, 1))
+    end
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function gecon_dev!(F::Ptr{Float32}, n::Integer, ld::Integer, anorm::Real; p::Real = 1, row_major::Bool = false)
+    out = zeros(Float64, 1)
+    st = if row_major
+        GC.@preserve out ccall((:rflu_gecon_rm_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float32}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), n, F, ld, Cdouble(anorm), pointer(out, 1))
+    else
+        GC.@preserve out ccall((:rflu_gecon_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float32}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), n, F, ld, Cdouble(anorm), pointer(out, 1))
+    end
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function gecon_host(F::StridedMatrix{Float64}, anorm::Real; p::Real = 1)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_gecon_f64, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float64}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), size(F, 1), F, stride(F, 2), Cdouble(anorm), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function gecon_host(F::StridedMatrix{Float32}, anorm::Real; p::Real = 1)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_gecon_f32, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float32}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), size(F, 1), F, stride(F, 2), Cdouble(anorm), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function gecon_batched_dev!(rcond::Ptr{Float64}, F::Ptr{Float64}, batch::Integer, n::Integer, lda::Integer, strideF::Integer, row_major::Bool,
+                            anorm::Ptr{Float64}; p::Real = 1)
+    st = ccall((:rflu_gecon_batched_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Float64}, Ptr{Float64}),
+               handle(), norm_code(p), batch, n, F, lda, strideF, Cint(row_major), anorm, rcond)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function gecon_batched_dev!(rcond::Ptr{Float64}, F::Ptr{Float32}, batch::Integer, n::Integer, lda::Integer, strideF::Integer, row_major::Bool,
+                            anorm::Ptr{Float64}; p::Real = 1)
+    st = ccall((:rflu_gecon_batched_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Float64}, Ptr{Float64}),
+               handle(), norm_code(p), batch, n, F, lda, strideF, Cint(row_major), anorm, rcond)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
 # ---- inv! / logabsdet from ComplexF64 / ComplexF32 factors (rflu_getri_c* / rflu_logabsdet_c*, csrc/complex_inverse.hip): the methods of
 # getri! / getri_dev! / logabsdet_dev / logabsdet_host / logabsdet_batched_dev! for the complex pointer and matrix types.  Column-major
 # only (there is no row-major complex entry); the sign is det / |det|, a ComplexF64 (batched: `sign` points at `batch` ComplexF64 values).
@@ -699,6 +820,17 @@ function det(F::LU{T, <:StridedMatrix{T}}) where {T <: GPUEltype}
     lu_on_gpu(F) || return LinearAlgebra.det(F)
     la, sg = logabsdet(F)
     return iszero(sg) ? zero(T) : sg * exp(la)
+end
+
+"""
+    rcond(F::LU, anorm; p = 1)
+
+`1 / (opnorm(A, p) * opnorm(inv(A), p))` estimated from the factors on the GPU (LAPACK gecon; `anorm = opnorm(A, p)` taken before
+`lu!`), `p` 1 or Inf; the stdlib's `LAPACK.gecon!` where the GPU path does not apply.
+"""
+function rcond(F::LU{T, <:StridedMatrix{T}}, anorm::Real; p::Real = 1) where {T <: GPUEltype}
+    lu_on_gpu(F) || return LinearAlgebra.LAPACK.gecon!(p == 1 ? '1' : 'I', copy(F.factors), T(anorm))
+    return GC.@preserve F gecon_host(F.factors, anorm; p = p)
 end
 
 # the complex element types: the same three on the GPU.  The sign is the unit complex number det / |det|; adjoint / transpose wrappers of

@@ -8,6 +8,8 @@ from ._ffi import Handle, RfluError, default_handle  # noqa: F401
 from .lu import (  # noqa: F401
     LU,
     BatchedLU,
+    cond,
+    cond_batched,
     MixedLU,
     NotConvergedError,
     NOPIVOT_NEGATIVE_INFO,
@@ -54,6 +56,10 @@ from .lu import (  # noqa: F401
     lu_complex_mixed,
     lu_mixed,
     normalize_pivot,
+    opnorm,
+    opnorm_batched,
+    rcond,
+    rcond_batched,
 )
 
 from .butterfly import (  # noqa: F401,E402
@@ -74,5 +80,6 @@ __all__ = [
     "inv", "inv_", "det", "logabsdet", "logdet", "inv_batched", "logabsdet_batched", "det_batched",
     "inv_complex", "inv_complex_", "det_complex", "logabsdet_complex", "logdet_complex", "logabsdet_complex_batched", "det_complex_batched",
     "inv_complex_batched",
+    "opnorm", "rcond", "cond", "opnorm_batched", "rcond_batched", "cond_batched",
     "normalize_pivot", "last_path", "Handle", "RfluError", "default_handle", "NOPIVOT_NEGATIVE_INFO",
 ]

@@ -42,6 +42,13 @@ _TYPED = {
     "rflu_getri_rm_{s}_dev": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "rflu_getri_{s}": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "rflu_getri_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_p]),
+    # operator norms (before the factorization) and the condition estimate from the factors: `norm` is NORM_ONE / NORM_INF
+    "rflu_lange_{s}_dev": (c_int, [c_p, c_int, c_i64, c_i64, c_p, c_i64, c_int, c_p]),
+    "rflu_lange_batched_{s}_dev": (c_int, [c_p, c_int, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p]),
+    "rflu_gecon_{s}_dev": (c_int, [c_p, c_int, c_i64, c_p, c_i64, c_dbl, c_p]),
+    "rflu_gecon_rm_{s}_dev": (c_int, [c_p, c_int, c_i64, c_p, c_i64, c_dbl, c_p]),
+    "rflu_gecon_{s}": (c_int, [c_p, c_int, c_i64, c_p, c_i64, c_dbl, c_p]),
+    "rflu_gecon_batched_{s}_dev": (c_int, [c_p, c_int, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_p]),
     "rflu_panel_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_p]),
     "rflu_laswp_rm_{s}_dev": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64]),
     "rflu_trsm_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64]),
@@ -123,6 +130,7 @@ K_GEMM, K_TRSM, K_LASWP, K_PANEL, K_TRANSPOSE, K_MISC = range(6)
 KCLASS_NAMES = ["gemm", "trsm", "laswp", "panel", "transpose", "misc", "gemm_small", "laswp_wide"]
 PATH_NONE, PATH_HIP_RECURSIVE, PATH_HIP_BLOCKED, PATH_HIP_LOOKAHEAD = 0, 1, 2, 3
 PATH_HIP_ENGINE, PATH_HIP_BATCHED = 4, 5
+NORM_ONE, NORM_INF = 1, 2   # enum rflu_norm
 
 _lib = None
 

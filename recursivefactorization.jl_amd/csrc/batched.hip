@@ -393,9 +393,234 @@ __global__ void __launch_bounds__(BT) getri_batched_kernel(BInvArgs<T> a)
     }
 }
 
+// ---- the batched condition estimate (rflu_gecon_batched_*) ------------------------------------------------------
+template <typename T>
+struct BCondArgs {
+    const T* F;
+    const double* anorm;
+    double* rcond;
+    int64_t lda, strideF, batch;
+    int n, row_major, norm;
+    BGeo g;
+};
+
+struct BStat {
+    double sum, maxabs, xj;
+    int argmax, differs, nonfinite;
+};
+
+// The statistics of the group's work vector xs[0 .. n), the same in every thread of the group.  Thread t < n holds x_t (these are the
+// threads with column slice 0, in the group's first wave, or its first two for n > 64).  sum|x_t| is added by the tree t += t + s,
+// s = 64 .. 1 -- the tree of cond_stats_kernel (condest.hip) on one chunk, whose steps s = 128 and, for n <= 64, s = 64 add +0.0 --; the
+// first index of max|x_t| and the two flags do not depend on an order.  sc: the group's scratch (3 doubles, 131 for n > 64).
+// Barriers: two (three for n > 64), under no condition but n, which the whole workgroup shares.
+template <typename T>
+__device__ __forceinline__ BStat bstats(const T* xs, const T* sg, double* sc, int n, int t, int jq)
+{
+    const int lane = t & 63, w = t >> 6;
+    int* si = reinterpret_cast<int*>(sc + 1);
+    double v = 0.0, av = -1.0;
+    int ai = lane, df = 0, nf = 0;
+    if (t < n) {
+        const T xv = xs[t];
+        v = __builtin_fabs((double)xv);
+        av = v;
+        ai = t;
+        nf = !(v < __builtin_inf());
+        df = (xv >= T(0) ? T(1) : T(-1)) != sg[t];
+    }
+    bu64 bd = __ballot(df), bn = __ballot(nf);
+    if (n > 64) {
+        if (w == 1) {
+            sc[3 + lane] = v;
+            sc[67 + lane] = av;
+            if (lane == 0) { si[0] = bd != 0; si[1] = bn != 0; }
+        }
+        __syncthreads();
+        if (w == 0) {
+            v += sc[3 + lane];
+            const double a1 = sc[67 + lane];
+            if (a1 > av) { av = a1; ai = 64 + lane; }
+            if (si[0]) bd = 1;
+            if (si[1]) bn = 1;
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        v += __shfl_down(v, s, 64);
+        const double oa = __shfl_xor(av, s, 64);
+        const int oi = __shfl_xor(ai, s, 64);
+        if (oa > av || (oa == av && oi < ai)) { av = oa; ai = oi; }
+    }
+    if (w == 0 && lane == 0) {
+        sc[0] = v;
+        sc[2] = av;
+        si[0] = ai;
+        si[1] = (bd != 0 ? 1 : 0) | (bn != 0 ? 2 : 0);
+    }
+    __syncthreads();
+    BStat r;
+    r.sum = sc[0];
+    r.maxabs = sc[2];
+    r.argmax = si[0];
+    r.differs = si[1] & 1;
+    r.nonfinite = (si[1] >> 1) & 1;
+    r.xj = __builtin_fabs((double)xs[jq]);
+    __syncthreads();   // everybody has read the scratch before its next writer comes
+    return r;
+}
+
+// Higham's estimator (LAPACK xLACN2 with the integer start and closing vectors of rflu.h) on M = U^-1 L^-1, wholly inside the kernel: the
+// factors go into LDS once (bload_matrix), bsubstitute<T, false> on one right-hand side is M x and bsubstitute<T, true> is M^T x; the
+// work vector, the previous sign vector and the scratch of bstats live in the 8-column x region of the solve's geometry.
+//
+// WHY NO GROUP CAN LEAVE ANOTHER ONE AT A BARRIER.  bsubstitute's barriers are workgroup-wide, a workgroup holds 4 / 2 / 1 matrices, and
+// the matrices need different numbers of estimator rounds.  So the code below has NO barrier under a condition that depends on a group's
+// state: every barrier stands in straight-line code of the round, inside bsubstitute / bstats (whose barrier counts depend on n alone,
+// and n is a kernel argument), or in loops whose trip count is n or the round counter.  The round loop is left through ONE test,
+// __syncthreads_or(act), whose result is the same in every thread of the workgroup; it runs at most 5 times.  What differs between
+// groups is only data: a finished group, a singular one and a group beyond the end of the batch (valid == false) run the same code with
+// nr = 0 right-hand sides (bsubstitute then touches nothing) and ignore the statistics, their estimate frozen.
+template <typename T>
+__global__ void __launch_bounds__(BT) gecon_batched_kernel(BCondArgs<T> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char bsmem[];
+    const BGeo g = a.g;
+    const int n = a.n, ld = g.ld;
+    const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1);
+    const int64_t b = (int64_t)blockIdx.x * (BT >> g.tpm_log) + grp;
+    const bool valid = b < a.batch;
+    unsigned char* base = bsmem + (size_t)grp * g.group_bytes;
+    T* s = reinterpret_cast<T*>(base);
+    T* xs = reinterpret_cast<T*>(base + g.off_x);       // the work vector ...
+    T* sg = xs + ld;                                     // ... the previous sign vector ...
+    double* sc = reinterpret_cast<double*>(xs + 2 * ld);   // ... and the scratch of bstats, 8-byte aligned: off_x is, and so is 2 * ld * sizeof(T)
+    int* si = reinterpret_cast<int*>(sc + 1);
+    const T* F = a.F + (valid ? b : 0) * a.strideF;
+
+    bload_matrix<T>(s, ld, F, a.lda, a.row_major, n, n, g, t, valid);
+    if (t == 0) { si[0] = 0; si[1] = 0; }
+    const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+    const bool own = c == 0 && r < n;   // this thread holds x_r (then r == t)
+    if (own) sg[r] = T(0);
+    __syncthreads();
+    {   // a NaN anywhere in the factors (bit 0), an exactly zero u_ii (bit 1): plain stores of the same value, whoever comes last
+        int f = 0;
+        if (r < n)
+            for (int j = c; j < n; j += cs) {
+                const T v = s[r + j * ld];
+                if (v != v) f |= 1;
+                if (j == r && v == T(0)) f |= 2;
+            }
+        if (f & 1) si[0] = 1;
+        if (f & 2) si[1] = 1;
+    }
+    __syncthreads();
+    const int scan = (si[0] ? 1 : 0) | (si[1] ? 2 : 0);
+    __syncthreads();
+
+    const bool inf_norm = a.norm == RFLU_NORM_INF;   // ||M||_inf = ||M^T||_1: M and M^T swap roles
+    bool act = valid && scan == 0, closing = false, bad = false;
+    double est = 0.0;
+    int j = 0;
+    for (int round = 0; round < 5; ++round) {
+        if (act && own) xs[r] = (round == 0 || r == j) ? T(1) : T(0);
+        __syncthreads();
+        if (inf_norm) bsubstitute<T, true>(s, xs, ld, n, act ? 1 : 0, r, c, cs);
+        else bsubstitute<T, false>(s, xs, ld, n, act ? 1 : 0, r, c, cs);
+        const BStat s1 = bstats<T>(xs, sg, sc, n, t, j);
+        if (act) {
+            if (s1.nonfinite) { bad = true; act = false; }
+            else if (round == 0) {
+                est = s1.sum / (double)n;
+                if (n == 1) act = false;
+            } else {
+                const double est_old = est;
+                est = s1.sum;
+                if (!s1.differs || est <= est_old) { act = false; closing = true; }
+            }
+        }
+        if (act && own) {
+            const T sv = xs[r] >= T(0) ? T(1) : T(-1);
+            sg[r] = sv;
+            xs[r] = sv;
+        }
+        __syncthreads();
+        if (inf_norm) bsubstitute<T, false>(s, xs, ld, n, act ? 1 : 0, r, c, cs);
+        else bsubstitute<T, true>(s, xs, ld, n, act ? 1 : 0, r, c, cs);
+        const BStat s2 = bstats<T>(xs, sg, sc, n, t, j);
+        if (act) {
+            if (s2.nonfinite) { bad = true; act = false; }
+            else {
+                j = s2.argmax;
+                if ((round > 0 && s2.xj == s2.maxabs) || round == 4) { act = false; closing = true; }
+            }
+        }
+        if (!__syncthreads_or(act ? 1 : 0)) break;
+    }
+    // the alternating vector's bound: every group runs the solve, those that do not need it with no right-hand side
+    if (closing && own) {
+        const T av = (T)(double)(n - 1 + r);
+        xs[r] = (r & 1) ? -av : av;
+    }
+    __syncthreads();
+    if (inf_norm) bsubstitute<T, true>(s, xs, ld, n, closing ? 1 : 0, r, c, cs);
+    else bsubstitute<T, false>(s, xs, ld, n, closing ? 1 : 0, r, c, cs);
+    const BStat s3 = bstats<T>(xs, sg, sc, n, t, 0);
+    if (closing) {
+        if (s3.nonfinite) bad = true;
+        else {
+            const double alt = 2.0 * s3.sum / (3.0 * (double)n * (double)(n - 1));
+            if (alt > est) est = alt;
+        }
+    }
+    if (valid && t == 0) {
+        const double an = a.anorm[b];
+        double rc;
+        if (an != an || an < 0.0) rc = __builtin_nan("");
+        else if (an == 0.0) rc = 0.0;
+        else if (scan & 2) rc = 0.0;
+        else if (scan & 1) rc = __builtin_nan("");
+        else if (bad || est == 0.0) rc = 0.0;
+        else rc = 1.0 / (an * est);
+        a.rcond[b] = rc;
+    }
+}
+
 }  // namespace
 
 bool batched_fits(int64_t m, int64_t n) { return std::max(m, n) <= BATCHED_MAX_DIM; }
+
+template <typename T>
+int launch_gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major,
+                         const double* anorm, double* rcond)
+{
+    BCondArgs<T> a;
+    a.F = F; a.anorm = anorm; a.rcond = rcond;
+    a.lda = lda; a.strideF = strideF; a.batch = batch;
+    a.n = (int)n; a.row_major = row_major; a.norm = norm;
+    a.g = batched_geo(n, n, sizeof(T), true, false);
+    // launch_batched's bookkeeping (Handle::batched_attr_set) has no row for a fourth kernel: the same launch with a flag of its own
+    const int groups = BT / a.g.tpm;
+    const size_t lds = (size_t)groups * a.g.group_bytes;
+    // The kernel also holds 256 bytes of static LDS (the word behind __syncthreads_or), so asking for all 160 KiB as dynamic memory is
+    // refused: ask once for what the largest launch needs (n = 128, one group: 138 KiB in Float64), the same value from every handle.
+    const BGeo gmax = batched_geo(BATCHED_MAX_DIM, BATCHED_MAX_DIM, sizeof(T), true, false);
+    const size_t lds_max = std::max(lds, (size_t)(BT / gmax.tpm) * gmax.group_bytes);
+    size_t* asked = &h->gecon_lds_asked[sizeof(T) == 4 ? 1 : 0];
+    if (lds > 64 * 1024 && *asked == 0) {
+        RFLU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gecon_batched_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        *asked = lds_max;
+    }
+    const int64_t wgs = (batch + groups - 1) / groups;
+    ProfScope ps(h, RFLU_K_TRSM, 22.0 * (double)batch * (double)n * (double)n, (double)batch * (double)n * (double)n * sizeof(T));
+    hipLaunchKernelGGL(gecon_batched_kernel<T>, dim3((unsigned)wgs), dim3(BT), lds, h->stream, a);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+template int launch_gecon_batched<double>(Handle*, int, int64_t, int64_t, const double*, int64_t, int64_t, int, const double*, double*);
+template int launch_gecon_batched<float>(Handle*, int, int64_t, int64_t, const float*, int64_t, int64_t, int, const double*, double*);
 
 template <typename T>
 int launch_getrf_batched(Handle* h, int64_t batch, int64_t m, int64_t n, T* A, int64_t lda, int64_t strideA, int row_major,

@@ -636,6 +636,174 @@ static int getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_
     return RFLU_OK;
 }
 
+// ---- operator norms and the condition estimate (include/rflu.h: NORMS, CONDITION; kernels: condest.hip) --------
+static bool norm_ok(const char* who, int norm)
+{
+    if (norm == RFLU_NORM_ONE || norm == RFLU_NORM_INF) return true;
+    set_error("%s: norm must be RFLU_NORM_ONE (1) or RFLU_NORM_INF (2), got %d", who, norm);
+    return false;
+}
+
+template <typename T>
+static int lange_dev(Handle* h, int norm, int64_t m, int64_t n, const T* A, int64_t lda, int row_major, double* out)
+{
+    if (!norm_ok("lange", norm)) return RFLU_ERR_ARG;
+    if (m < 0 || n < 0 || out == nullptr || lda < std::max<int64_t>(row_major ? n : m, 1) || (m > 0 && n > 0 && A == nullptr)) {
+        set_error("lange: bad arguments m=%lld n=%lld lda=%lld (or a null pointer)", (long long)m, (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    return launch_lange<T>(h, norm, m, n, A, lda, row_major, out);
+}
+
+template <typename T>
+static int lange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const T* A, int64_t lda, int64_t strideA, int row_major,
+                         double* out_dev)
+{
+    if (!norm_ok("lange_batched", norm)) return RFLU_ERR_ARG;
+    if (batch < 0 || m < 0 || n < 0) {
+        set_error("lange_batched: negative size batch=%lld m=%lld n=%lld", (long long)batch, (long long)m, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0) return RFLU_OK;
+    if (out_dev == nullptr || (m > 0 && n > 0 && A == nullptr)) { set_error("lange_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (m == 0 || n == 0) {
+        RFLU_HIP(hipMemsetAsync(out_dev, 0, (size_t)batch * sizeof(double), h->stream));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        return RFLU_OK;
+    }
+    const int64_t len = row_major ? n : m, cnt = row_major ? m : n;
+    if (lda < len || (batch > 1 && strideA < (cnt - 1) * lda + len)) {
+        set_error("lange_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", (long long)lda, (long long)strideA, (long long)m,
+                  (long long)n, row_major ? "row-major" : "column-major");
+        return RFLU_ERR_ARG;
+    }
+    RFLU_TRY(launch_lange_batched<T>(h, norm, batch, m, n, A, lda, strideA, row_major, out_dev));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+// rcond = 1 / (anorm * est): Higham's estimator (LAPACK xLACN2 with the integer start and closing vectors stated in rflu.h) on
+// M = U^-1 L^-1.  ONE layout change per call: W = the transposed image of F in h->work.  Column-major factors: W is their row-major
+// image, every M x is getrs_rm on W and every M^T x is getrs_trans_view on F in place; row-major factors: M x is getrs_rm on F in place
+// and M^T x is getrs_trans_view on W.  The work vector stays in the row-major n x 1 form the chain kernels take (ldb = 1).
+template <typename T>
+int gecon_dev(Handle* h, int norm, int64_t n, const T* F, int64_t ld, int row_major, double anorm, double* rcond)
+{
+    if (!norm_ok("gecon", norm)) return RFLU_ERR_ARG;
+    if (n < 0 || ld < std::max<int64_t>(n, 1) || rcond == nullptr || (n > 0 && F == nullptr)) {
+        set_error("gecon: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
+        return RFLU_ERR_ARG;
+    }
+    if (anorm < 0.0) { set_error("gecon: anorm = %g is negative", anorm); return RFLU_ERR_ARG; }
+    if (n > (int64_t)NB * 256 * 4) {
+        set_error("gecon: n = %lld exceeds the %d rows the cooperative transposed solve covers", (long long)n, NB * 256 * 4);
+        return RFLU_ERR_ARG;
+    }
+    *rcond = 0.0;
+    if (n == 0) { *rcond = 1.0; return RFLU_OK; }
+    if (anorm != anorm) { *rcond = anorm; return RFLU_OK; }
+    if (anorm == 0.0) return RFLU_OK;
+    int64_t zero1 = 0;
+    RFLU_TRY(launch_logabsdet<T>(h, n, F, ld + 1, nullptr, nullptr, nullptr, &zero1));
+    if (zero1 != 0) return RFLU_OK;   // an exactly zero u_ii: rcond = 0 before any solve is launched
+
+    const int64_t ldw = workspace_ld(h, n);
+    RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldw * sizeof(T)));
+    RFLU_TRY(ensure_buffer(&h->cond_work, &h->cond_work_bytes, 2 * (size_t)n * sizeof(T)));
+    T* W = static_cast<T*>(h->work);
+    T* x = static_cast<T*>(h->cond_work);
+    T* sgn = x + n;
+    RFLU_TRY(launch_transpose<T>(h, n, n, F, ld, W, ldw));
+    RFLU_HIP(hipMemsetAsync(sgn, 0, (size_t)n * sizeof(T), h->stream));
+    const T* RM = row_major ? F : W;
+    const T* V = row_major ? W : F;
+    const int64_t ldrm = row_major ? ld : ldw, ldv = row_major ? ldw : ld;
+    // ||M||_inf = ||M^T||_1: for the Inf norm M and M^T swap roles
+    auto apply = [&](bool transposed) -> int {
+        if (transposed != (norm == RFLU_NORM_INF)) return getrs_trans_view<T>(h, n, 1, V, ldv, nullptr, x, 1);
+        return getrs_rm<T>(h, n, 1, RM, ldrm, nullptr, x, 1);
+    };
+    CondStats st;
+    double est = 0.0;
+    bool bad = false, closing = false;
+    int64_t j = 0;
+    for (int round = 0; round < 5; ++round) {
+        RFLU_TRY(launch_cond_fill<T>(h, n, x, round == 0 ? COND_FILL_ONES : COND_FILL_UNIT, j));
+        RFLU_TRY(apply(false));
+        RFLU_TRY(launch_cond_stats<T>(h, n, x, sgn, -1, 1, &st));   // x and sgn hold sign(x) afterwards
+        if (st.nonfinite) { bad = true; break; }
+        if (round == 0) {
+            est = st.sum / (double)n;
+            if (n == 1) break;
+        } else {
+            const double est_old = est;
+            est = st.sum;
+            if (st.differs == 0 || est <= est_old) { closing = true; break; }
+        }
+        RFLU_TRY(apply(true));
+        RFLU_TRY(launch_cond_stats<T>(h, n, x, sgn, j, 0, &st));
+        if (st.nonfinite) { bad = true; break; }
+        j = (int64_t)st.argmax;
+        if ((round > 0 && st.xj_abs == st.maxabs) || round == 4) { closing = true; break; }
+    }
+    if (closing) {
+        RFLU_TRY(launch_cond_fill<T>(h, n, x, COND_FILL_ALT, 0));
+        RFLU_TRY(apply(false));
+        RFLU_TRY(launch_cond_stats<T>(h, n, x, sgn, -1, 0, &st));
+        if (st.nonfinite) bad = true;
+        else {
+            const double alt = 2.0 * st.sum / (3.0 * (double)n * (double)(n - 1));
+            if (alt > est) est = alt;
+        }
+    }
+    if (bad) {   // overflow in the substitution gives 0; a NaN in the factors (a norm keeps it) gives NaN
+        double fnorm = 0.0;
+        RFLU_TRY(launch_lange<T>(h, RFLU_NORM_ONE, n, n, F, ld, 0, &fnorm));
+        *rcond = (fnorm != fnorm) ? fnorm : 0.0;
+        return RFLU_OK;
+    }
+    *rcond = est == 0.0 ? 0.0 : 1.0 / (anorm * est);
+    return RFLU_OK;
+}
+
+template <typename T>
+static int gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major,
+                         const double* anorm_dev, double* rcond_dev)
+{
+    if (!norm_ok("gecon_batched", norm)) return RFLU_ERR_ARG;
+    if (batch < 0 || n < 0) {
+        set_error("gecon_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0) return RFLU_OK;
+    if (rcond_dev == nullptr || (n > 0 && (F == nullptr || anorm_dev == nullptr))) { set_error("gecon_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (n > 0 && (lda < n || (batch > 1 && strideF < (n - 1) * lda + n))) {
+        set_error("gecon_batched: lda=%lld strideF=%lld too small for n=%lld", (long long)lda, (long long)strideF, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    std::vector<double> host((size_t)batch, 1.0);
+    if (n == 0) {   // the empty matrix: rcond = 1
+        RFLU_HIP(hipMemcpyAsync(rcond_dev, host.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        return RFLU_OK;
+    }
+    if (batched_fits(n, n)) {
+        RFLU_TRY(launch_gecon_batched<T>(h, norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        return RFLU_OK;
+    }
+    RFLU_HIP(hipMemcpyAsync(host.data(), anorm_dev, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    for (int64_t b = 0; b < batch; ++b) {
+        const double an = host[(size_t)b];
+        if (an < 0.0) { host[(size_t)b] = std::nan(""); continue; }   // a member's bad anorm spoils its own output only
+        RFLU_TRY(gecon_dev<T>(h, norm, n, F + b * strideF, lda, row_major, an, &host[(size_t)b]));
+    }
+    RFLU_HIP(hipMemcpyAsync(rcond_dev, host.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 // the complex batched inverse (kernel: batched_complex.hip): Ainv_b <- inv(op(A_b)), op by trans = 0 / 1 / 2.
 // Above the one-launch limit, column-major only: the real loop's steps on the single-matrix complex getri, then for 'T' / 'C' one layout
 // change of the result through the handle's workspace (conjugating for 'C') and a copy back -- correct, not fast.
@@ -934,7 +1102,8 @@ static int cmixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int
     template int trsm_public<T>(Handle*, int64_t, int64_t, const T*, int64_t, T*, int64_t);                                           \
     template int getrs_cm_dev<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t);                          \
     template int getrs_trans_cm_dev<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t);                    \
-    template int getri_cm_dev<T>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);
+    template int getri_cm_dev<T>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);                                            \
+    template int gecon_dev<T>(Handle*, int, int64_t, const T*, int64_t, int, double, double*);
 RFLU_INSTANTIATE_DRIVER(double)
 RFLU_INSTANTIATE_DRIVER(float)
 
@@ -956,7 +1125,7 @@ static Handle* H(rflu_handle_t h) { return reinterpret_cast<Handle*>(h); }
 
 extern "C" {
 
-int rflu_version(void) { return 108; }
+int rflu_version(void) { return 109; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -1044,6 +1213,7 @@ int rflu_destroy(rflu_handle_t handle)
     if (h->mixed_norms_host) (void)hipHostFree(h->mixed_norms_host);
     if (h->inv_work) (void)hipFree(h->inv_work);
     if (h->inv_part) (void)hipFree(h->inv_part);
+    if (h->cond_work) (void)hipFree(h->cond_work);
     if (h->pm_cnt) (void)hipFree(h->pm_cnt);
     if (h->pm_dst) (void)hipFree(h->pm_dst);
     if (h->pm_src) (void)hipFree(h->pm_src);
@@ -1311,6 +1481,43 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
         CHECK_HANDLE(handle);                                                                                         \
         return getri_batched<T>(H(handle), batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi,        \
                                 strideI, info_dev);                                                                   \
+    }                                                                                                                 \
+    int rflu_lange_##SFX##_dev(rflu_handle_t handle, int norm, int64_t m, int64_t n, const T* A, int64_t lda,          \
+                               int row_major, double* out)                                                            \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return lange_dev<T>(H(handle), norm, m, n, A, lda, row_major, out);                                           \
+    }                                                                                                                 \
+    int rflu_lange_batched_##SFX##_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t m, int64_t n,           \
+                                       const T* A, int64_t lda, int64_t strideA, int row_major, double* out_dev)      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return lange_batched<T>(H(handle), norm, batch, m, n, A, lda, strideA, row_major, out_dev);                   \
+    }                                                                                                                 \
+    int rflu_gecon_##SFX##_dev(rflu_handle_t handle, int norm, int64_t n, const T* F, int64_t lda, double anorm,      \
+                               double* rcond_out)                                                                     \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return gecon_dev<T>(H(handle), norm, n, F, lda, 0, anorm, rcond_out);                                         \
+    }                                                                                                                 \
+    int rflu_gecon_rm_##SFX##_dev(rflu_handle_t handle, int norm, int64_t n, const T* R, int64_t ld, double anorm,    \
+                                  double* rcond_out)                                                                  \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return gecon_dev<T>(H(handle), norm, n, R, ld, 1, anorm, rcond_out);                                          \
+    }                                                                                                                 \
+    int rflu_gecon_##SFX(rflu_handle_t handle, int norm, int64_t n, const T* F, int64_t lda, double anorm,            \
+                         double* rcond_out)                                                                           \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return gecon_host<T>(H(handle), norm, n, F, lda, anorm, rcond_out);                                           \
+    }                                                                                                                 \
+    int rflu_gecon_batched_##SFX##_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t n, const T* F,          \
+                                       int64_t lda, int64_t strideF, int row_major, const double* anorm_dev,          \
+                                       double* rcond_dev)                                                             \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return gecon_batched<T>(H(handle), norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev);         \
     }                                                                                                                 \
     int rflu_fill_uniform_##SFX##_dev(rflu_handle_t handle, T* A, int64_t m, int64_t n, int64_t ld, int row_major,    \
                                       uint64_t seed, int64_t M_global, int64_t i0, int64_t j0, double diag_add)       \

@@ -38,6 +38,7 @@ template <typename T> int trsm_public(Handle* h, int64_t n, int64_t nrhs, const 
 template <typename T> int getrs_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb);
 template <typename T> int getrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb);
 template <typename T> int getri_cm_dev(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info);
+template <typename T> int gecon_dev(Handle* h, int norm, int64_t n, const T* F, int64_t ld, int row_major, double anorm, double* rcond);
 
 // ---- streams.cpp ------------------------------------------------------------------------------------------------------------------
 int get_event(Handle* h, size_t idx, hipEvent_t* ev);   // the handle's reusable events (timing disabled), by number
@@ -62,5 +63,6 @@ template <typename T> int getrf_host(Handle* h, int64_t m, int64_t n, T* A, int6
 template <typename T> int getrs_host(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb, bool trans);
 template <typename T> int getri_host(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info);
 template <typename T> int logabsdet_host(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign);
+template <typename T> int gecon_host(Handle* h, int norm, int64_t n, const T* F, int64_t lda, double anorm, double* rcond);
 
 }  // namespace rflu

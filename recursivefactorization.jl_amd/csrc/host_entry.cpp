@@ -137,6 +137,22 @@ int getri_host(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int
     return RFLU_OK;
 }
 
+// rcond from host factors: H2D, then the device entry (which checks norm and anorm and serves the special values)
+template <typename T>
+int gecon_host(Handle* h, int norm, int64_t n, const T* F, int64_t lda, double anorm, double* rcond)
+{
+    if (n < 0 || lda < std::max<int64_t>(n, 1) || rcond == nullptr || (n > 0 && F == nullptr)) {
+        set_error("gecon: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    if (n == 0) return gecon_dev<T>(h, norm, 0, F, 1, 0, anorm, rcond);
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(T)));
+    T* dF = static_cast<T*>(h->hostA_dev);
+    RFLU_TRY(copy_in(dF, F, lda, n, n, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));   // the special values return without another wait: the caller's array is free by then
+    return gecon_dev<T>(h, norm, n, dF, n, 0, anorm, rcond);
+}
+
 // ---- the way back of the factors, overlapped with the factorization -------------------------------------------------------------------
 // Rows [0, r) of the factors are final as soon as every block column left of r has been applied everywhere (later interchanges only
 // touch rows below), and in the row-major workspace a block of rows is one contiguous piece.  Once the factorization is enqueued
@@ -530,7 +546,8 @@ int clogabsdet_host(Handle* h, int64_t n, const R* F, int64_t ld, const int64_t*
     template int getrf_host<T>(Handle*, int64_t, int64_t, T*, int64_t, int64_t*, int, int64_t, int64_t*);                             \
     template int getrs_host<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t, bool);                      \
     template int getri_host<T>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);                                              \
-    template int logabsdet_host<T>(Handle*, int64_t, const T*, int64_t, const int64_t*, double*, double*);
+    template int logabsdet_host<T>(Handle*, int64_t, const T*, int64_t, const int64_t*, double*, double*);                            \
+    template int gecon_host<T>(Handle*, int, int64_t, const T*, int64_t, double, double*);
 RFLU_INSTANTIATE_HOST(double)
 RFLU_INSTANTIATE_HOST(float)
 #define RFLU_INSTANTIATE_HOST_COMPLEX(R)                                                                                              \

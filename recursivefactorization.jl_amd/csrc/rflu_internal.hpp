@@ -205,6 +205,9 @@ struct Handle {
     size_t inv_work_bytes = 0;
     void* inv_part = nullptr;    // logabsdet: per-chunk partial sums, then {logabs, sign, first zero}
     size_t inv_part_bytes = 0;
+    // operator norms / condition estimate (condest.hip): the estimator's work vector and sign vector, per-chunk partial results
+    void* cond_work = nullptr;
+    size_t cond_work_bytes = 0;
 
     // pivot bookkeeping: for every chunk of NB pivots the list of (dst,src) row moves equivalent to its interchanges
     int* pm_cnt = nullptr;
@@ -243,6 +246,7 @@ struct Handle {
     bool eng_attr_set[2] = {false, false};    // same for the persistent update engine (engine.hip)
     bool batched_attr_set[3][4] = {};         // same for the batched kernels (batched_kernels.hpp): [getrf|getrs|getri][f64, f32, cf64, cf32]
     bool cinv_attr_set[2] = {false, false};   // same for the 64x64 triangular inverses of the complex getri (complex_inverse.hip): [cf64, cf32]
+    size_t gecon_lds_asked[2] = {0, 0};       // dynamic LDS asked for the batched condition estimate so far (batched.hip: gecon_batched_kernel): [f64, f32]
     void* eng_state = nullptr;                // device: EngState (engine.hpp)
     void* eng_host = nullptr;                 // pinned host image of its initial value
     long long* eng_trace_buf = nullptr;       // device: RFLU_ENGINE_TRACE stamps + workgroup-time accounting (measurement only)
@@ -461,6 +465,36 @@ int launch_logabsdet_batched(Handle* h, int64_t batch, int64_t n, const T* F, in
 // V: row-major n x n image of F^T, overwritten by A^-T; *info (host): first exactly-zero u_ii, V then untouched.  Complete on return.
 template <typename T>
 int getri_view(Handle* h, int64_t n, T* V, int64_t ld, const int64_t* ipiv, int64_t* info);
+
+// condest.hip: operator norms and the vector kernels of the condition estimate.  Every sum is Float64 in a fixed
+// order (no read-modify-write on shared words): results repeat bit for bit.
+// *out (host) = the 1- or Inf-norm of the m x n matrix A; element (i, j) at [i + j*lda] or (row_major) [i*lda + j].  Synchronises.
+template <typename T>
+int launch_lange(Handle* h, int norm, int64_t m, int64_t n, const T* A, int64_t lda, int row_major, double* out);
+// out_dev[b] (device) = the same for matrix b at A + b*strideA; one workgroup per matrix up to 128 x 128, the single kernels' strided
+// loop above; bit-identical to launch_lange on the same matrix.  Enqueued only.
+template <typename T>
+int launch_lange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const T* A, int64_t lda, int64_t strideA, int row_major,
+                         double* out_dev);
+// the estimator's vectors: x and sgn are n contiguous elements on the device
+struct CondStats {
+    double sum;        // sum of |x_i|, chunks of 1024 by a fixed tree, chunk sums in index order
+    double maxabs;     // max |x_i| ...
+    double xj_abs;     // |x[jq]| (0 when jq < 0)
+    long long argmax;  // ... and the FIRST index that attains it
+    int differs;       // number of i with sign(x_i) != sgn[i], sign(v) = v >= 0 ? +1 : -1
+    int nonfinite;     // a NaN or Inf among the x_i
+};
+enum { COND_FILL_ONES = 0, COND_FILL_UNIT = 1, COND_FILL_ALT = 2 };   // ones; e_j; x_i = (-1)^i (n - 1 + i)
+template <typename T>
+int launch_cond_fill(Handle* h, int64_t n, T* x, int mode, int64_t j);
+// the statistics of x (host, the stream is synchronised); write_sign: afterwards x and sgn hold sign(x)
+template <typename T>
+int launch_cond_stats(Handle* h, int64_t n, T* x, T* sgn, int64_t jq, int write_sign, CondStats* out);
+// batched.hip: the whole estimator on a matrix held in LDS, one launch for n <= BATCHED_MAX_DIM
+template <typename T>
+int launch_gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major,
+                         const double* anorm, double* rcond);
 
 // mixed.hip: the kernels of the mixed-precision solve.  A, X, B, R column-major Float64; F row-major Float32.
 constexpr int RESIDUAL_PASS = 8;   // right-hand sides per launch of residual_few

@@ -636,6 +636,115 @@ def logdet(F, *, handle=None) -> float:
     return la
 
 
+def _norm_code(p, what: str) -> int:
+    """``p`` of ``opnorm`` / ``rcond`` / ``cond``: 1, or ``math.inf`` / ``"inf"``; anything else raises ``ValueError``."""
+    if isinstance(p, str):
+        if p.lower() == "inf":
+            return _ffi.NORM_INF
+    elif isinstance(p, (int, float)) and not isinstance(p, bool):
+        if p == 1:
+            return _ffi.NORM_ONE
+        if p == float("inf"):
+            return _ffi.NORM_INF
+    raise ValueError(f"{what}: p must be 1 or inf (math.inf / \"inf\"), got {p!r}")
+
+
+def _cond_sfx(dtype, what: str) -> str:
+    if str(dtype).replace("torch.", "") in ("complex128", "complex64"):
+        raise TypeError(f"{what}: complex element types are not served yet (got {dtype}); Float64/Float32 only")
+    return _sfx(dtype)
+
+
+def _swap_norm(code: int) -> int:
+    return _ffi.NORM_INF if code == _ffi.NORM_ONE else _ffi.NORM_ONE
+
+
+def opnorm(A, p=1, *, handle=None) -> float:
+    """``opnorm(A, 1)`` / ``opnorm(A, Inf)``: the largest column / row sum of ``|a_ij|`` of an m x n matrix (LAPACK lange,
+    ``rflu_lange_*_dev``), as a Python float.  Float64 sums in a fixed order for both element types: bit-identical from run to run and
+    whatever the alignment.  ``A``: a column-major or row-major CUDA tensor, or a NumPy array (copied to the device).  A NaN anywhere
+    gives NaN; an empty matrix gives 0.  Take it BEFORE ``lu_`` overwrites ``A``: ``rcond`` needs it.  ``Adjoint(A)`` swaps 1 and inf."""
+    code = _norm_code(p, "opnorm")
+    if isinstance(A, Adjoint):
+        A, code = A.parent, _swap_norm(code)
+        if isinstance(A, Adjoint):
+            raise TypeError("opnorm of a doubly wrapped matrix: unwrap it first")
+    if getattr(A, "ndim", None) != 2:
+        raise ValueError("opnorm needs a matrix")
+    sfx = _cond_sfx(A.dtype, "opnorm")
+    m, n = int(A.shape[0]), int(A.shape[1])
+    if m == 0 or n == 0:
+        return 0.0
+    import torch
+
+    if not _is_torch(A):
+        if not isinstance(A, np.ndarray):
+            raise TypeError("A must be a numpy.ndarray or a CUDA torch.Tensor")
+        dev = torch.device("cuda", handle.device if handle is not None else 0)
+        if A.flags.f_contiguous and not A.flags.c_contiguous:   # a Fortran-ordered array stays column-major on the device
+            A = torch.from_numpy(np.ascontiguousarray(A.T)).to(dev).T
+        else:
+            A = torch.from_numpy(np.ascontiguousarray(A)).to(dev)
+    if not A.is_cuda:
+        raise _ffi.RfluError("torch input must live on the MI355X (device='cuda'); host data goes in as NumPy")
+    if A.stride(0) == 1 and (A.stride(1) >= m or n == 1):
+        row_major, ld = 0, (int(A.stride(1)) if n > 1 else m)
+    elif A.stride(1) == 1 and (A.stride(0) >= n or m == 1):
+        row_major, ld = 1, (int(A.stride(0)) if m > 1 else n)
+    else:
+        raise ValueError("opnorm: the matrix must be dense column-major or row-major (unit stride in one dimension)")
+    h = handle or _ffi.default_handle(A.device.index or 0)
+    h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+    out = ctypes.c_double(0.0)
+    h.call(f"rflu_lange_{sfx}_dev", code, m, n, ctypes.c_void_p(A.data_ptr()), ld, row_major, ctypes.byref(out))
+    return float(out.value)
+
+
+def rcond(F, anorm, p=1, *, handle=None) -> float:
+    """The reciprocal condition number ``1 / (||A|| ||inv(A)||)`` in the 1- or inf-norm from the factors (LAPACK gecon,
+    ``rflu_gecon_*``): ``anorm = opnorm(A, p)`` taken before the factorization, ``||inv(A)||`` estimated by Higham's method with at most
+    11 solves of one right-hand side -- 2n^2 flops each against 2n^3/3 for the factorization; ``F`` is only read.  The estimate is a
+    lower bound of ``||inv(A)||`` up to rounding, so ``rcond`` errs towards well-conditioned by a small factor at most.
+    Layouts as ``inv_``: column-major or row-major CUDA factors, or column-major NumPy factors.  ``n == 0`` gives 1, ``anorm == 0`` or an
+    exactly zero ``u_ii`` gives 0, a NaN ``anorm`` or a NaN in the factors gives NaN; ``anorm < 0`` raises.  ``Adjoint(F)`` swaps 1 and inf."""
+    code = _norm_code(p, "rcond")
+    F, adj = _unwrap_adjoint(F, "rcond")
+    if isinstance(F, LU) and F.factors is not None:
+        _cond_sfx(F.factors.dtype, "rcond")
+    A, n, sfx, kind, ld = _square_factors(F, "rcond")
+    if adj:
+        code = _swap_norm(code)
+    anorm = float(anorm)
+    if anorm < 0.0:
+        raise ValueError("rcond: anorm must not be negative")
+    if n == 0:
+        return 1.0
+    h, ap = _handle_for(A, kind, handle)
+    out = ctypes.c_double(0.0)
+    name = {"cm": f"rflu_gecon_{sfx}_dev", "rm": f"rflu_gecon_rm_{sfx}_dev", "host": f"rflu_gecon_{sfx}"}[kind]
+    h.call(name, code, n, ap, ld, anorm, ctypes.byref(out))
+    return float(out.value)
+
+
+def cond(A, p=1, *, handle=None) -> float:
+    """``cond(A, 1)`` / ``cond(A, Inf)`` as Julia computes them: ``opnorm``, then ``lu`` on a copy (``check=False``), then ``1 / rcond``;
+    ``inf`` when ``rcond == 0`` (a singular matrix).  ``A`` stays intact."""
+    code = _norm_code(p, "cond")
+    if isinstance(A, Adjoint):
+        A, code = A.parent, _swap_norm(code)
+        if isinstance(A, Adjoint):
+            raise TypeError("cond of a doubly wrapped matrix: unwrap it first")
+    if getattr(A, "ndim", None) != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("cond needs a square matrix")
+    _cond_sfx(A.dtype, "cond")
+    if A.shape[0] == 0:
+        return 1.0
+    p = 1 if code == _ffi.NORM_ONE else float("inf")
+    anorm = opnorm(A, p, handle=handle)
+    rc = rcond(lu(A, check=False, handle=handle), anorm, p, handle=handle)
+    return float("inf") if rc == 0.0 else 1.0 / rc
+
+
 def _complex_trans(F, trans, what: str):
     """The plain factorization and which of the three matrices is meant: "N" (A), "T" (transpose(A)) or "C" (A', the conjugate
     transpose) -- LAPACK's letters, as in ``ldiv_complex_batched_``.  ``Transpose is Adjoint`` in this package, so a wrapper cannot say
@@ -1178,6 +1287,74 @@ def det_batched(F, *, handle=None):
 
     la, sg = logabsdet_batched(F, handle=handle)
     return torch.where(sg == 0, torch.zeros_like(sg), sg * torch.exp(la))
+
+
+def opnorm_batched(A, p=1, *, handle=None):
+    """``opnorm(A_b, p)`` of every matrix of a (batch, m, n) CUDA tensor (``rflu_lange_batched_*_dev``; one workgroup per matrix up to
+    128 x 128): a Float64 CUDA tensor of length ``batch``, entry b bit-identical to ``opnorm`` on matrix b.  ``Adjoint(A)`` swaps 1 and inf."""
+    code = _norm_code(p, "opnorm_batched")
+    if isinstance(A, Adjoint):
+        A, code = A.parent, _swap_norm(code)
+    if not _is_torch(A) or A.ndim != 3:
+        raise TypeError("opnorm_batched needs a 3-D CUDA tensor (batch, m, n)")
+    sfx = _cond_sfx(A.dtype, "opnorm_batched")
+    if not A.is_cuda:
+        raise TypeError("opnorm_batched: the batch must live on the MI355X (device='cuda')")
+    import torch
+
+    batch, m, n = (int(x) for x in A.shape)
+    row_major, ld, stride_a = _batched_layout(A, "opnorm_batched")
+    out = torch.zeros(batch, dtype=torch.float64, device=A.device)
+    if batch > 0 and m > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        h.call(f"rflu_lange_batched_{sfx}_dev", code, batch, m, n, ctypes.c_void_p(A.data_ptr()), ld, stride_a, row_major,
+               ctypes.c_void_p(out.data_ptr()))
+    return out
+
+
+def rcond_batched(F, anorm, p=1, *, handle=None):
+    """``rcond`` of every matrix of a batch from its factors (``rflu_gecon_batched_*_dev``: ONE launch up to n = 128, the whole estimator
+    inside the kernel on the factors held in LDS; larger matrices are looped over ``rflu_gecon_*``).  ``anorm``: a Float64 CUDA tensor of
+    length ``batch`` (``opnorm_batched`` before the factorization).  Returns a Float64 CUDA tensor of length ``batch``; a singular member
+    gives 0 and a NaN member NaN in its own entry only.  ``Adjoint(F)`` swaps 1 and inf."""
+    code = _norm_code(p, "rcond_batched")
+    G, adj = _unwrap_adjoint(F, "rcond_batched")
+    if isinstance(G, BatchedLU) and _is_torch(G.factors):
+        _cond_sfx(G.factors.dtype, "rcond_batched")
+    F, adj, A, sfx, row_major, ld, stride_f = _batched_square(F, "rcond_batched")
+    if adj:
+        code = _swap_norm(code)
+    import torch
+
+    batch, n = int(A.shape[0]), int(A.shape[1])
+    if not (_is_torch(anorm) and anorm.is_cuda and anorm.dtype == torch.float64 and anorm.ndim == 1 and anorm.shape[0] == batch
+            and (batch <= 1 or anorm.stride(0) == 1)):
+        raise TypeError("rcond_batched: anorm must be a contiguous Float64 CUDA tensor of length batch")
+    out = torch.ones(batch, dtype=torch.float64, device=A.device)
+    if batch > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        h.call(f"rflu_gecon_batched_{sfx}_dev", code, batch, n, ctypes.c_void_p(A.data_ptr()), ld, stride_f, row_major,
+               ctypes.c_void_p(anorm.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    return out
+
+
+def cond_batched(A, p=1, *, handle=None):
+    """``cond(A_b, p)`` of every matrix of a (batch, n, n) CUDA tensor: ``opnorm_batched``, ``lu_batched`` on a copy (``check=False``),
+    ``1 / rcond_batched``; ``inf`` where ``rcond == 0``.  A Float64 CUDA tensor of length ``batch``."""
+    code = _norm_code(p, "cond_batched")
+    if isinstance(A, Adjoint):
+        A, code = A.parent, _swap_norm(code)
+    if not _is_torch(A) or A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError("cond_batched needs a 3-D CUDA tensor (batch, n, n)")
+    _cond_sfx(A.dtype, "cond_batched")
+    import torch
+
+    p = 1 if code == _ffi.NORM_ONE else float("inf")
+    anorm = opnorm_batched(A, p, handle=handle)
+    rc = rcond_batched(lu_batched(A, check=False, handle=handle), anorm, p, handle=handle)
+    return torch.where(rc == 0, torch.full_like(rc, float("inf")), 1.0 / rc)
 
 
 def _cbatched_sfx(dtype, what: str) -> str:
