@@ -246,7 +246,8 @@ int rflu_getri_batched_f32_dev(rflu_handle_t handle, int64_t batch, int64_t n, c
 
 /* ---- NORMS, CONDITION: what LAPACK pairs with getrf (lange + gecon) and Julia's cond(A, 1) / cond(A, Inf) is made of: the operator
  * norm of A BEFORE the factorization overwrites it, then an estimate of rcond = 1 / (||A|| ||A^-1||) from the packed factors alone.
- * Float64 / Float32 only (not complex).  Kernels: csrc/condest.hip and gecon_batched_kernel in csrc/batched.hip; DESIGN.md section 4.11.
+ * Float64 / Float32 here; the complex form is the block COMPLEX NORMS, CONDITION below.  Kernels: csrc/condest.hip and
+ * gecon_batched_kernel in csrc/batched.hip; DESIGN.md section 4.11.
  * Every sum is formed in Float64 for both element types, in a fixed order -- no read-modify-write on shared words, partial sums per
  * chunk, the chunks combined in index order -- so results are bit-identical from run to run.  Work goes on the handle's stream and is
  * complete on return (the batched lange entry included).
@@ -454,6 +455,69 @@ int rflu_gemm_rm_cf64_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K,
                           const double* B_dev, int64_t ldb, double* C_dev, int64_t ldc);
 int rflu_gemm_rm_cf32_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K, const float* A_dev, int64_t lda,
                           const float* B_dev, int64_t ldb, float* C_dev, int64_t ldc);
+
+/* ---- COMPLEX NORMS, CONDITION: the NORMS, CONDITION block above for ComplexF64 / ComplexF32 (LAPACK zlange / clange + zgecon / cgecon).
+ * Kernels: csrc/complex_condest.hip and cgecon_batched_kernel in csrc/batched_complex.hip; DESIGN.md section 4.12.  The contract is that
+ * of the real block with the storage rules of the other complex entries: a matrix crosses as double* / float* at interleaved (re, im)
+ * pairs, every lda / strideA / strideF counts COMPLEX elements, a pointer aligned to the real type is enough.  Argument lists are those
+ * of the _f64 / _f32 entries of the same name.  There is NO rflu_gecon_rm_c*: the single-matrix complex path is column-major only.
+ * rflu_lange_c* keeps row_major (it only reads); rflu_gecon_batched_c* keeps row_major (the complex batched factors exist in both
+ * orientations).  Work goes on the handle's stream and is complete on return.
+ *
+ * rflu_lange_c*: |a| = hypot(re, im) in Float64 (ComplexF32 parts are converted first).  The sums are Float64 in the fixed order of the
+ * real entries with "element" read as complex element: chunks of 1024 elements of a line, thread t owns elements 4t .. 4t+3 in index
+ * order, the same wave tree, the four wave sums in order, the chunks in index order; groups of 256 lines for the sum across lines, the
+ * groups in index order.  Results are bit-identical from run to run, whatever the alignment and lda, and between the single and batched
+ * entries.  16-byte loads where the pointer allows (for _cf32 also the start of every line, i.e. an even lda), element loads otherwise:
+ * the same additions either way.  Padding is never read.  A NaN in EITHER part of any element gives NaN -- also when the other part is
+ * Inf (the parts are tested, not the modulus: C's hypot(Inf, NaN) is Inf); otherwise an Inf gives Inf; m == 0 or n == 0 gives 0.  The
+ * batched entry is one workgroup per matrix up to max(m, n) <= 128 for both element types and runs the single entry's kernels per
+ * matrix above that, with the same bits. */
+int rflu_lange_cf64_dev(rflu_handle_t handle, int norm, int64_t m, int64_t n, const double* A_dev, int64_t lda, int row_major,
+                        double* out);
+int rflu_lange_cf32_dev(rflu_handle_t handle, int norm, int64_t m, int64_t n, const float* A_dev, int64_t lda, int row_major,
+                        double* out);
+int rflu_lange_batched_cf64_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t m, int64_t n, const double* A_dev, int64_t lda,
+                                int64_t strideA, int row_major, double* out_dev);
+int rflu_lange_batched_cf32_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t m, int64_t n, const float* A_dev, int64_t lda,
+                                int64_t strideA, int row_major, double* out_dev);
+/* rflu_gecon_c*: *rcond_out = 1 / (anorm * est), est an estimate of ||U^-1 L^-1|| = ||A^-1|| in the norm `norm`; no ipiv argument; F
+ * (column-major packed L\U as rflu_getrf_c* left it) is ONLY READ; the host entry is H2D, then the device entry.
+ *   - The method is LAPACK zlacn2 (at most 5 iterations) on M = U^-1 L^-1 with the real entry's two stated changes carried over: the
+ *     all-ones start vector with first estimate sum|v_i| / n, and the closing vector x_i = (-1)^i (n - 1 + i) with the bound
+ *     2 sum|v_i| / (3 n (n - 1)).  n = 1: the estimate is |v_0| of the first solve.
+ *   - The pair of operators is M and M^H (the ADJOINT, not M^T).  For RFLU_NORM_INF the two swap roles (||M||_inf = ||M^H||_1).
+ *   - After a solve with M the next iterate is the phase vector x_i = v_i / |v_i|: |v_i| is hypot in Float64, the two quotients are
+ *     formed in Float64 and rounded to the element type; x_i = 1 + 0i where both parts of v_i are zero.
+ *   - There is NO repeated-sign-vector test (zlacn2 has none).  The stops are: est <= est_old; |x_jlast| == |x_j| with j the FIRST index
+ *     of the largest modulus; 5 iterations.  The result is the larger of the iteration's estimate and the closing vector's bound.
+ *     At most 11 solves with one right-hand side, 8n^2 real flops each.
+ *   - One layout change per call: the row-major image W of F is made once in the handle's workspace; every M x is the few-right-hand-side
+ *     forward solve of rflu_mixed_solve_cf32_dev (here also for ComplexF64) on W, every M^H x the few-right-hand-side path of
+ *     rflu_getrs_trans_c*_dev with conj = 1 on F in place, both with ipiv = NULL.  Between two solves: fixed-order vector kernels and one
+ *     read of a few scalars by the host.  No kernel of this path waits for another workgroup.  Neither solve path states a size limit,
+ *     so there is NO size limit on n here (beyond memory).
+ *   - Special values, the first in this order deciding: n == 0: 1.  anorm NaN: NaN.  anorm == 0: 0.  A u_ii with BOTH parts zero: 0,
+ *     before any solve is launched (u_ii = 0 + 1i is not singular).  A NaN in either part of any factor entry: NaN.  A non-finite vector
+ *     out of a solve (no xLATRS scaling): 0.
+ *   - anorm < 0, norm not 1 / 2, lda < n, NULL pointers: RFLU_ERR_ARG with a message.
+ *   - A solve, an inverse or a factorization after rflu_gecon_c* on the same handle is bit-identical to one on a fresh handle.
+ * rflu_gecon_batched_c*: the same for every matrix of a batch (matrix b at F_dev + b*strideF complex elements in either orientation;
+ * anorm_dev, rcond_dev: DEVICE arrays of `batch` doubles).  n <= 64 (ComplexF64) / n <= 128 (ComplexF32): ONE launch, the factors in LDS
+ * once, the whole estimator inside the kernel (the batched substitutions of rflu_getrs_batched_c*, trans = 0 and trans = 2, on one
+ * right-hand side; they multiply by one reciprocal of u_kk per column where the single entry divides), every group of a workgroup
+ * running the same number of rounds.  Larger n: a column-major batch is looped over the single entry -- correct, NOT fast; a row-major
+ * one is RFLU_ERR_ARG (the single-matrix complex path is column-major only).  Special values per member as above, except that a
+ * member's anorm < 0 gives NaN in its own output; one member's NaN or singularity touches its own output only.  batch == 0: success;
+ * n == 0: every rcond is 1. */
+int rflu_gecon_cf64_dev(rflu_handle_t handle, int norm, int64_t n, const double* F_dev, int64_t lda, double anorm, double* rcond_out);
+int rflu_gecon_cf32_dev(rflu_handle_t handle, int norm, int64_t n, const float* F_dev, int64_t lda, double anorm, double* rcond_out);
+int rflu_gecon_cf64(rflu_handle_t handle, int norm, int64_t n, const double* F_host, int64_t lda, double anorm, double* rcond_out);
+int rflu_gecon_cf32(rflu_handle_t handle, int norm, int64_t n, const float* F_host, int64_t lda, double anorm, double* rcond_out);
+int rflu_gecon_batched_cf64_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t n, const double* F_dev, int64_t lda,
+                                int64_t strideF, int row_major, const double* anorm_dev, double* rcond_dev);
+int rflu_gecon_batched_cf32_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t n, const float* F_dev, int64_t lda,
+                                int64_t strideF, int row_major, const double* anorm_dev, double* rcond_dev);
 
 /* ---- MIXED PRECISION: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme) ----
  * The Float32 factorization is the faster one; refinement with Float64 residuals r = b - A x brings the solution to Float64 backward

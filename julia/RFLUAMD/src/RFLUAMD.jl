@@ -727,6 +727,101 @@ function getri_batched_dev!(Ainv::Ptr{ComplexF32}, ldi::Integer, strideI::Intege
     return Ainv
 end
 
+# ---- operator norms and the condition estimate for ComplexF64 / ComplexF32 (rflu_lange_c* / rflu_gecon_c*, csrc/complex_condest.hip and
+# cgecon_batched_kernel of csrc/batched_complex.hip): the methods of lange_dev / lange_batched_dev! / gecon_dev! / gecon_host /
+# gecon_batched_dev! for the complex pointer and matrix types.  Moduli are hypot(re, im) in Float64; the estimator is LAPACK zlacn2 on M
+# and M' with the start and closing vectors of include/rflu.h.  A single matrix is column-major only (there is no rflu_gecon_rm_c*, so
+# gecon_dev! takes no row_major); leading dimensions and strides count complex elements.
+function lange_dev(A::Ptr{ComplexF64}, m::Integer, n::Integer, lda::Integer; p::Real = 1, row_major::Bool = false)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_lange_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float64}, Int64, Cint, Ptr{Float64}),
+               handle(), norm_code(p), m, n, reinterpret(Ptr{Float64}, A), lda, Cint(row_major), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function lange_batched_dev!(out::Ptr{Float64}, A::Ptr{ComplexF64}, batch::Integer, m::Integer, n::Integer, lda::Integer, strideA::Integer,
+                            row_major::Bool; p::Real = 1)
+    st = ccall((:rflu_lange_batched_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Float64}),
+               handle(), norm_code(p), batch, m, n, reinterpret(Ptr{Float64}, A), lda, strideA, Cint(row_major), out)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function gecon_dev!(F::Ptr{ComplexF64}, n::Integer, ld::Integer, anorm::Real; p::Real = 1)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_gecon_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float64}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), n, reinterpret(Ptr{Float64}, F), ld, Cdouble(anorm), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function gecon_host(F::StridedMatrix{ComplexF64}, anorm::Real; p::Real = 1)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_gecon_cf64, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float64}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), size(F, 1), reinterpret(Ptr{Float64}, pointer(F)), stride(F, 2), Cdouble(anorm), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function gecon_batched_dev!(rcond::Ptr{Float64}, F::Ptr{ComplexF64}, batch::Integer, n::Integer, lda::Integer, strideF::Integer, row_major::Bool,
+                            anorm::Ptr{Float64}; p::Real = 1)
+    st = ccall((:rflu_gecon_batched_cf64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float64}, Int64, Int64, Cint, Ptr{Float64}, Ptr{Float64}),
+               handle(), norm_code(p), batch, n, reinterpret(Ptr{Float64}, F), lda, strideF, Cint(row_major), anorm, rcond)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function lange_dev(A::Ptr{ComplexF32}, m::Integer, n::Integer, lda::Integer; p::Real = 1, row_major::Bool = false)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_lange_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float32}, Int64, Cint, Ptr{Float64}),
+               handle(), norm_code(p), m, n, reinterpret(Ptr{Float32}, A), lda, Cint(row_major), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function lange_batched_dev!(out::Ptr{Float64}, A::Ptr{ComplexF32}, batch::Integer, m::Integer, n::Integer, lda::Integer, strideA::Integer,
+                            row_major::Bool; p::Real = 1)
+    st = ccall((:rflu_lange_batched_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Float64}),
+               handle(), norm_code(p), batch, m, n, reinterpret(Ptr{Float32}, A), lda, strideA, Cint(row_major), out)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
+function gecon_dev!(F::Ptr{ComplexF32}, n::Integer, ld::Integer, anorm::Real; p::Real = 1)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_gecon_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float32}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), n, reinterpret(Ptr{Float32}, F), ld, Cdouble(anorm), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function gecon_host(F::StridedMatrix{ComplexF32}, anorm::Real; p::Real = 1)
+    out = zeros(Float64, 1)
+    st = GC.@preserve out ccall((:rflu_gecon_cf32, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Ptr{Float32}, Int64, Cdouble, Ptr{Float64}),
+               handle(), norm_code(p), size(F, 1), reinterpret(Ptr{Float32}, pointer(F)), stride(F, 2), Cdouble(anorm), pointer(out, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return out[1]
+end
+
+function gecon_batched_dev!(rcond::Ptr{Float64}, F::Ptr{ComplexF32}, batch::Integer, n::Integer, lda::Integer, strideF::Integer, row_major::Bool,
+                            anorm::Ptr{Float64}; p::Real = 1)
+    st = ccall((:rflu_gecon_batched_cf32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float32}, Int64, Int64, Cint, Ptr{Float64}, Ptr{Float64}),
+               handle(), norm_code(p), batch, n, reinterpret(Ptr{Float32}, F), lda, strideF, Cint(row_major), anorm, rcond)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return nothing
+end
+
 # ---- dispatch: who serves a call (RecursiveFactorization src/lu.jl:92-93, 114-126) -------------------------------------------
 const GPUEltype = Union{Float32, Float64}                                  # every entry serves these
 const GPUAnyEltype = Union{Float32, Float64, ComplexF32, ComplexF64}       # lu! and ldiv!(F, B) serve the complex types as well
@@ -830,6 +925,13 @@ end
 """
 function rcond(F::LU{T, <:StridedMatrix{T}}, anorm::Real; p::Real = 1) where {T <: GPUEltype}
     lu_on_gpu(F) || return LinearAlgebra.LAPACK.gecon!(p == 1 ? '1' : 'I', copy(F.factors), T(anorm))
+    return GC.@preserve F gecon_host(F.factors, anorm; p = p)
+end
+
+# rcond of a complex LU: LAPACK zgecon / cgecon's place.  The real type of anorm is that of the element; |conj z| = |z|, so F' and
+# transpose(F) share their condition number and only swap p = 1 and p = Inf, which is left to the caller as for the real method.
+function rcond(F::LU{T, <:StridedMatrix{T}}, anorm::Real; p::Real = 1) where {T <: GPUComplexEltype}
+    lu_on_gpu(F) || return LinearAlgebra.LAPACK.gecon!(p == 1 ? '1' : 'I', copy(F.factors), real(T)(anorm))
     return GC.@preserve F gecon_host(F.factors, anorm; p = p)
 end
 

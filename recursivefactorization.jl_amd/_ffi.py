@@ -116,6 +116,12 @@ _COMPLEX = {
     "rflu_logabsdet_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
     # the batched inverse: the real entry's arguments with `trans` (0 / 1 / 2) before info_dev
     "rflu_getri_batched_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p]),
+    # complex operator norms and the condition estimate: the real entries' arguments; there is no rflu_gecon_rm_c* (column-major only)
+    "rflu_lange_{s}_dev": (c_int, [c_p, c_int, c_i64, c_i64, c_p, c_i64, c_int, c_p]),
+    "rflu_lange_batched_{s}_dev": (c_int, [c_p, c_int, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p]),
+    "rflu_gecon_{s}_dev": (c_int, [c_p, c_int, c_i64, c_p, c_i64, c_dbl, c_p]),
+    "rflu_gecon_{s}": (c_int, [c_p, c_int, c_i64, c_p, c_i64, c_dbl, c_p]),
+    "rflu_gecon_batched_{s}_dev": (c_int, [c_p, c_int, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_p]),
 }
 
 EXPORTS = dict(_PLAIN)

@@ -518,4 +518,249 @@ template int launch_cgetri_batched<double>(Handle*, int64_t, int64_t, const doub
 template int launch_cgetri_batched<float>(Handle*, int64_t, int64_t, const float*, int64_t, int64_t, int, const int64_t*, int64_t, float*,
                                           int64_t, int64_t, int, int64_t*);
 
+// ---- the batched condition estimate, behind everything above for the reason given at the inverse.
+namespace {
+
+template <typename R>
+struct CCondArgs {
+    const Cx<R>* F;
+    const double* anorm;
+    double* rcond;
+    int64_t lda, strideF, batch;
+    int n, row_major, norm;
+    BGeo g;
+};
+
+struct CBStat {
+    double sum, maxabs, xj;
+    int argmax, nonfinite;
+};
+
+// the modulus the estimator adds: Float64 hypot, NaN when either part is one (cabs64 of complex_condest.hip)
+template <typename R>
+__device__ __forceinline__ double cbabs64(Cx<R> z)
+{
+    const double x = (double)z.re, y = (double)z.im;
+    if (x != x || y != y) return __builtin_nan("");
+    return hypot(x, y);
+}
+
+// The statistics of the group's work vector X(0 .. n, 0), the same in every thread of the group: bstats of batched.hip on moduli and
+// without the sign test.  Thread t < n holds x_t.  sum|x_t| is added by the tree t += t + s, s = 64 .. 1 -- the tree of
+// ccond_stats_kernel (complex_condest.hip) on one chunk, whose steps s = 128 and, for n <= 64, s = 64 add +0.0 --; the first index of the
+// largest modulus and the flag do not depend on an order.  sc: the group's scratch (3 doubles, 131 for n > 64).
+// Barriers: two (three for n > 64), under no condition but n, which the whole workgroup shares.
+template <typename R>
+__device__ __forceinline__ CBStat cbstats(const CImage<R>& X, double* sc, int n, int t, int jq)
+{
+    const int lane = t & 63, w = t >> 6;
+    int* si = reinterpret_cast<int*>(sc + 1);
+    double v = 0.0, av = -1.0;
+    int ai = lane, nf = 0;
+    if (t < n) {
+        v = cbabs64<R>(X.get(t, 0));
+        av = v;
+        ai = t;
+        nf = !(v < __builtin_inf());
+    }
+    bu64 bn = __ballot(nf);
+    if (n > 64) {
+        if (w == 1) {
+            sc[3 + lane] = v;
+            sc[67 + lane] = av;
+            if (lane == 0) si[1] = bn != 0;
+        }
+        __syncthreads();
+        if (w == 0) {
+            v += sc[3 + lane];
+            const double a1 = sc[67 + lane];
+            if (a1 > av) { av = a1; ai = 64 + lane; }
+            if (si[1]) bn = 1;
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        v += __shfl_down(v, s, 64);
+        const double oa = __shfl_xor(av, s, 64);
+        const int oi = __shfl_xor(ai, s, 64);
+        if (oa > av || (oa == av && oi < ai)) { av = oa; ai = oi; }
+    }
+    if (w == 0 && lane == 0) {
+        sc[0] = v;
+        sc[2] = av;
+        si[0] = ai;
+        si[1] = bn != 0 ? 1 : 0;
+    }
+    __syncthreads();
+    CBStat r;
+    r.sum = sc[0];
+    r.maxabs = sc[2];
+    r.argmax = si[0];
+    r.nonfinite = si[1];
+    r.xj = cbabs64<R>(X.get(jq, 0));
+    __syncthreads();   // everybody has read the scratch before its next writer comes
+    return r;
+}
+
+// Higham's estimator (LAPACK zlacn2 with the integer start and closing vectors of rflu.h) on M = U^-1 L^-1, wholly inside the kernel: the
+// factors go into LDS once (cbload_matrix), cbsubstitute<R, 0> on one right-hand side is M x and cbsubstitute<R, 2> is M^H x; the work
+// vector (column 0), the reciprocals of the conjugated diagonal (column 1) and the scratch of cbstats (from column 2 on) live in the
+// 8-column x region of the solve's geometry.  No previous-sign vector: zlacn2 has no such test.
+//
+// WHY NO GROUP CAN LEAVE ANOTHER ONE AT A BARRIER.  cbsubstitute's barriers are workgroup-wide, a workgroup holds 4 / 2 / 1 matrices, and
+// the matrices need different numbers of estimator rounds.  So the code below has NO barrier under a condition that depends on a group's
+// state: every barrier stands in straight-line code of the round, inside cbsubstitute / cbstats (whose barrier counts depend on n alone,
+// and n is a kernel argument), or in loops whose trip count is n or the round counter.  The round loop is left through ONE test,
+// __syncthreads_or(act), whose result is the same in every thread of the workgroup; it runs at most 5 times.  What differs between
+// groups is only data: a finished group, a singular one and a group beyond the end of the batch (valid == false) run the same code with
+// nr = 0 right-hand sides (cbsubstitute then touches nothing) and ignore the statistics, their estimate frozen.
+template <typename R>
+__global__ void __launch_bounds__(BT) cgecon_batched_kernel(CCondArgs<R> a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char cbsmem[];
+    const BGeo g = a.g;
+    const int n = a.n, ld = g.ld;
+    const int grp = (int)threadIdx.x >> g.tpm_log, t = (int)threadIdx.x & (g.tpm - 1);
+    const int64_t b = (int64_t)blockIdx.x * (BT >> g.tpm_log) + grp;
+    const bool valid = b < a.batch;
+    unsigned char* base = cbsmem + (size_t)grp * g.group_bytes;
+    typedef typename CVec<R>::type V2;
+    const CImage<R> S{reinterpret_cast<V2*>(base), ld};
+    const CImage<R> X{reinterpret_cast<V2*>(base + g.off_x), ld};              // column 0: the work vector
+    const CImage<R> D{reinterpret_cast<V2*>(base + g.off_a), 0};               // [n]: 1 / u_kk
+    const CImage<R> DC{reinterpret_cast<V2*>(base + g.off_x) + ld, 0};         // [n]: 1 / conj(u_kk), column 1 of the x region
+    double* sc = reinterpret_cast<double*>(reinterpret_cast<V2*>(base + g.off_x) + 2 * ld);   // 8-byte aligned: off_x and a V2 are
+    int* si = reinterpret_cast<int*>(sc + 1);
+    const Cx<R>* F = a.F + (valid ? b : 0) * a.strideF;
+
+    cbload_matrix<R>(S, F, a.lda, a.row_major, n, n, g, t, valid);
+    if (t == 0) { si[0] = 0; si[1] = 0; }
+    const int r = t & ((1 << g.rt_log) - 1), c = t >> g.rt_log, cs = g.tpm >> g.rt_log;
+    const bool own = c == 0 && r < n;   // this thread holds x_r (then r == t)
+    __syncthreads();
+    {   // a NaN in either part of any factor entry (bit 0), a u_ii with both parts zero (bit 1): plain stores of the same value
+        int f = 0;
+        if (r < n)
+            for (int j = c; j < n; j += cs) {
+                const Cx<R> v = S.get(r, j);
+                if (v.re != v.re || v.im != v.im) f |= 1;
+                if (j == r && v.re == R(0) && v.im == R(0)) f |= 2;
+            }
+        if (f & 1) si[0] = 1;
+        if (f & 2) si[1] = 1;
+    }
+    if (t < n) {   // one reciprocal per column and operator for the whole estimate, formed as cgetrs_batched_kernel forms them
+        Cx<R> d = S.get(t, t);
+        D.put(t, 0, cdiv(Cx<R>{R(1), R(0)}, d));
+        d.im = -d.im;
+        DC.put(t, 0, cdiv(Cx<R>{R(1), R(0)}, d));
+    }
+    __syncthreads();
+    const int scan = (si[0] ? 1 : 0) | (si[1] ? 2 : 0);
+    __syncthreads();
+
+    const bool inf_norm = a.norm == RFLU_NORM_INF;   // ||M||_inf = ||M^H||_1: M and M^H swap roles
+    const Cx<R> one{R(1), R(0)}, zero{R(0), R(0)};
+    bool act = valid && scan == 0, closing = false, bad = false;
+    double est = 0.0;
+    int j = 0;
+    for (int round = 0; round < 5; ++round) {
+        if (act && own) X.put(r, 0, (round == 0 || r == j) ? one : zero);
+        __syncthreads();
+        if (inf_norm) cbsubstitute<R, 2>(S, X, DC, n, act ? 1 : 0, r, c, cs);
+        else cbsubstitute<R, 0>(S, X, D, n, act ? 1 : 0, r, c, cs);
+        const CBStat s1 = cbstats<R>(X, sc, n, t, j);
+        if (act) {
+            if (s1.nonfinite) { bad = true; act = false; }
+            else if (round == 0) {
+                est = s1.sum / (double)n;
+                if (n == 1) act = false;
+            } else {
+                const double est_old = est;
+                est = s1.sum;
+                if (est <= est_old) { act = false; closing = true; }
+            }
+        }
+        if (act && own) {   // the phase vector: two Float64 quotients rounded to the element type, 1 + 0i for a zero
+            const Cx<R> v = X.get(r, 0);
+            const double m = cbabs64<R>(v);
+            const bool z = v.re == R(0) && v.im == R(0);
+            X.put(r, 0, z ? one : Cx<R>{(R)((double)v.re / m), (R)((double)v.im / m)});
+        }
+        __syncthreads();
+        if (inf_norm) cbsubstitute<R, 0>(S, X, D, n, act ? 1 : 0, r, c, cs);
+        else cbsubstitute<R, 2>(S, X, DC, n, act ? 1 : 0, r, c, cs);
+        const CBStat s2 = cbstats<R>(X, sc, n, t, j);
+        if (act) {
+            if (s2.nonfinite) { bad = true; act = false; }
+            else {
+                j = s2.argmax;
+                if ((round > 0 && s2.xj == s2.maxabs) || round == 4) { act = false; closing = true; }
+            }
+        }
+        if (!__syncthreads_or(act ? 1 : 0)) break;
+    }
+    // the alternating vector's bound: every group runs the solve, those that do not need it with no right-hand side
+    if (closing && own) {
+        const R av = (R)(double)(n - 1 + r);
+        X.put(r, 0, Cx<R>{(r & 1) ? -av : av, R(0)});
+    }
+    __syncthreads();
+    if (inf_norm) cbsubstitute<R, 2>(S, X, DC, n, closing ? 1 : 0, r, c, cs);
+    else cbsubstitute<R, 0>(S, X, D, n, closing ? 1 : 0, r, c, cs);
+    const CBStat s3 = cbstats<R>(X, sc, n, t, 0);
+    if (closing) {
+        if (s3.nonfinite) bad = true;
+        else {
+            const double alt = 2.0 * s3.sum / (3.0 * (double)n * (double)(n - 1));
+            if (alt > est) est = alt;
+        }
+    }
+    if (valid && t == 0) {
+        const double an = a.anorm[b];
+        double rc;
+        if (an != an || an < 0.0) rc = __builtin_nan("");
+        else if (an == 0.0) rc = 0.0;
+        else if (scan & 2) rc = 0.0;
+        else if (scan & 1) rc = __builtin_nan("");
+        else if (bad || est == 0.0) rc = 0.0;
+        else rc = 1.0 / (an * est);
+        a.rcond[b] = rc;
+    }
+}
+
+}  // namespace
+
+template <typename R>
+int launch_cgecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, int row_major,
+                          const double* anorm, double* rcond)
+{
+    CCondArgs<R> a;
+    a.F = reinterpret_cast<const Cx<R>*>(F); a.anorm = anorm; a.rcond = rcond;
+    a.lda = lda; a.strideF = strideF; a.batch = batch;
+    a.n = (int)n; a.row_major = row_major; a.norm = norm;
+    a.g = batched_geo(n, n, sizeof(Cx<R>), true, true);
+    // launch_batched's bookkeeping (Handle::batched_attr_set) has no row for a fourth kernel: the same launch with a flag of its own.
+    // The kernel also holds static LDS (the word behind __syncthreads_or), so asking for all 160 KiB as dynamic memory is refused: ask
+    // once for what the largest launch needs, the same value from every handle.
+    const int groups = BT / a.g.tpm;
+    const size_t lds = (size_t)groups * a.g.group_bytes;
+    const int64_t nmax = sizeof(R) == 8 ? CBATCHED_MAX_DIM_CF64 : CBATCHED_MAX_DIM_CF32;
+    const BGeo gmax = batched_geo(nmax, nmax, sizeof(Cx<R>), true, true);
+    const size_t lds_max = std::max(lds, (size_t)(BT / gmax.tpm) * gmax.group_bytes);
+    size_t* asked = &h->cgecon_lds_asked[sizeof(R) == 4 ? 1 : 0];
+    if (lds > 64 * 1024 && *asked == 0) {
+        RFLU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&cgecon_batched_kernel<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        *asked = lds_max;
+    }
+    const int64_t wgs = (batch + groups - 1) / groups;
+    ProfScope ps(h, RFLU_K_TRSM, 88.0 * (double)batch * (double)n * (double)n, (double)batch * (double)n * (double)n * sizeof(Cx<R>));
+    hipLaunchKernelGGL(cgecon_batched_kernel<R>, dim3((unsigned)wgs), dim3(BT), lds, h->stream, a);
+    RFLU_HIP(hipGetLastError());
+    return RFLU_OK;
+}
+
+template int launch_cgecon_batched<double>(Handle*, int, int64_t, int64_t, const double*, int64_t, int64_t, int, const double*, double*);
+template int launch_cgecon_batched<float>(Handle*, int, int64_t, int64_t, const float*, int64_t, int64_t, int, const double*, double*);
+
 }  // namespace rflu

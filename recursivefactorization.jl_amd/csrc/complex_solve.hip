@@ -395,5 +395,7 @@ template int cgetrs_trans_cm_dev<double>(Handle*, int64_t, int64_t, const double
 template int cgetrs_trans_cm_dev<float>(Handle*, int64_t, int64_t, const float*, int64_t, const int64_t*, float*, int64_t, int);
 template int launch_claswp_rev<double>(Handle*, double*, int64_t, int64_t, int64_t, int64_t, const int64_t*);
 template int launch_claswp_rev<float>(Handle*, float*, int64_t, int64_t, int64_t, int64_t, const int64_t*);
+// the forward narrow solve on ComplexF64 row-major factors: M x of the condition estimate (cgecon_dev, driver.cpp)
+template int csolve_fwd_narrow<double>(Handle*, int64_t, int, const double*, int64_t, const int64_t*, double*, int64_t);
 
 }  // namespace rflu

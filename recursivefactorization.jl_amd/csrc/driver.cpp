@@ -860,6 +860,162 @@ static int cgetri_batched(Handle* h, int64_t batch, int64_t n, const R* F, int64
     return RFLU_OK;
 }
 
+// ---- complex operator norms and condition estimate (include/rflu.h: COMPLEX NORMS, CONDITION; kernels: complex_condest.hip and
+// cgecon_batched_kernel in batched_complex.hip).  Sizes and leading dimensions count complex elements.
+template <typename R>
+static int clange_dev(Handle* h, int norm, int64_t m, int64_t n, const R* A, int64_t lda, int row_major, double* out)
+{
+    if (!norm_ok("complex lange", norm)) return RFLU_ERR_ARG;
+    if (m < 0 || n < 0 || out == nullptr || lda < std::max<int64_t>(row_major ? n : m, 1) || (m > 0 && n > 0 && A == nullptr)) {
+        set_error("complex lange: bad arguments m=%lld n=%lld lda=%lld (or a null pointer)", (long long)m, (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    return launch_clange<R>(h, norm, m, n, A, lda, row_major, out);
+}
+
+template <typename R>
+static int clange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const R* A, int64_t lda, int64_t strideA, int row_major,
+                          double* out_dev)
+{
+    if (!norm_ok("complex lange_batched", norm)) return RFLU_ERR_ARG;
+    if (batch < 0 || m < 0 || n < 0) {
+        set_error("complex lange_batched: negative size batch=%lld m=%lld n=%lld", (long long)batch, (long long)m, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0) return RFLU_OK;
+    if (out_dev == nullptr || (m > 0 && n > 0 && A == nullptr)) { set_error("complex lange_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (m == 0 || n == 0) {
+        RFLU_HIP(hipMemsetAsync(out_dev, 0, (size_t)batch * sizeof(double), h->stream));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        return RFLU_OK;
+    }
+    const int64_t len = row_major ? n : m, cnt = row_major ? m : n;
+    if (lda < len || (batch > 1 && strideA < (cnt - 1) * lda + len)) {
+        set_error("complex lange_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", (long long)lda, (long long)strideA,
+                  (long long)m, (long long)n, row_major ? "row-major" : "column-major");
+        return RFLU_ERR_ARG;
+    }
+    RFLU_TRY(launch_clange_batched<R>(h, norm, batch, m, n, A, lda, strideA, row_major, out_dev));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+// rcond = 1 / (anorm * est): Higham's estimator (LAPACK zlacn2 with the integer start and closing vectors stated in rflu.h) on
+// M = U^-1 L^-1 of column-major complex factors.  ONE layout change per call: W = the row-major image of F in h->work.  Every M x is
+// csolve_fwd_narrow on W, every M^H x the narrow path of cgetrs_trans_cm_dev (conj = 1) on F in place, both with ipiv = NULL and one
+// right-hand side, the n contiguous elements of x.  Neither narrow path states a size limit, so there is none here.
+template <typename R>
+int cgecon_dev(Handle* h, int norm, int64_t n, const R* F, int64_t lda, double anorm, double* rcond)
+{
+    if (!norm_ok("complex gecon", norm)) return RFLU_ERR_ARG;
+    if (n < 0 || lda < std::max<int64_t>(n, 1) || rcond == nullptr || (n > 0 && F == nullptr)) {
+        set_error("complex gecon: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    if (anorm < 0.0) { set_error("complex gecon: anorm = %g is negative", anorm); return RFLU_ERR_ARG; }
+    *rcond = 0.0;
+    if (n == 0) { *rcond = 1.0; return RFLU_OK; }
+    if (anorm != anorm) { *rcond = anorm; return RFLU_OK; }
+    if (anorm == 0.0) return RFLU_OK;
+    int64_t zero1 = 0;
+    RFLU_TRY(launch_clogabsdet<R>(h, n, F, lda + 1, nullptr, nullptr, nullptr, nullptr, &zero1));
+    if (zero1 != 0) return RFLU_OK;   // a u_ii with both parts zero: rcond = 0 before any solve is launched
+
+    const int64_t ldw = cworkspace_ld(n);
+    RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldw * 2 * sizeof(R)));
+    RFLU_TRY(ensure_buffer(&h->cond_work, &h->cond_work_bytes, (size_t)n * 2 * sizeof(R)));
+    R* W = static_cast<R*>(h->work);
+    R* x = static_cast<R*>(h->cond_work);
+    RFLU_TRY(launch_ctranspose<R>(h, n, n, F, lda, W, ldw));
+    // ||M||_inf = ||M^H||_1: for the Inf norm M and M^H swap roles
+    auto apply = [&](bool adjoint) -> int {
+        if (adjoint != (norm == RFLU_NORM_INF)) return cgetrs_trans_cm_dev<R>(h, n, 1, F, lda, nullptr, x, n, 1);
+        return csolve_fwd_narrow<R>(h, n, 1, W, ldw, nullptr, x, n);
+    };
+    CondStats st;
+    double est = 0.0;
+    bool bad = false, closing = false;
+    int64_t j = 0;
+    for (int round = 0; round < 5; ++round) {
+        RFLU_TRY(launch_ccond_fill<R>(h, n, x, round == 0 ? COND_FILL_ONES : COND_FILL_UNIT, j));
+        RFLU_TRY(apply(false));
+        RFLU_TRY(launch_ccond_stats<R>(h, n, x, -1, 1, &st));   // x holds its phases afterwards
+        if (st.nonfinite) { bad = true; break; }
+        if (round == 0) {
+            est = st.sum / (double)n;
+            if (n == 1) break;
+        } else {
+            const double est_old = est;
+            est = st.sum;
+            if (est <= est_old) { closing = true; break; }
+        }
+        RFLU_TRY(apply(true));
+        RFLU_TRY(launch_ccond_stats<R>(h, n, x, j, 0, &st));
+        if (st.nonfinite) { bad = true; break; }
+        j = (int64_t)st.argmax;
+        if ((round > 0 && st.xj_abs == st.maxabs) || round == 4) { closing = true; break; }
+    }
+    if (closing) {
+        RFLU_TRY(launch_ccond_fill<R>(h, n, x, COND_FILL_ALT, 0));
+        RFLU_TRY(apply(false));
+        RFLU_TRY(launch_ccond_stats<R>(h, n, x, -1, 0, &st));
+        if (st.nonfinite) bad = true;
+        else {
+            const double alt = 2.0 * st.sum / (3.0 * (double)n * (double)(n - 1));
+            if (alt > est) est = alt;
+        }
+    }
+    if (bad) {   // overflow in the substitution gives 0; a NaN in the factors (a norm keeps it) gives NaN
+        double fnorm = 0.0;
+        RFLU_TRY(launch_clange<R>(h, RFLU_NORM_ONE, n, n, F, lda, 0, &fnorm));
+        *rcond = (fnorm != fnorm) ? fnorm : 0.0;
+        return RFLU_OK;
+    }
+    *rcond = est == 0.0 ? 0.0 : 1.0 / (anorm * est);
+    return RFLU_OK;
+}
+template int cgecon_dev<double>(Handle*, int, int64_t, const double*, int64_t, double, double*);
+template int cgecon_dev<float>(Handle*, int, int64_t, const float*, int64_t, double, double*);
+
+template <typename R>
+static int cgecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, int row_major,
+                          const double* anorm_dev, double* rcond_dev)
+{
+    if (!norm_ok("complex gecon_batched", norm)) return RFLU_ERR_ARG;
+    if (batch < 0 || n < 0) {
+        set_error("complex gecon_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (batch == 0) return RFLU_OK;
+    if (rcond_dev == nullptr || (n > 0 && (F == nullptr || anorm_dev == nullptr))) { set_error("complex gecon_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (n > 0 && (lda < n || (batch > 1 && strideF < (n - 1) * lda + n))) {
+        set_error("complex gecon_batched: lda=%lld strideF=%lld too small for n=%lld", (long long)lda, (long long)strideF, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    std::vector<double> host((size_t)batch, 1.0);
+    if (n == 0) {   // the empty matrix: rcond = 1
+        RFLU_HIP(hipMemcpyAsync(rcond_dev, host.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        return RFLU_OK;
+    }
+    if (cbatched_fits<R>(n, n)) {
+        RFLU_TRY(launch_cgecon_batched<R>(h, norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev));
+        RFLU_HIP(hipStreamSynchronize(h->stream));
+        return RFLU_OK;
+    }
+    if (row_major) return refuse_large_row_major<R>("complex gecon_batched");
+    RFLU_HIP(hipMemcpyAsync(host.data(), anorm_dev, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    for (int64_t b = 0; b < batch; ++b) {
+        const double an = host[(size_t)b];
+        if (an < 0.0) { host[(size_t)b] = std::nan(""); continue; }   // a member's bad anorm spoils its own output only
+        RFLU_TRY(cgecon_dev<R>(h, norm, n, F + 2 * b * strideF, lda, an, &host[(size_t)b]));
+    }
+    RFLU_HIP(hipMemcpyAsync(rcond_dev, host.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 // ---- mixed precision: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme; kernels: mixed.hip) ----
 // The Float32 factors stay in the row-major layout getrf_rm<float> leaves them in and every solve of the loop is getrs_rm<float> on
 // them: no n x n layout change after the first (getrs_cm_dev would pay one per solve).
@@ -1125,7 +1281,7 @@ static Handle* H(rflu_handle_t h) { return reinterpret_cast<Handle*>(h); }
 
 extern "C" {
 
-int rflu_version(void) { return 109; }
+int rflu_version(void) { return 110; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -1678,6 +1834,37 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
         CHECK_HANDLE(handle);                                                                                         \
         return clogabsdet_batched_dev<R>(H(handle), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs_dev,         \
                                          sign_dev);                                                                   \
+    }                                                                                                                 \
+    int rflu_lange_##SFX##_dev(rflu_handle_t handle, int norm, int64_t m, int64_t n, const R* A, int64_t lda,          \
+                               int row_major, double* out)                                                            \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return clange_dev<R>(H(handle), norm, m, n, A, lda, row_major, out);                                          \
+    }                                                                                                                 \
+    int rflu_lange_batched_##SFX##_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t m, int64_t n,           \
+                                       const R* A, int64_t lda, int64_t strideA, int row_major, double* out_dev)      \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return clange_batched<R>(H(handle), norm, batch, m, n, A, lda, strideA, row_major, out_dev);                  \
+    }                                                                                                                 \
+    int rflu_gecon_##SFX##_dev(rflu_handle_t handle, int norm, int64_t n, const R* F, int64_t lda, double anorm,      \
+                               double* rcond_out)                                                                     \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgecon_dev<R>(H(handle), norm, n, F, lda, anorm, rcond_out);                                           \
+    }                                                                                                                 \
+    int rflu_gecon_##SFX(rflu_handle_t handle, int norm, int64_t n, const R* F, int64_t lda, double anorm,            \
+                         double* rcond_out)                                                                           \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgecon_host<R>(H(handle), norm, n, F, lda, anorm, rcond_out);                                          \
+    }                                                                                                                 \
+    int rflu_gecon_batched_##SFX##_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t n, const R* F,          \
+                                       int64_t lda, int64_t strideF, int row_major, const double* anorm_dev,          \
+                                       double* rcond_dev)                                                             \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return cgecon_batched<R>(H(handle), norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev);        \
     }
 DEFINE_COMPLEX(cf64, double)
 DEFINE_COMPLEX(cf32, float)

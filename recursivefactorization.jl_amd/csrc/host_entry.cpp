@@ -542,6 +542,23 @@ int clogabsdet_host(Handle* h, int64_t n, const R* F, int64_t ld, const int64_t*
     return launch_clogabsdet<R>(h, n, static_cast<const R*>(h->hostB_dev), 1, dipiv, logabs, sign_re, sign_im, nullptr);
 }
 
+// rcond from complex host factors: H2D, then the device entry (which checks norm and anorm and serves the special values)
+template <typename R>
+int cgecon_host(Handle* h, int norm, int64_t n, const R* F, int64_t lda, double anorm, double* rcond)
+{
+    typedef HostCx<R> Z;
+    if (n < 0 || lda < std::max<int64_t>(n, 1) || rcond == nullptr || (n > 0 && F == nullptr)) {
+        set_error("complex gecon: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    if (n == 0) return cgecon_dev<R>(h, norm, 0, F, 1, anorm, rcond);
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(Z)));
+    Z* dF = static_cast<Z*>(h->hostA_dev);
+    RFLU_TRY(copy_in(dF, reinterpret_cast<const Z*>(F), lda, n, n, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));   // the special values return without another wait: the caller's array is free by then
+    return cgecon_dev<R>(h, norm, n, reinterpret_cast<const R*>(dF), n, anorm, rcond);
+}
+
 #define RFLU_INSTANTIATE_HOST(T)                                                                                                      \
     template int getrf_host<T>(Handle*, int64_t, int64_t, T*, int64_t, int64_t*, int, int64_t, int64_t*);                             \
     template int getrs_host<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t, bool);                      \
@@ -555,7 +572,8 @@ RFLU_INSTANTIATE_HOST(float)
     template int cgetrs_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t);                           \
     template int cgetrs_trans_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t, int);             \
     template int cgetri_host<R>(Handle*, int64_t, R*, int64_t, const int64_t*, int64_t*);                                             \
-    template int clogabsdet_host<R>(Handle*, int64_t, const R*, int64_t, const int64_t*, double*, double*, double*);
+    template int clogabsdet_host<R>(Handle*, int64_t, const R*, int64_t, const int64_t*, double*, double*, double*);               \
+    template int cgecon_host<R>(Handle*, int, int64_t, const R*, int64_t, double, double*);
 RFLU_INSTANTIATE_HOST_COMPLEX(double)
 RFLU_INSTANTIATE_HOST_COMPLEX(float)
 

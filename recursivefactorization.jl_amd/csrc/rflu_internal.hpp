@@ -247,6 +247,7 @@ struct Handle {
     bool batched_attr_set[3][4] = {};         // same for the batched kernels (batched_kernels.hpp): [getrf|getrs|getri][f64, f32, cf64, cf32]
     bool cinv_attr_set[2] = {false, false};   // same for the 64x64 triangular inverses of the complex getri (complex_inverse.hip): [cf64, cf32]
     size_t gecon_lds_asked[2] = {0, 0};       // dynamic LDS asked for the batched condition estimate so far (batched.hip: gecon_batched_kernel): [f64, f32]
+    size_t cgecon_lds_asked[2] = {0, 0};      // the same for the complex estimate (batched_complex.hip: cgecon_batched_kernel): [cf64, cf32]
     void* eng_state = nullptr;                // device: EngState (engine.hpp)
     void* eng_host = nullptr;                 // pinned host image of its initial value
     long long* eng_trace_buf = nullptr;       // device: RFLU_ENGINE_TRACE stamps + workgroup-time accounting (measurement only)

@@ -649,10 +649,24 @@ def _norm_code(p, what: str) -> int:
     raise ValueError(f"{what}: p must be 1 or inf (math.inf / \"inf\"), got {p!r}")
 
 
+_COMPLEX_COND = {"opnorm": "opnorm_complex", "rcond": "rcond_complex", "cond": "cond_complex", "opnorm_batched": "opnorm_complex_batched",
+                 "rcond_batched": "rcond_complex_batched", "cond_batched": "cond_complex_batched"}
+_REAL_COND = {v: k for k, v in _COMPLEX_COND.items()}
+
+
 def _cond_sfx(dtype, what: str) -> str:
     if str(dtype).replace("torch.", "") in ("complex128", "complex64"):
-        raise TypeError(f"{what}: complex element types are not served yet (got {dtype}); Float64/Float32 only")
+        raise TypeError(f"{what} serves Float64/Float32 only (got {dtype}); complex element types go to {_COMPLEX_COND[what]}")
     return _sfx(dtype)
+
+
+def _ccond_sfx(dtype, what: str) -> str:
+    name = str(dtype).replace("torch.", "")
+    if name == "complex128":
+        return "cf64"
+    if name == "complex64":
+        return "cf32"
+    raise TypeError(f"{what} serves ComplexF64/ComplexF32 only (got {dtype}); real element types go to {_REAL_COND[what]}")
 
 
 def _swap_norm(code: int) -> int:
@@ -872,6 +886,97 @@ def logdet_complex(F, *, trans="N", handle=None) -> complex:
     principal branch; no domain error, a complex logarithm has none)."""
     la, sg = logabsdet_complex(F, trans=trans, handle=handle)
     return complex(la, float(np.angle(sg)))
+
+
+def opnorm_complex(A, p=1, *, handle=None) -> float:
+    """``opnorm(A, 1)`` / ``opnorm(A, Inf)`` of a ``complex128`` / ``complex64`` m x n matrix: the largest column / row sum of the moduli
+    ``hypot(re, im)`` (LAPACK zlange / clange, ``rflu_lange_cf64_dev`` / ``_cf32_dev``), as a Python float.  Shapes and rules are those
+    of ``opnorm``: Float64 moduli and sums in a fixed order for both element types, bit-identical from run to run and whatever the
+    alignment; a column-major or row-major CUDA tensor, or a NumPy array (copied to the device).  A NaN in either part of any element
+    gives NaN, even next to an Inf; an empty matrix gives 0.  Take it BEFORE ``lu_complex_`` overwrites ``A``.  ``Adjoint(A)`` swaps 1
+    and inf; no ``trans`` letter is needed, because |conj z| = |z|: the transposed and the adjoint view have the same norms."""
+    code = _norm_code(p, "opnorm_complex")
+    if isinstance(A, Adjoint):
+        A, code = A.parent, _swap_norm(code)
+        if isinstance(A, Adjoint):
+            raise TypeError("opnorm_complex of a doubly wrapped matrix: unwrap it first")
+    if getattr(A, "ndim", None) != 2:
+        raise ValueError("opnorm_complex needs a matrix")
+    sfx = _ccond_sfx(A.dtype, "opnorm_complex")
+    m, n = int(A.shape[0]), int(A.shape[1])
+    if m == 0 or n == 0:
+        return 0.0
+    import torch
+
+    if not _is_torch(A):
+        if not isinstance(A, np.ndarray):
+            raise TypeError("A must be a numpy.ndarray or a CUDA torch.Tensor")
+        dev = torch.device("cuda", handle.device if handle is not None else 0)
+        if A.flags.f_contiguous and not A.flags.c_contiguous:   # a Fortran-ordered array stays column-major on the device
+            A = torch.from_numpy(np.ascontiguousarray(A.T)).to(dev).T
+        else:
+            A = torch.from_numpy(np.ascontiguousarray(A)).to(dev)
+    if not A.is_cuda:
+        raise _ffi.RfluError("torch input must live on the MI355X (device='cuda'); host data goes in as NumPy")
+    if A.is_conj():
+        A = A.resolve_conj()   # the moduli are the same; the library reads plain memory
+    if A.stride(0) == 1 and (A.stride(1) >= m or n == 1):
+        row_major, ld = 0, (int(A.stride(1)) if n > 1 else m)
+    elif A.stride(1) == 1 and (A.stride(0) >= n or m == 1):
+        row_major, ld = 1, (int(A.stride(0)) if m > 1 else n)
+    else:
+        raise ValueError("opnorm_complex: the matrix must be dense column-major or row-major (unit stride in one dimension)")
+    h = handle or _ffi.default_handle(A.device.index or 0)
+    h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+    out = ctypes.c_double(0.0)
+    h.call(f"rflu_lange_{sfx}_dev", code, m, n, ctypes.c_void_p(A.data_ptr()), ld, row_major, ctypes.byref(out))
+    return float(out.value)
+
+
+def rcond_complex(F, anorm, p=1, *, handle=None) -> float:
+    """``rcond`` for the ``LU`` that ``lu_complex`` / ``lu_complex_`` returned (LAPACK zgecon / cgecon, ``rflu_gecon_cf64`` / ``_cf32``
+    and their ``_dev`` forms): ``anorm = opnorm_complex(A, p)`` taken before the factorization, ``||inv(A)||`` estimated by Higham's
+    method (zlacn2: the pair of operators is M and its ADJOINT, the iterate is the phase vector ``v_i / |v_i|``) with at most 11 solves of
+    one right-hand side; ``F`` is only read.  The factors: a column-major CUDA tensor or a Fortran-ordered NumPy array (the complex path
+    is column-major only).  ``n == 0`` gives 1, ``anorm == 0`` or a ``u_ii`` with both parts zero gives 0, a NaN ``anorm`` or a NaN in
+    the factors gives NaN; ``anorm < 0`` raises.  ``Adjoint(F)`` swaps 1 and inf; no ``trans`` letter is needed, because |conj z| = |z|:
+    transpose(A) and A' have the same norms and the same condition number."""
+    code = _norm_code(p, "rcond_complex")
+    F, adj = _unwrap_adjoint(F, "rcond_complex")
+    if isinstance(F, LU) and F.factors is not None:
+        _ccond_sfx(F.factors.dtype, "rcond_complex")
+    A, n, sfx, kind, ld = _complex_square_factors(F, "rcond_complex")
+    if adj:
+        code = _swap_norm(code)
+    anorm = float(anorm)
+    if anorm < 0.0:
+        raise ValueError("rcond_complex: anorm must not be negative")
+    if n == 0:
+        return 1.0
+    h, ap = _handle_for(A, kind, handle)
+    out = ctypes.c_double(0.0)
+    h.call(f"rflu_gecon_{sfx}" + ("" if kind == "host" else "_dev"), code, n, ap, ld, anorm, ctypes.byref(out))
+    return float(out.value)
+
+
+def cond_complex(A, p=1, *, handle=None) -> float:
+    """``cond(A, 1)`` / ``cond(A, Inf)`` of a complex matrix as Julia computes them: ``opnorm_complex``, then ``lu_complex`` on a copy
+    (``check=False``), then ``1 / rcond_complex``; ``inf`` when ``rcond == 0`` (a singular matrix).  ``A`` stays intact.  ``Adjoint(A)``
+    swaps 1 and inf, which also serves transpose(A): |conj z| = |z|, so the two have the same condition number."""
+    code = _norm_code(p, "cond_complex")
+    if isinstance(A, Adjoint):
+        A, code = A.parent, _swap_norm(code)
+        if isinstance(A, Adjoint):
+            raise TypeError("cond_complex of a doubly wrapped matrix: unwrap it first")
+    if getattr(A, "ndim", None) != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("cond_complex needs a square matrix")
+    _ccond_sfx(A.dtype, "cond_complex")
+    if A.shape[0] == 0:
+        return 1.0
+    p = 1 if code == _ffi.NORM_ONE else float("inf")
+    anorm = opnorm_complex(A, p, handle=handle)
+    rc = rcond_complex(lu_complex(A, check=False, handle=handle), anorm, p, handle=handle)
+    return float("inf") if rc == 0.0 else 1.0 / rc
 
 
 class NotConvergedError(ArithmeticError):
@@ -1489,6 +1594,86 @@ def inv_complex_batched(F, *, trans="N", check=True, handle=None):
         if _as_bool(check):
             _check_batched_info(info_t, True)
     return X
+
+
+def opnorm_complex_batched(A, p=1, *, handle=None):
+    """``opnorm_complex(A_b, p)`` of every matrix of a complex (batch, m, n) CUDA tensor (``rflu_lange_batched_cf64_dev`` / ``_cf32_dev``;
+    one workgroup per matrix up to 128 x 128): a Float64 CUDA tensor of length ``batch``, entry b bit-identical to ``opnorm_complex`` on
+    matrix b.  ``Adjoint(A)`` swaps 1 and inf (|conj z| = |z|: no ``trans`` letter is needed)."""
+    code = _norm_code(p, "opnorm_complex_batched")
+    if isinstance(A, Adjoint):
+        A, code = A.parent, _swap_norm(code)
+    if not _is_torch(A) or A.ndim != 3:
+        raise TypeError("opnorm_complex_batched needs a 3-D CUDA tensor (batch, m, n)")
+    sfx = _ccond_sfx(A.dtype, "opnorm_complex_batched")
+    if not A.is_cuda:
+        raise TypeError("opnorm_complex_batched: the batch must live on the MI355X (device='cuda')")
+    import torch
+
+    if A.is_conj():
+        A = A.resolve_conj()
+    batch, m, n = (int(x) for x in A.shape)
+    row_major, ld, stride_a = _batched_layout(A, "opnorm_complex_batched")
+    out = torch.zeros(batch, dtype=torch.float64, device=A.device)
+    if batch > 0 and m > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        h.call(f"rflu_lange_batched_{sfx}_dev", code, batch, m, n, ctypes.c_void_p(A.data_ptr()), ld, stride_a, row_major,
+               ctypes.c_void_p(out.data_ptr()))
+    return out
+
+
+def rcond_complex_batched(F, anorm, p=1, *, handle=None):
+    """``rcond_complex`` of every matrix of the ``BatchedLU`` that ``lu_complex_batched_`` returned (``rflu_gecon_batched_cf64_dev`` /
+    ``_cf32_dev``: ONE launch up to n = 64 for ``complex128`` and n = 128 for ``complex64``, the whole estimator inside the kernel on the
+    factors held in LDS; larger column-major matrices are looped over ``rflu_gecon_c*``, larger row-major ones are refused).  ``anorm``: a
+    Float64 CUDA tensor of length ``batch`` (``opnorm_complex_batched`` before the factorization).  Returns a Float64 CUDA tensor of
+    length ``batch``; a singular member gives 0 and a NaN member NaN in its own entry only.  ``Adjoint(F)`` swaps 1 and inf (|conj z| =
+    |z|: no ``trans`` letter is needed)."""
+    code = _norm_code(p, "rcond_complex_batched")
+    G, adj = _unwrap_adjoint(F, "rcond_complex_batched")
+    if not isinstance(G, BatchedLU):
+        raise TypeError("rcond_complex_batched needs the BatchedLU that lu_complex_batched_ returned")
+    A = G.factors
+    if not (_is_torch(A) and A.is_cuda) or A.ndim != 3:
+        raise TypeError("rcond_complex_batched: the factors must be a 3-D CUDA tensor")
+    if A.shape[1] != A.shape[2]:
+        raise ValueError("rcond_complex_batched needs square factorizations")
+    sfx = _ccond_sfx(A.dtype, "rcond_complex_batched")
+    row_major, ld, stride_f = _batched_layout(A, "rcond_complex_batched")
+    if adj:
+        code = _swap_norm(code)
+    import torch
+
+    batch, n = int(A.shape[0]), int(A.shape[1])
+    if not (_is_torch(anorm) and anorm.is_cuda and anorm.dtype == torch.float64 and anorm.ndim == 1 and anorm.shape[0] == batch
+            and (batch <= 1 or anorm.stride(0) == 1)):
+        raise TypeError("rcond_complex_batched: anorm must be a contiguous Float64 CUDA tensor of length batch")
+    out = torch.ones(batch, dtype=torch.float64, device=A.device)
+    if batch > 0 and n > 0:
+        h = handle or _ffi.default_handle(A.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(A.device).cuda_stream)
+        h.call(f"rflu_gecon_batched_{sfx}_dev", code, batch, n, ctypes.c_void_p(A.data_ptr()), ld, stride_f, row_major,
+               ctypes.c_void_p(anorm.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    return out
+
+
+def cond_complex_batched(A, p=1, *, handle=None):
+    """``cond_complex(A_b, p)`` of every matrix of a complex (batch, n, n) CUDA tensor: ``opnorm_complex_batched``, ``lu_complex_batched``
+    on a copy (``check=False``), ``1 / rcond_complex_batched``; ``inf`` where ``rcond == 0``.  A Float64 CUDA tensor of length ``batch``.
+    ``Adjoint(A)`` swaps 1 and inf (|conj z| = |z|: no ``trans`` letter is needed)."""
+    code = _norm_code(p, "cond_complex_batched")
+    if isinstance(A, Adjoint):
+        A, code = A.parent, _swap_norm(code)
+    if not _is_torch(A) or A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError("cond_complex_batched needs a 3-D CUDA tensor (batch, n, n)")
+    _ccond_sfx(A.dtype, "cond_complex_batched")
+    import torch
+
+    p = 1 if code == _ffi.NORM_ONE else float("inf")
+    anorm = opnorm_complex_batched(A, p, handle=handle)
+    rc = rcond_complex_batched(lu_complex_batched(A, check=False, handle=handle), anorm, p, handle=handle)
+    return torch.where(rc == 0, torch.full_like(rc, float("inf")), 1.0 / rc)
 
 
 def last_path(device: int = 0) -> str:
