@@ -525,7 +525,11 @@ int rflu_gecon_batched_cf32_dev(rflu_handle_t handle, int norm, int64_t batch, i
  * Float32 factors of a Float64 matrix.  A (column-major, lda >= n) is only read.  F32_dev: caller-owned n x n ROW-MAJOR
  * (ldf >= n, the layout and rules of rflu_getrf_rm_f32_dev), receives L\U.  ipiv / pivot / blocksize / info as in
  * rflu_getrf_rm_f32_dev (info = first exactly-zero pivot OF THE FLOAT32 FACTORIZATION).  *anorm_out (host, required) = ||A||_inf,
- * bit-identical from run to run. */
+ * bit-identical from run to run.  The Float32 image that is factored is the IEEE conversion of every entry of A: round to nearest, ties
+ * to even; an entry beyond FLT_MAX + half an ulp becomes +-Inf, a NaN stays a NaN, and underflow is GRADUAL: an entry in the Float32
+ * subnormal range becomes the nearest subnormal, nothing is flushed to zero (an entry of magnitude 2^-150 or less becomes a zero, and
+ * as a pivot sets info).  The image, ||A||_inf and the factors do not depend on the alignment of A / F32 or on lda / ldf.  The complex
+ * entry below converts both parts of every element in the same way. */
 int rflu_mixed_getrf_f64_dev(rflu_handle_t handle, int64_t n, const double* A_dev, int64_t lda, float* F32_dev, int64_t ldf,
                              int64_t* ipiv_dev, int pivot, int64_t blocksize, double* anorm_out, int64_t* info);
 /* X <- A^-1 B to Float64 backward error by iterative refinement.  A, B are only read; X (n x nrhs, ldx) is written.

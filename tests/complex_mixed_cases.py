@@ -5,11 +5,14 @@ tests/test_gpu_complex_mixed.py uses them on the GPU).  Pure numpy / scipy, no G
     in np.clongdouble; the rule is ||r_k||_inf <= ||x_k||_inf ||A||_inf eps64 sqrt(n) per column, every norm in MODULI.
   * exact_solve_case: CONSTRUCTED row-major factors L\\U and interchanges with a Gaussian-integer solution: every partial sum of both
     substitutions is exact in Float32 in any order, so the forward solve must return X by ==.  See its docstring.
+  * cdemote_input / cdemote_restated, crefine_case: the complex inputs of the exact tests of the demoted image and of the refinement
+    loop (tests/test_gpu_complex_mixed_exact.py); what makes them exact is said in tests/mixed_cases.py, parts A and B.
 """
 import functools
 
 import numpy as np
 
+import mixed_cases as mc
 from complex_inv_cases import DIAG
 
 EPS = float(np.finfo(np.float64).eps)
@@ -161,5 +164,122 @@ def exact_solve_case(n, nrhs):
     assert np.array_equal(c.W.astype(np.complex128), np.tril(L, -1) + U)                  # the factors are Float32 numbers
     assert np.array_equal(c.B.astype(np.complex128) * 2, B2[0] + 1j * B2[1])              # so is B
     for a in (c.W, c.X, c.B, c.ipiv):
+        a.setflags(write=False)
+    return c
+
+
+# ---- the demoted image, element by element (part A of tests/mixed_cases.py, complex) ---------------------------------------------------
+CDEMOTE_SIZES = [1, 2, 63, 64, 65, 129, 193]       # both sides of the 64 x 64 tile, several tiles in the diagonal order
+CDM_T = 64                                         # csrc/complex_mixed.hip
+CMUTATIONS = ["truncation", "half_away", "dropped_last_column"]
+
+
+@functools.lru_cache(maxsize=None)
+def cdemote_input(n, kind, fam):
+    """The n x n ComplexF64 input, column-major, read-only.  kind 'upper' / 'lower' as mixed_cases.demote_input: the pivot rule is the
+    largest modulus with the lowest row on ties, Smith's division of a zero numerator gives 0 and a division by 1 + 0i returns the
+    numerator, so triu(F32) (upper) and tril(F32, -1) (lower) are the demoted input itself.
+    fam 'random': both parts from mixed_cases.family (lower: parts in (1/4, 1/2), so every modulus is below 1/sqrt(2) < 3/4);
+    fam 'axis': one part from the family, the other zero -- purely real or purely imaginary at random -- so that hypot is exact, every
+    modulus is on the grid 2^-40 and ||A||_inf must come back by == (lower: the nonzero part in (1/2, 3/4))."""
+    rng = np.random.default_rng([42000, n, 0 if kind == "upper" else 1, 0 if fam == "random" else 1])
+    if fam == "random":
+        kw = {} if kind == "upper" else {"exps": (-2,)}
+        V = mc.family((n, n), rng, **kw)[0] + 1j * mc.family((n, n), rng, **kw)[0]
+    else:
+        kw = {} if kind == "upper" else {"exps": (-1,), "mbits": 22}
+        V = mc.family((n, n), rng, **kw)[0] * np.where(rng.integers(0, 2, size=(n, n)) == 1, 1j, 1.0)
+    A = np.asfortranarray(np.triu(V) if kind == "upper" else np.tril(V, -1) + np.eye(n))
+    A.setflags(write=False)
+    return A
+
+
+def expected_cimage(A):
+    """numpy's IEEE conversion of both parts"""
+    with np.errstate(over="ignore"):
+        return np.asarray(A).astype(np.complex64)
+
+
+def exact_axis_anorm(A):
+    """||A||_inf of an on-axis matrix: the modulus of an entry is |re| + |im| with one of them zero"""
+    assert not np.any((A.real != 0) & (A.imag != 0))
+    return mc.exact_anorm(np.abs(A.real) + np.abs(A.imag))
+
+
+def cdemote_restated(A, mutation=None):
+    """(F, anorm): cdemote_relayout_kernel + rowsum_max_kernel restated tile by tile: lane l owns row l of a 64 x 64 tile, wave w adds
+    hypot(re, im) over the columns c = w, w + 4, .. in ascending order, the waves' sums are added as ((s0 + s1) + s2) + s3, a row's
+    tiles in tile order.  The 16-byte and the element-wise forms move the same elements.  F starts as SENTINEL32 in both parts."""
+    n = A.shape[0]
+    conv = {"truncation": mc.truncate32, "half_away": mc.half_away32}.get(mutation, mc.expected_image)
+    F = np.full((n, n), mc.SENTINEL32 * (1 + 1j), dtype=np.complex64)
+    nt = (n + CDM_T - 1) // CDM_T
+    part = np.zeros((nt, n))
+    for bx in range(nt):
+        for by in range(nt):
+            tj = (by + bx) % nt
+            i0, j0 = bx * CDM_T, tj * CDM_T
+            P = np.zeros((CDM_T, CDM_T), dtype=np.complex128)
+            blk = A[i0:i0 + CDM_T, j0:j0 + CDM_T]
+            P[:blk.shape[0], :blk.shape[1]] = blk
+            tile = conv(P.real) + 1j * conv(P.imag)
+            rsum = np.zeros((4, CDM_T))
+            for w in range(4):
+                for c in range(w, CDM_T, 4):
+                    rsum[w] = rsum[w] + np.hypot(P[:, c].real, P[:, c].imag)
+            rows, cols = min(CDM_T, n - i0), min(CDM_T, n - j0)
+            part[tj, i0:i0 + rows] = (((rsum[0] + rsum[1]) + rsum[2]) + rsum[3])[:rows]
+            if mutation == "dropped_last_column" and cols < CDM_T:
+                cols -= 1
+            F[i0:i0 + rows, j0:j0 + cols] = tile[:rows, :cols]
+    s = np.zeros(n)
+    for t in range(nt):
+        s = s + part[t]
+    return F, float(s.max())
+
+
+# ---- the refinement loop, step by step (part B of tests/mixed_cases.py, complex) -------------------------------------------------------
+REFINE_N = [1, 33, 257, 513]
+REFINE_NRHS = [1, 8, 9, 33, 65]      # 8 and 9: both sides of CNARROW (the column-major and the row-major image of the right-hand sides)
+# c_k = 1 + 2^-S_CPLX.  The largest s that the dense cases allow.  Two conditions bind (test_complex_mixed_cases.py recomputes both):
+# the largest row sum of the moduli of all terms of B - A X over the grid above is 25415 units of 1/2 (n = 513, nrhs = 8), 15 bits, so
+# 15 + s <= 53 allows 38; the rule must be MISSED at step 0 by a factor no rounding of hypot or sqrt can bridge (2^10 is asked for), and
+# with the dense A of n = 513 (||A||_inf about 6000, ||b|| / ||x|| about 40) a scaled column misses it by 2^(43.6 - s): s <= 33.
+S_CPLX = 33
+
+
+class CRefineCase(mc.RefineCase):
+    """mixed_cases.RefineCase with complex A, x0, b0; F32 is complex64; every entry is a Gaussian integer times 1/2."""
+
+
+@functools.lru_cache(maxsize=None)
+def crefine_case(n, nrhs):
+    """exact_solve_case(n, nrhs) as what rflu_mixed_getrs_cf64_dev takes: A = P^T L U formed in integer arithmetic on 2 U, dense
+    ComplexF64; ||A||_inf in moduli (rounded: the rule is missed or met by orders of magnitude, mixed_cases.refine_proof)."""
+    e = exact_solve_case(n, nrhs)
+    L, U2 = np.rint(e.L.real).astype(np.int64) + 1j * np.rint(e.L.imag).astype(np.int64), 2 * e.U
+    lr, li, ur, ui = (np.rint(p).astype(np.int64) for p in (L.real, L.imag, U2.real, U2.imag))
+    A2 = [lr @ ur - li @ ui, lr @ ui + li @ ur]                       # 2 P A
+    for k in range(n - 1, -1, -1):                                    # P^T: the interchanges undone last first
+        p = e.ipiv[k] - 1
+        if p != k:
+            for part in A2:
+                part[[k, p]] = part[[p, k]]
+    perm = list(range(n))
+    for k in range(n):
+        p = int(e.ipiv[k]) - 1
+        if p != k:
+            perm[k], perm[p] = perm[p], perm[k]
+    c = CRefineCase()
+    c.n, c.nrhs, c.ipiv = n, nrhs, e.ipiv
+    c.A = np.asfortranarray((A2[0] + 1j * A2[1]) / 2)
+    c.x0, c.b0 = e.X.astype(np.complex128), e.B.astype(np.complex128)
+    assert np.array_equal(c.A @ c.x0, c.b0)                           # small Gaussian half-integers: exact in complex128
+    c.anorm = anorm_inf(c.A)
+    c.F32 = e.W
+    c.L, c.U, c.perm = e.L.astype(np.complex64), e.U.astype(np.complex64), np.asarray(perm)
+    c.term_sum = float((np.abs(c.A) @ np.abs(c.x0) + np.abs(c.b0)).max())
+    c.fwd_sum, c.bwd_sum = e.fwd_sum, e.bwd_sum
+    for a in (c.A, c.x0, c.b0):
         a.setflags(write=False)
     return c

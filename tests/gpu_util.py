@@ -27,6 +27,43 @@ def to_dev_cm(A):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(A).T)).to("cuda:0").T
 
 
+class Store:
+    """A real or complex matrix in a REAL device buffer (complex: interleaved re, im) with leading dimension ld (in elements), its first
+    element `off` real words after a 16-byte boundary, and `sentinel` in every word that is not the matrix: the words in front, the
+    ld - inner elements behind every column (row, if row_major).  `ptr` is what the C entries take, `get()` reads the matrix back,
+    `raw()` the whole buffer, `padding_intact()` says whether every other word still holds the sentinel."""
+
+    def __init__(self, M, ld, real=np.float64, off=0, row_major=False, sentinel=-7.25):
+        M = np.asarray(M)
+        S = M if row_major else M.T                                   # outer x inner, inner contiguous
+        self.outer, self.inner = S.shape
+        self.cplx = np.iscomplexobj(M)
+        self.w = 2 if self.cplx else 1
+        self.ld, self.off, self.row_major, self.sentinel = ld, off, row_major, sentinel
+        assert ld >= self.inner
+        host = np.full(off + self.outer * ld * self.w, sentinel, dtype=real)
+        v = host[off:].reshape(self.outer, ld, self.w)
+        v[:, :self.inner, 0] = S.real
+        if self.cplx:
+            v[:, :self.inner, 1] = S.imag
+        self.buf = torch.from_numpy(host).to("cuda:0")
+        assert self.buf.data_ptr() % 16 == 0
+        self.address = self.buf.data_ptr() + off * host.itemsize
+        self.ptr = ctypes.c_void_p(self.address)
+
+    def raw(self):
+        return self.buf.cpu().numpy()
+
+    def get(self):
+        v = self.raw()[self.off:].reshape(self.outer, self.ld, self.w)[:, :self.inner]
+        S = v[..., 0] + 1j * v[..., 1] if self.cplx else v[..., 0]
+        return S if self.row_major else S.T
+
+    def padding_intact(self):
+        r = self.raw()
+        return bool((r[:self.off] == self.sentinel).all() and (r[self.off:].reshape(self.outer, self.ld, self.w)[:, self.inner:] == self.sentinel).all())
+
+
 def sfx(dtype):
     return "f64" if np.dtype(dtype) == np.float64 else "f32"
 
