@@ -457,7 +457,7 @@ int rflu_gemm_rm_cf32_dev(rflu_handle_t handle, int64_t M, int64_t N, int64_t K,
                           const float* B_dev, int64_t ldb, float* C_dev, int64_t ldc);
 
 /* ---- COMPLEX NORMS, CONDITION: the NORMS, CONDITION block above for ComplexF64 / ComplexF32 (LAPACK zlange / clange + zgecon / cgecon).
- * Kernels: csrc/complex_condest.hip and cgecon_batched_kernel in csrc/batched_complex.hip; DESIGN.md section 4.12.  The contract is that
+ * Kernels: csrc/condest.hip and cgecon_batched_kernel in csrc/batched_complex.hip; DESIGN.md section 4.12.  The contract is that
  * of the real block with the storage rules of the other complex entries: a matrix crosses as double* / float* at interleaved (re, im)
  * pairs, every lda / strideA / strideF counts COMPLEX elements, a pointer aligned to the real type is enough.  Argument lists are those
  * of the _f64 / _f32 entries of the same name.  There is NO rflu_gecon_rm_c*: the single-matrix complex path is column-major only.

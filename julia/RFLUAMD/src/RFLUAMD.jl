@@ -727,7 +727,7 @@ function getri_batched_dev!(Ainv::Ptr{ComplexF32}, ldi::Integer, strideI::Intege
     return Ainv
 end
 
-# ---- operator norms and the condition estimate for ComplexF64 / ComplexF32 (rflu_lange_c* / rflu_gecon_c*, csrc/complex_condest.hip and
+# ---- operator norms and the condition estimate for ComplexF64 / ComplexF32 (rflu_lange_c* / rflu_gecon_c*, csrc/condest.hip and
 # cgecon_batched_kernel of csrc/batched_complex.hip): the methods of lange_dev / lange_batched_dev! / gecon_dev! / gecon_host /
 # gecon_batched_dev! for the complex pointer and matrix types.  Moduli are hypot(re, im) in Float64; the estimator is LAPACK zlacn2 on M
 # and M' with the start and closing vectors of include/rflu.h.  A single matrix is column-major only (there is no rflu_gecon_rm_c*, so

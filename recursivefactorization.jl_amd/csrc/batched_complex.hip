@@ -536,7 +536,7 @@ struct CBStat {
     int argmax, nonfinite;
 };
 
-// the modulus the estimator adds: Float64 hypot, NaN when either part is one (cabs64 of complex_condest.hip)
+// the modulus the estimator adds: Float64 hypot, NaN when either part is one (CplxElem::abs of rflu_internal.hpp)
 template <typename R>
 __device__ __forceinline__ double cbabs64(Cx<R> z)
 {
@@ -547,7 +547,7 @@ __device__ __forceinline__ double cbabs64(Cx<R> z)
 
 // The statistics of the group's work vector X(0 .. n, 0), the same in every thread of the group: bstats of batched.hip on moduli and
 // without the sign test.  Thread t < n holds x_t.  sum|x_t| is added by the tree t += t + s, s = 64 .. 1 -- the tree of
-// ccond_stats_kernel (complex_condest.hip) on one chunk, whose steps s = 128 and, for n <= 64, s = 64 add +0.0 --; the first index of the
+// cond_stats_kernel (condest.hip) on one chunk, whose steps s = 128 and, for n <= 64, s = 64 add +0.0 --; the first index of the
 // largest modulus and the flag do not depend on an order.  sc: the group's scratch (3 doubles, 131 for n > 64).
 // Barriers: two (three for n > 64), under no condition but n, which the whole workgroup shares.
 template <typename R>

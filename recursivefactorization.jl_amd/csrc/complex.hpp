@@ -138,22 +138,7 @@ template <typename R>
 int clogabsdet_batched_dev(Handle* h, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, const int64_t* ipiv,
                            int64_t stride_ipiv, double* logabs_dev, double* sign_dev);
 
-// complex_condest.hip: the operator norms of a complex matrix and the vector kernels of the complex condition
-// estimate.  Every sum is Float64 in the fixed order of condest.hip with "element" read as complex element; |a| = hypot in Float64, a
-// NaN in either part gives NaN.  *out (host) = the 1- or Inf-norm of the m x n matrix A; synchronises.
-template <typename R>
-int launch_clange(Handle* h, int norm, int64_t m, int64_t n, const R* A, int64_t lda, int row_major, double* out);
-// out_dev[b] (device) = the same for matrix b at A + 2*b*strideA, bit-identical to launch_clange on that matrix.  Enqueued only.
-template <typename R>
-int launch_clange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const R* A, int64_t lda, int64_t strideA, int row_major,
-                          double* out_dev);
-// the estimator's vector x (n contiguous complex elements on the device): COND_FILL_ONES / _UNIT / _ALT with a zero imaginary part
-template <typename R>
-int launch_ccond_fill(Handle* h, int64_t n, R* x, int mode, int64_t j);
-// the statistics of x (host, the stream is synchronised; CondStats::differs is not used); write_phase: afterwards x holds x_i / |x_i|
-// (1 + 0i where both parts are zero)
-template <typename R>
-int launch_ccond_stats(Handle* h, int64_t n, R* x, int64_t jq, int write_phase, CondStats* out);
+// the complex condition estimate (the norms and the vector kernels are condest.hip, declared in rflu_internal.hpp)
 // batched_complex.hip: the whole estimator on a matrix held in LDS, one launch for n <= CBATCHED_MAX_DIM_CF64 / _CF32
 template <typename R>
 int launch_cgecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, int row_major,

@@ -636,36 +636,38 @@ static int getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_
     return RFLU_OK;
 }
 
-// ---- operator norms and the condition estimate (include/rflu.h: NORMS, CONDITION; kernels: condest.hip) --------
-static bool norm_ok(const char* who, int norm)
+// ---- operator norms and the condition estimate, real and complex (include/rflu.h: NORMS, COMPLEX NORMS, CONDITION; kernels: condest.hip
+// and the batched estimators of batched.hip / batched_complex.hip, DESIGN.md sections 4.11, 4.12).  E is the element trait of
+// rflu_internal.hpp: sizes, leading dimensions and strides count elements, every message starts with E::WHO.
+static bool norm_ok(const char* pre, const char* who, int norm)
 {
     if (norm == RFLU_NORM_ONE || norm == RFLU_NORM_INF) return true;
-    set_error("%s: norm must be RFLU_NORM_ONE (1) or RFLU_NORM_INF (2), got %d", who, norm);
+    set_error("%s%s: norm must be RFLU_NORM_ONE (1) or RFLU_NORM_INF (2), got %d", pre, who, norm);
     return false;
 }
 
-template <typename T>
-static int lange_dev(Handle* h, int norm, int64_t m, int64_t n, const T* A, int64_t lda, int row_major, double* out)
+template <typename E>
+static int lange_dev(Handle* h, int norm, int64_t m, int64_t n, const typename E::real* A, int64_t lda, int row_major, double* out)
 {
-    if (!norm_ok("lange", norm)) return RFLU_ERR_ARG;
+    if (!norm_ok(E::WHO, "lange", norm)) return RFLU_ERR_ARG;
     if (m < 0 || n < 0 || out == nullptr || lda < std::max<int64_t>(row_major ? n : m, 1) || (m > 0 && n > 0 && A == nullptr)) {
-        set_error("lange: bad arguments m=%lld n=%lld lda=%lld (or a null pointer)", (long long)m, (long long)n, (long long)lda);
+        set_error("%slange: bad arguments m=%lld n=%lld lda=%lld (or a null pointer)", E::WHO, (long long)m, (long long)n, (long long)lda);
         return RFLU_ERR_ARG;
     }
-    return launch_lange<T>(h, norm, m, n, A, lda, row_major, out);
+    return launch_lange<E>(h, norm, m, n, A, lda, row_major, out);
 }
 
-template <typename T>
-static int lange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const T* A, int64_t lda, int64_t strideA, int row_major,
-                         double* out_dev)
+template <typename E>
+static int lange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const typename E::real* A, int64_t lda, int64_t strideA,
+                         int row_major, double* out_dev)
 {
-    if (!norm_ok("lange_batched", norm)) return RFLU_ERR_ARG;
+    if (!norm_ok(E::WHO, "lange_batched", norm)) return RFLU_ERR_ARG;
     if (batch < 0 || m < 0 || n < 0) {
-        set_error("lange_batched: negative size batch=%lld m=%lld n=%lld", (long long)batch, (long long)m, (long long)n);
+        set_error("%slange_batched: negative size batch=%lld m=%lld n=%lld", E::WHO, (long long)batch, (long long)m, (long long)n);
         return RFLU_ERR_ARG;
     }
     if (batch == 0) return RFLU_OK;
-    if (out_dev == nullptr || (m > 0 && n > 0 && A == nullptr)) { set_error("lange_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (out_dev == nullptr || (m > 0 && n > 0 && A == nullptr)) { set_error("%slange_batched: null pointer", E::WHO); return RFLU_ERR_ARG; }
     if (m == 0 || n == 0) {
         RFLU_HIP(hipMemsetAsync(out_dev, 0, (size_t)batch * sizeof(double), h->stream));
         RFLU_HIP(hipStreamSynchronize(h->stream));
@@ -673,23 +675,88 @@ static int lange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t 
     }
     const int64_t len = row_major ? n : m, cnt = row_major ? m : n;
     if (lda < len || (batch > 1 && strideA < (cnt - 1) * lda + len)) {
-        set_error("lange_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", (long long)lda, (long long)strideA, (long long)m,
-                  (long long)n, row_major ? "row-major" : "column-major");
+        set_error("%slange_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", E::WHO, (long long)lda, (long long)strideA,
+                  (long long)m, (long long)n, row_major ? "row-major" : "column-major");
         return RFLU_ERR_ARG;
     }
-    RFLU_TRY(launch_lange_batched<T>(h, norm, batch, m, n, A, lda, strideA, row_major, out_dev));
+    RFLU_TRY(launch_lange_batched<E>(h, norm, batch, m, n, A, lda, strideA, row_major, out_dev));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
 
-// rcond = 1 / (anorm * est): Higham's estimator (LAPACK xLACN2 with the integer start and closing vectors stated in rflu.h) on
-// M = U^-1 L^-1.  ONE layout change per call: W = the transposed image of F in h->work.  Column-major factors: W is their row-major
-// image, every M x is getrs_rm on W and every M^T x is getrs_trans_view on F in place; row-major factors: M x is getrs_rm on F in place
-// and M^T x is getrs_trans_view on W.  The work vector stays in the row-major n x 1 form the chain kernels take (ldb = 1).
+// Higham's estimate of ||M||_1 (LAPACK xLACN2 with the integer start and closing vectors stated in rflu.h) on the caller's work vector
+// x: fill(mode, j) makes a start vector, apply(false) is x <- M x and apply(true) x <- M^T x (complex: M^H x), stats(jq, write, &st) the
+// statistics of x, after which x holds its signs (phases) when `write`.  sign_ends: an unchanged sign vector ends the iteration (real
+// elements; complex phases are never compared).  *bad: a NaN or Inf turned up in x, *est then says nothing.
+template <typename Fill, typename Apply, typename Stats>
+static int higham_estimate(int64_t n, bool sign_ends, Fill fill, Apply apply, Stats stats, double* est_out, bool* bad_out)
+{
+    CondStats st;
+    double est = 0.0;
+    bool bad = false, closing = false;
+    int64_t j = 0;
+    for (int round = 0; round < 5; ++round) {
+        RFLU_TRY(fill(round == 0 ? COND_FILL_ONES : COND_FILL_UNIT, j));
+        RFLU_TRY(apply(false));
+        RFLU_TRY(stats(-1, 1, &st));
+        if (st.nonfinite) { bad = true; break; }
+        if (round == 0) {
+            est = st.sum / (double)n;
+            if (n == 1) break;
+        } else {
+            const double est_old = est;
+            est = st.sum;
+            if ((sign_ends && st.differs == 0) || est <= est_old) { closing = true; break; }
+        }
+        RFLU_TRY(apply(true));
+        RFLU_TRY(stats(j, 0, &st));
+        if (st.nonfinite) { bad = true; break; }
+        j = (int64_t)st.argmax;
+        if ((round > 0 && st.xj_abs == st.maxabs) || round == 4) { closing = true; break; }
+    }
+    if (closing) {
+        RFLU_TRY(fill(COND_FILL_ALT, 0));
+        RFLU_TRY(apply(false));
+        RFLU_TRY(stats(-1, 0, &st));
+        if (st.nonfinite) bad = true;
+        else {
+            const double alt = 2.0 * st.sum / (3.0 * (double)n * (double)(n - 1));
+            if (alt > est) est = alt;
+        }
+    }
+    *est_out = est;
+    *bad_out = bad;
+    return RFLU_OK;
+}
+
+// the estimate on the n elements at x (and, real elements, their signs at sgn) with the caller's two solves, then rcond
+template <typename E, typename Apply>
+static int gecon_estimate(Handle* h, int64_t n, const typename E::real* F, int64_t ld, typename E::real* x, typename E::real* sgn,
+                          double anorm, Apply apply, double* rcond)
+{
+    double est = 0.0;
+    bool bad = false;
+    RFLU_TRY(higham_estimate(
+        n, E::PARTS == 1, [&](int mode, int64_t j) { return launch_cond_fill<E>(h, n, x, mode, j); }, apply,
+        [&](int64_t jq, int write, CondStats* st) { return launch_cond_stats<E>(h, n, x, sgn, jq, write, st); }, &est, &bad));
+    if (bad) {   // overflow in the substitution gives 0; a NaN in the factors (a norm keeps it) gives NaN
+        double fnorm = 0.0;
+        RFLU_TRY(launch_lange<E>(h, RFLU_NORM_ONE, n, n, F, ld, 0, &fnorm));
+        *rcond = (fnorm != fnorm) ? fnorm : 0.0;
+        return RFLU_OK;
+    }
+    *rcond = est == 0.0 ? 0.0 : 1.0 / (anorm * est);
+    return RFLU_OK;
+}
+
+// rcond = 1 / (anorm * est) with Higham's estimator on M = U^-1 L^-1.  ONE layout change per call: W = the transposed image of F in
+// h->work.  Column-major factors: W is their row-major image, every M x is getrs_rm on W and every M^T x is getrs_trans_view on F in
+// place; row-major factors: M x is getrs_rm on F in place and M^T x is getrs_trans_view on W.  The work vector stays in the row-major
+// n x 1 form the chain kernels take (ldb = 1).
 template <typename T>
 int gecon_dev(Handle* h, int norm, int64_t n, const T* F, int64_t ld, int row_major, double anorm, double* rcond)
 {
-    if (!norm_ok("gecon", norm)) return RFLU_ERR_ARG;
+    if (!norm_ok("", "gecon", norm)) return RFLU_ERR_ARG;
     if (n < 0 || ld < std::max<int64_t>(n, 1) || rcond == nullptr || (n > 0 && F == nullptr)) {
         set_error("gecon: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
         return RFLU_ERR_ARG;
@@ -723,62 +790,62 @@ int gecon_dev(Handle* h, int norm, int64_t n, const T* F, int64_t ld, int row_ma
         if (transposed != (norm == RFLU_NORM_INF)) return getrs_trans_view<T>(h, n, 1, V, ldv, nullptr, x, 1);
         return getrs_rm<T>(h, n, 1, RM, ldrm, nullptr, x, 1);
     };
-    CondStats st;
-    double est = 0.0;
-    bool bad = false, closing = false;
-    int64_t j = 0;
-    for (int round = 0; round < 5; ++round) {
-        RFLU_TRY(launch_cond_fill<T>(h, n, x, round == 0 ? COND_FILL_ONES : COND_FILL_UNIT, j));
-        RFLU_TRY(apply(false));
-        RFLU_TRY(launch_cond_stats<T>(h, n, x, sgn, -1, 1, &st));   // x and sgn hold sign(x) afterwards
-        if (st.nonfinite) { bad = true; break; }
-        if (round == 0) {
-            est = st.sum / (double)n;
-            if (n == 1) break;
-        } else {
-            const double est_old = est;
-            est = st.sum;
-            if (st.differs == 0 || est <= est_old) { closing = true; break; }
-        }
-        RFLU_TRY(apply(true));
-        RFLU_TRY(launch_cond_stats<T>(h, n, x, sgn, j, 0, &st));
-        if (st.nonfinite) { bad = true; break; }
-        j = (int64_t)st.argmax;
-        if ((round > 0 && st.xj_abs == st.maxabs) || round == 4) { closing = true; break; }
-    }
-    if (closing) {
-        RFLU_TRY(launch_cond_fill<T>(h, n, x, COND_FILL_ALT, 0));
-        RFLU_TRY(apply(false));
-        RFLU_TRY(launch_cond_stats<T>(h, n, x, sgn, -1, 0, &st));
-        if (st.nonfinite) bad = true;
-        else {
-            const double alt = 2.0 * st.sum / (3.0 * (double)n * (double)(n - 1));
-            if (alt > est) est = alt;
-        }
-    }
-    if (bad) {   // overflow in the substitution gives 0; a NaN in the factors (a norm keeps it) gives NaN
-        double fnorm = 0.0;
-        RFLU_TRY(launch_lange<T>(h, RFLU_NORM_ONE, n, n, F, ld, 0, &fnorm));
-        *rcond = (fnorm != fnorm) ? fnorm : 0.0;
-        return RFLU_OK;
-    }
-    *rcond = est == 0.0 ? 0.0 : 1.0 / (anorm * est);
-    return RFLU_OK;
+    return gecon_estimate<RealElem<T>>(h, n, F, ld, x, sgn, anorm, apply, rcond);
 }
 
-template <typename T>
-static int gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major,
-                         const double* anorm_dev, double* rcond_dev)
+// The same on M = U^-1 L^-1 of column-major complex factors.  ONE layout change per call: W = the row-major image of F in h->work.
+// Every M x is csolve_fwd_narrow on W, every M^H x the narrow path of cgetrs_trans_cm_dev (conj = 1) on F in place, both with
+// ipiv = NULL and one right-hand side, the n contiguous elements of x.  Neither narrow path states a size limit, so there is none here.
+template <typename R>
+int cgecon_dev(Handle* h, int norm, int64_t n, const R* F, int64_t lda, double anorm, double* rcond)
 {
-    if (!norm_ok("gecon_batched", norm)) return RFLU_ERR_ARG;
+    if (!norm_ok("complex ", "gecon", norm)) return RFLU_ERR_ARG;
+    if (n < 0 || lda < std::max<int64_t>(n, 1) || rcond == nullptr || (n > 0 && F == nullptr)) {
+        set_error("complex gecon: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    if (anorm < 0.0) { set_error("complex gecon: anorm = %g is negative", anorm); return RFLU_ERR_ARG; }
+    *rcond = 0.0;
+    if (n == 0) { *rcond = 1.0; return RFLU_OK; }
+    if (anorm != anorm) { *rcond = anorm; return RFLU_OK; }
+    if (anorm == 0.0) return RFLU_OK;
+    int64_t zero1 = 0;
+    RFLU_TRY(launch_clogabsdet<R>(h, n, F, lda + 1, nullptr, nullptr, nullptr, nullptr, &zero1));
+    if (zero1 != 0) return RFLU_OK;   // a u_ii with both parts zero: rcond = 0 before any solve is launched
+
+    const int64_t ldw = cworkspace_ld(n);
+    RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldw * 2 * sizeof(R)));
+    RFLU_TRY(ensure_buffer(&h->cond_work, &h->cond_work_bytes, (size_t)n * 2 * sizeof(R)));
+    R* W = static_cast<R*>(h->work);
+    R* x = static_cast<R*>(h->cond_work);
+    RFLU_TRY(launch_ctranspose<R>(h, n, n, F, lda, W, ldw));
+    // ||M||_inf = ||M^H||_1: for the Inf norm M and M^H swap roles
+    auto apply = [&](bool adjoint) -> int {
+        if (adjoint != (norm == RFLU_NORM_INF)) return cgetrs_trans_cm_dev<R>(h, n, 1, F, lda, nullptr, x, n, 1);
+        return csolve_fwd_narrow<R>(h, n, 1, W, ldw, nullptr, x, n);
+    };
+    return gecon_estimate<CplxElem<R>>(h, n, F, lda, x, nullptr, anorm, apply, rcond);
+}
+template int cgecon_dev<double>(Handle*, int, int64_t, const double*, int64_t, double, double*);
+template int cgecon_dev<float>(Handle*, int, int64_t, const float*, int64_t, double, double*);
+
+// One launch where the matrix fits a workgroup's LDS; above that a loop over the single-matrix estimate, which for complex elements is
+// column-major only.
+template <typename E>
+static int gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const typename E::real* F, int64_t lda, int64_t strideF,
+                         int row_major, const double* anorm_dev, double* rcond_dev)
+{
+    typedef typename E::real R;
+    constexpr bool CPLX = E::PARTS == 2;
+    if (!norm_ok(E::WHO, "gecon_batched", norm)) return RFLU_ERR_ARG;
     if (batch < 0 || n < 0) {
-        set_error("gecon_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
+        set_error("%sgecon_batched: negative size batch=%lld n=%lld", E::WHO, (long long)batch, (long long)n);
         return RFLU_ERR_ARG;
     }
     if (batch == 0) return RFLU_OK;
-    if (rcond_dev == nullptr || (n > 0 && (F == nullptr || anorm_dev == nullptr))) { set_error("gecon_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (rcond_dev == nullptr || (n > 0 && (F == nullptr || anorm_dev == nullptr))) { set_error("%sgecon_batched: null pointer", E::WHO); return RFLU_ERR_ARG; }
     if (n > 0 && (lda < n || (batch > 1 && strideF < (n - 1) * lda + n))) {
-        set_error("gecon_batched: lda=%lld strideF=%lld too small for n=%lld", (long long)lda, (long long)strideF, (long long)n);
+        set_error("%sgecon_batched: lda=%lld strideF=%lld too small for n=%lld", E::WHO, (long long)lda, (long long)strideF, (long long)n);
         return RFLU_ERR_ARG;
     }
     std::vector<double> host((size_t)batch, 1.0);
@@ -787,17 +854,20 @@ static int gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const T*
         RFLU_HIP(hipStreamSynchronize(h->stream));
         return RFLU_OK;
     }
-    if (batched_fits(n, n)) {
-        RFLU_TRY(launch_gecon_batched<T>(h, norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev));
+    if (CPLX ? cbatched_fits<R>(n, n) : batched_fits(n, n)) {
+        RFLU_TRY(CPLX ? launch_cgecon_batched<R>(h, norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev)
+                      : launch_gecon_batched<R>(h, norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev));
         RFLU_HIP(hipStreamSynchronize(h->stream));
         return RFLU_OK;
     }
+    if (CPLX && row_major) return refuse_large_row_major<R>("complex gecon_batched");
     RFLU_HIP(hipMemcpyAsync(host.data(), anorm_dev, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     for (int64_t b = 0; b < batch; ++b) {
         const double an = host[(size_t)b];
         if (an < 0.0) { host[(size_t)b] = std::nan(""); continue; }   // a member's bad anorm spoils its own output only
-        RFLU_TRY(gecon_dev<T>(h, norm, n, F + b * strideF, lda, row_major, an, &host[(size_t)b]));
+        const R* Fb = F + E::PARTS * b * strideF;
+        RFLU_TRY(CPLX ? cgecon_dev<R>(h, norm, n, Fb, lda, an, &host[(size_t)b]) : gecon_dev<R>(h, norm, n, Fb, lda, row_major, an, &host[(size_t)b]));
     }
     RFLU_HIP(hipMemcpyAsync(rcond_dev, host.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
     RFLU_HIP(hipStreamSynchronize(h->stream));
@@ -856,162 +926,6 @@ static int cgetri_batched(Handle* h, int64_t batch, int64_t n, const R* F, int64
         }
     }
     RFLU_HIP(hipMemcpyAsync(info_dev, infos.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
-
-// ---- complex operator norms and condition estimate (include/rflu.h: COMPLEX NORMS, CONDITION; kernels: complex_condest.hip and
-// cgecon_batched_kernel in batched_complex.hip).  Sizes and leading dimensions count complex elements.
-template <typename R>
-static int clange_dev(Handle* h, int norm, int64_t m, int64_t n, const R* A, int64_t lda, int row_major, double* out)
-{
-    if (!norm_ok("complex lange", norm)) return RFLU_ERR_ARG;
-    if (m < 0 || n < 0 || out == nullptr || lda < std::max<int64_t>(row_major ? n : m, 1) || (m > 0 && n > 0 && A == nullptr)) {
-        set_error("complex lange: bad arguments m=%lld n=%lld lda=%lld (or a null pointer)", (long long)m, (long long)n, (long long)lda);
-        return RFLU_ERR_ARG;
-    }
-    return launch_clange<R>(h, norm, m, n, A, lda, row_major, out);
-}
-
-template <typename R>
-static int clange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const R* A, int64_t lda, int64_t strideA, int row_major,
-                          double* out_dev)
-{
-    if (!norm_ok("complex lange_batched", norm)) return RFLU_ERR_ARG;
-    if (batch < 0 || m < 0 || n < 0) {
-        set_error("complex lange_batched: negative size batch=%lld m=%lld n=%lld", (long long)batch, (long long)m, (long long)n);
-        return RFLU_ERR_ARG;
-    }
-    if (batch == 0) return RFLU_OK;
-    if (out_dev == nullptr || (m > 0 && n > 0 && A == nullptr)) { set_error("complex lange_batched: null pointer"); return RFLU_ERR_ARG; }
-    if (m == 0 || n == 0) {
-        RFLU_HIP(hipMemsetAsync(out_dev, 0, (size_t)batch * sizeof(double), h->stream));
-        RFLU_HIP(hipStreamSynchronize(h->stream));
-        return RFLU_OK;
-    }
-    const int64_t len = row_major ? n : m, cnt = row_major ? m : n;
-    if (lda < len || (batch > 1 && strideA < (cnt - 1) * lda + len)) {
-        set_error("complex lange_batched: lda=%lld strideA=%lld too small for %lld x %lld (%s)", (long long)lda, (long long)strideA,
-                  (long long)m, (long long)n, row_major ? "row-major" : "column-major");
-        return RFLU_ERR_ARG;
-    }
-    RFLU_TRY(launch_clange_batched<R>(h, norm, batch, m, n, A, lda, strideA, row_major, out_dev));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
-
-// rcond = 1 / (anorm * est): Higham's estimator (LAPACK zlacn2 with the integer start and closing vectors stated in rflu.h) on
-// M = U^-1 L^-1 of column-major complex factors.  ONE layout change per call: W = the row-major image of F in h->work.  Every M x is
-// csolve_fwd_narrow on W, every M^H x the narrow path of cgetrs_trans_cm_dev (conj = 1) on F in place, both with ipiv = NULL and one
-// right-hand side, the n contiguous elements of x.  Neither narrow path states a size limit, so there is none here.
-template <typename R>
-int cgecon_dev(Handle* h, int norm, int64_t n, const R* F, int64_t lda, double anorm, double* rcond)
-{
-    if (!norm_ok("complex gecon", norm)) return RFLU_ERR_ARG;
-    if (n < 0 || lda < std::max<int64_t>(n, 1) || rcond == nullptr || (n > 0 && F == nullptr)) {
-        set_error("complex gecon: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
-        return RFLU_ERR_ARG;
-    }
-    if (anorm < 0.0) { set_error("complex gecon: anorm = %g is negative", anorm); return RFLU_ERR_ARG; }
-    *rcond = 0.0;
-    if (n == 0) { *rcond = 1.0; return RFLU_OK; }
-    if (anorm != anorm) { *rcond = anorm; return RFLU_OK; }
-    if (anorm == 0.0) return RFLU_OK;
-    int64_t zero1 = 0;
-    RFLU_TRY(launch_clogabsdet<R>(h, n, F, lda + 1, nullptr, nullptr, nullptr, nullptr, &zero1));
-    if (zero1 != 0) return RFLU_OK;   // a u_ii with both parts zero: rcond = 0 before any solve is launched
-
-    const int64_t ldw = cworkspace_ld(n);
-    RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldw * 2 * sizeof(R)));
-    RFLU_TRY(ensure_buffer(&h->cond_work, &h->cond_work_bytes, (size_t)n * 2 * sizeof(R)));
-    R* W = static_cast<R*>(h->work);
-    R* x = static_cast<R*>(h->cond_work);
-    RFLU_TRY(launch_ctranspose<R>(h, n, n, F, lda, W, ldw));
-    // ||M||_inf = ||M^H||_1: for the Inf norm M and M^H swap roles
-    auto apply = [&](bool adjoint) -> int {
-        if (adjoint != (norm == RFLU_NORM_INF)) return cgetrs_trans_cm_dev<R>(h, n, 1, F, lda, nullptr, x, n, 1);
-        return csolve_fwd_narrow<R>(h, n, 1, W, ldw, nullptr, x, n);
-    };
-    CondStats st;
-    double est = 0.0;
-    bool bad = false, closing = false;
-    int64_t j = 0;
-    for (int round = 0; round < 5; ++round) {
-        RFLU_TRY(launch_ccond_fill<R>(h, n, x, round == 0 ? COND_FILL_ONES : COND_FILL_UNIT, j));
-        RFLU_TRY(apply(false));
-        RFLU_TRY(launch_ccond_stats<R>(h, n, x, -1, 1, &st));   // x holds its phases afterwards
-        if (st.nonfinite) { bad = true; break; }
-        if (round == 0) {
-            est = st.sum / (double)n;
-            if (n == 1) break;
-        } else {
-            const double est_old = est;
-            est = st.sum;
-            if (est <= est_old) { closing = true; break; }
-        }
-        RFLU_TRY(apply(true));
-        RFLU_TRY(launch_ccond_stats<R>(h, n, x, j, 0, &st));
-        if (st.nonfinite) { bad = true; break; }
-        j = (int64_t)st.argmax;
-        if ((round > 0 && st.xj_abs == st.maxabs) || round == 4) { closing = true; break; }
-    }
-    if (closing) {
-        RFLU_TRY(launch_ccond_fill<R>(h, n, x, COND_FILL_ALT, 0));
-        RFLU_TRY(apply(false));
-        RFLU_TRY(launch_ccond_stats<R>(h, n, x, -1, 0, &st));
-        if (st.nonfinite) bad = true;
-        else {
-            const double alt = 2.0 * st.sum / (3.0 * (double)n * (double)(n - 1));
-            if (alt > est) est = alt;
-        }
-    }
-    if (bad) {   // overflow in the substitution gives 0; a NaN in the factors (a norm keeps it) gives NaN
-        double fnorm = 0.0;
-        RFLU_TRY(launch_clange<R>(h, RFLU_NORM_ONE, n, n, F, lda, 0, &fnorm));
-        *rcond = (fnorm != fnorm) ? fnorm : 0.0;
-        return RFLU_OK;
-    }
-    *rcond = est == 0.0 ? 0.0 : 1.0 / (anorm * est);
-    return RFLU_OK;
-}
-template int cgecon_dev<double>(Handle*, int, int64_t, const double*, int64_t, double, double*);
-template int cgecon_dev<float>(Handle*, int, int64_t, const float*, int64_t, double, double*);
-
-template <typename R>
-static int cgecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, int row_major,
-                          const double* anorm_dev, double* rcond_dev)
-{
-    if (!norm_ok("complex gecon_batched", norm)) return RFLU_ERR_ARG;
-    if (batch < 0 || n < 0) {
-        set_error("complex gecon_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
-        return RFLU_ERR_ARG;
-    }
-    if (batch == 0) return RFLU_OK;
-    if (rcond_dev == nullptr || (n > 0 && (F == nullptr || anorm_dev == nullptr))) { set_error("complex gecon_batched: null pointer"); return RFLU_ERR_ARG; }
-    if (n > 0 && (lda < n || (batch > 1 && strideF < (n - 1) * lda + n))) {
-        set_error("complex gecon_batched: lda=%lld strideF=%lld too small for n=%lld", (long long)lda, (long long)strideF, (long long)n);
-        return RFLU_ERR_ARG;
-    }
-    std::vector<double> host((size_t)batch, 1.0);
-    if (n == 0) {   // the empty matrix: rcond = 1
-        RFLU_HIP(hipMemcpyAsync(rcond_dev, host.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        RFLU_HIP(hipStreamSynchronize(h->stream));
-        return RFLU_OK;
-    }
-    if (cbatched_fits<R>(n, n)) {
-        RFLU_TRY(launch_cgecon_batched<R>(h, norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev));
-        RFLU_HIP(hipStreamSynchronize(h->stream));
-        return RFLU_OK;
-    }
-    if (row_major) return refuse_large_row_major<R>("complex gecon_batched");
-    RFLU_HIP(hipMemcpyAsync(host.data(), anorm_dev, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    for (int64_t b = 0; b < batch; ++b) {
-        const double an = host[(size_t)b];
-        if (an < 0.0) { host[(size_t)b] = std::nan(""); continue; }   // a member's bad anorm spoils its own output only
-        RFLU_TRY(cgecon_dev<R>(h, norm, n, F + 2 * b * strideF, lda, an, &host[(size_t)b]));
-    }
-    RFLU_HIP(hipMemcpyAsync(rcond_dev, host.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
@@ -1642,13 +1556,13 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
                                int row_major, double* out)                                                            \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return lange_dev<T>(H(handle), norm, m, n, A, lda, row_major, out);                                           \
+        return lange_dev<RealElem<T>>(H(handle), norm, m, n, A, lda, row_major, out);                                 \
     }                                                                                                                 \
     int rflu_lange_batched_##SFX##_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t m, int64_t n,           \
                                        const T* A, int64_t lda, int64_t strideA, int row_major, double* out_dev)      \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return lange_batched<T>(H(handle), norm, batch, m, n, A, lda, strideA, row_major, out_dev);                   \
+        return lange_batched<RealElem<T>>(H(handle), norm, batch, m, n, A, lda, strideA, row_major, out_dev);         \
     }                                                                                                                 \
     int rflu_gecon_##SFX##_dev(rflu_handle_t handle, int norm, int64_t n, const T* F, int64_t lda, double anorm,      \
                                double* rcond_out)                                                                     \
@@ -1673,7 +1587,8 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
                                        double* rcond_dev)                                                             \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return gecon_batched<T>(H(handle), norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev);         \
+        return gecon_batched<RealElem<T>>(H(handle), norm, batch, n, F, lda, strideF, row_major, anorm_dev,           \
+                                          rcond_dev);                                                                 \
     }                                                                                                                 \
     int rflu_fill_uniform_##SFX##_dev(rflu_handle_t handle, T* A, int64_t m, int64_t n, int64_t ld, int row_major,    \
                                       uint64_t seed, int64_t M_global, int64_t i0, int64_t j0, double diag_add)       \
@@ -1839,13 +1754,13 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
                                int row_major, double* out)                                                            \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return clange_dev<R>(H(handle), norm, m, n, A, lda, row_major, out);                                          \
+        return lange_dev<CplxElem<R>>(H(handle), norm, m, n, A, lda, row_major, out);                                 \
     }                                                                                                                 \
     int rflu_lange_batched_##SFX##_dev(rflu_handle_t handle, int norm, int64_t batch, int64_t m, int64_t n,           \
                                        const R* A, int64_t lda, int64_t strideA, int row_major, double* out_dev)      \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return clange_batched<R>(H(handle), norm, batch, m, n, A, lda, strideA, row_major, out_dev);                  \
+        return lange_batched<CplxElem<R>>(H(handle), norm, batch, m, n, A, lda, strideA, row_major, out_dev);         \
     }                                                                                                                 \
     int rflu_gecon_##SFX##_dev(rflu_handle_t handle, int norm, int64_t n, const R* F, int64_t lda, double anorm,      \
                                double* rcond_out)                                                                     \
@@ -1864,7 +1779,8 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
                                        double* rcond_dev)                                                             \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return cgecon_batched<R>(H(handle), norm, batch, n, F, lda, strideF, row_major, anorm_dev, rcond_dev);        \
+        return gecon_batched<CplxElem<R>>(H(handle), norm, batch, n, F, lda, strideF, row_major, anorm_dev,           \
+                                          rcond_dev);                                                                 \
     }
 DEFINE_COMPLEX(cf64, double)
 DEFINE_COMPLEX(cf32, float)

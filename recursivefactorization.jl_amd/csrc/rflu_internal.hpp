@@ -467,31 +467,54 @@ int launch_logabsdet_batched(Handle* h, int64_t batch, int64_t n, const T* F, in
 template <typename T>
 int getri_view(Handle* h, int64_t n, T* V, int64_t ld, const int64_t* ipiv, int64_t* info);
 
-// condest.hip: operator norms and the vector kernels of the condition estimate.  Every sum is Float64 in a fixed
-// order (no read-modify-write on shared words): results repeat bit for bit.
+// condest.hip (DESIGN.md sections 4.11, 4.12): operator norms and the vector kernels of the condition estimate, one source for the four
+// element types.  An ELEMENT is what a leading dimension counts: RealElem<R> is one R, CplxElem<R> one interleaved (re, im) pair of R, and
+// every array crosses as R* (R = double / float).  Every sum is Float64 in a fixed order (no read-modify-write on shared words): results
+// repeat bit for bit.
+template <typename R>
+struct RealElem {
+    typedef R real;
+    static constexpr int PARTS = 1;
+    static constexpr const char* WHO = "";   // in front of the entry's name in every message
+    static __device__ __forceinline__ double abs(const R* p) { return __builtin_fabs((double)p[0]); }
+};
+template <typename R>
+struct CplxElem {
+    typedef R real;
+    static constexpr int PARTS = 2;
+    static constexpr const char* WHO = "complex ";
+    // Float64 hypot, except that a NaN in EITHER part gives NaN: C's hypot(Inf, NaN) is Inf, so the parts are tested, not the modulus
+    static __device__ __forceinline__ double abs(const R* p)
+    {
+        const double x = (double)p[0], y = (double)p[1];
+        if (x != x || y != y) return __builtin_nan("");
+        return hypot(x, y);
+    }
+};
 // *out (host) = the 1- or Inf-norm of the m x n matrix A; element (i, j) at [i + j*lda] or (row_major) [i*lda + j].  Synchronises.
-template <typename T>
-int launch_lange(Handle* h, int norm, int64_t m, int64_t n, const T* A, int64_t lda, int row_major, double* out);
-// out_dev[b] (device) = the same for matrix b at A + b*strideA; one workgroup per matrix up to 128 x 128, the single kernels' strided
-// loop above; bit-identical to launch_lange on the same matrix.  Enqueued only.
-template <typename T>
-int launch_lange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const T* A, int64_t lda, int64_t strideA, int row_major,
-                         double* out_dev);
+template <typename E>
+int launch_lange(Handle* h, int norm, int64_t m, int64_t n, const typename E::real* A, int64_t lda, int row_major, double* out);
+// out_dev[b] (device) = the same for matrix b, strideA elements after the one before; one workgroup per matrix up to 128 x 128, the
+// single kernels matrix by matrix above; bit-identical to launch_lange on the same matrix.  Enqueued only.
+template <typename E>
+int launch_lange_batched(Handle* h, int norm, int64_t batch, int64_t m, int64_t n, const typename E::real* A, int64_t lda, int64_t strideA,
+                         int row_major, double* out_dev);
 // the estimator's vectors: x and sgn are n contiguous elements on the device
 struct CondStats {
     double sum;        // sum of |x_i|, chunks of 1024 by a fixed tree, chunk sums in index order
     double maxabs;     // max |x_i| ...
     double xj_abs;     // |x[jq]| (0 when jq < 0)
     long long argmax;  // ... and the FIRST index that attains it
-    int differs;       // number of i with sign(x_i) != sgn[i], sign(v) = v >= 0 ? +1 : -1
+    int differs;       // real: number of i with sign(x_i) != sgn[i], sign(v) = v >= 0 ? +1 : -1; complex: 0
     int nonfinite;     // a NaN or Inf among the x_i
 };
-enum { COND_FILL_ONES = 0, COND_FILL_UNIT = 1, COND_FILL_ALT = 2 };   // ones; e_j; x_i = (-1)^i (n - 1 + i)
-template <typename T>
-int launch_cond_fill(Handle* h, int64_t n, T* x, int mode, int64_t j);
-// the statistics of x (host, the stream is synchronised); write_sign: afterwards x and sgn hold sign(x)
-template <typename T>
-int launch_cond_stats(Handle* h, int64_t n, T* x, T* sgn, int64_t jq, int write_sign, CondStats* out);
+enum { COND_FILL_ONES = 0, COND_FILL_UNIT = 1, COND_FILL_ALT = 2 };   // ones; e_j; x_i = (-1)^i (n - 1 + i); imaginary parts zero
+template <typename E>
+int launch_cond_fill(Handle* h, int64_t n, typename E::real* x, int mode, int64_t j);
+// the statistics of x (host, the stream is synchronised).  `write`, real: afterwards x and sgn hold sign(x); complex: sgn is never read
+// (pass nullptr) and afterwards x holds the phases x_i / |x_i| (1 + 0i where both parts are zero)
+template <typename E>
+int launch_cond_stats(Handle* h, int64_t n, typename E::real* x, typename E::real* sgn, int64_t jq, int write, CondStats* out);
 // batched.hip: the whole estimator on a matrix held in LDS, one launch for n <= BATCHED_MAX_DIM
 template <typename T>
 int launch_gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major,

@@ -7,7 +7,7 @@ first_argmax and alternating it reuses.
     2 sum / (3 n (n - 1))), the pair of operators M and M^H, the phase vector v_i / |v_i| with |v_i| = hypot in Float64 and the two
     quotients rounded to the element type (1 + 0i for a zero), NO repeated-sign-vector test, the FIRST index of the largest modulus,
     every sum of moduli by cond_cases.kernel_sum;
-  * line_sum_along / line_sum_across / lange_restatement: the norm sums of csrc/complex_condest.hip in their order;
+  * line_sum_along / line_sum_across / lange_restatement: the norm sums of csrc/condest.hip in their order;
   * the random inputs: the three families of cond_cases with an independent imaginary part;
   * the exact inputs: the real exact factors of cond_cases embedded as complex, and axis_case -- dense small integer factors whose U has
     its columns multiplied by random powers of i, kept where every vector of the estimator's trace lies on the axes (one part of every
@@ -30,7 +30,7 @@ import scipy.linalg as sla
 import cond_cases as R
 from cond_cases import FAMILIES, MAX_ROUNDS, NORM_INF, NORM_ONE, alternating, first_argmax, kernel_sum
 
-LN_CHUNK, LN_THREADS, LN_GROUP = 1024, 256, 256      # csrc/complex_condest.hip (asserted against the source)
+LN_CHUNK, LN_THREADS, LN_GROUP = 1024, 256, 256      # csrc/condest.hip (asserted against the source)
 CGECON_SIZES = [1, 2, 3, 33, 255, 256, 257, 1025]   # single-matrix random sizes: around the 256-row block of the narrow solves, two chunks
 CBATCHED_SIZES = {np.complex128: [1, 2, 3, 7, 8, 31, 32, 33, 63, 64], np.complex64: [1, 2, 3, 7, 8, 31, 32, 33, 63, 64, 65, 100, 127, 128]}
 CBATCHED_LIMIT = {np.complex128: 64, np.complex64: 128}
@@ -218,9 +218,9 @@ def crcond_restatement(F, norm, anorm, dtype, solvers=None, fault=None, detail=F
     return out(float(np.float64(1.0) / (np.float64(anorm) * np.float64(est))), float(est), solves)
 
 
-# ---- the norm sums of complex_condest.hip ------------------------------------------------------------------------------------------
+# ---- the norm sums of condest.hip --------------------------------------------------------------------------------------------------
 def line_sum_along(mods):
-    """Sum of one line's moduli in clange_along_kernel's order."""
+    """Sum of one line's moduli in lange_along_kernel's order."""
     a = np.asarray(mods, dtype=np.float64)
     acc = None
     for c0 in range(0, a.size, LN_CHUNK):
@@ -242,7 +242,7 @@ def line_sum_along(mods):
 
 
 def line_sum_across(mods):
-    """Sum over the lines of one position's moduli in clange_across_kernel / clange_max_kernel's order."""
+    """Sum over the lines of one position's moduli in lange_across_kernel / lange_max_kernel's order."""
     a = np.asarray(mods, dtype=np.float64)
     acc = None
     for g0 in range(0, a.size, LN_GROUP):

@@ -21,12 +21,12 @@ RANDOM_SIZES = [1, 2, 3, 7, 8, 31, 32, 33, 63, 64, 65, 127, 128, 129, 257]
 
 
 def test_constants_match_the_sources():
-    src = open(os.path.join(CSRC, "complex_condest.hip")).read()
-    assert int(re.search(r"constexpr int CLN_CHUNK = (\d+);", src).group(1)) == C.LN_CHUNK
-    assert int(re.search(r"constexpr int CLN_THREADS = (\d+);", src).group(1)) == C.LN_THREADS
-    assert int(re.search(r"constexpr int CLN_GROUP = (\d+);", src).group(1)) == C.LN_GROUP
-    assert int(re.search(r"constexpr int CCS_CHUNK = (\d+);", src).group(1)) == R.CS_CHUNK
-    assert int(re.search(r"constexpr int CCS_THREADS = (\d+);", src).group(1)) == R.CS_THREADS
+    src = open(os.path.join(CSRC, "condest.hip")).read()   # one source for the real and the complex elements: the real constants
+    assert int(re.search(r"constexpr int LN_CHUNK = (\d+);", src).group(1)) == C.LN_CHUNK
+    assert int(re.search(r"constexpr int LN_THREADS = (\d+);", src).group(1)) == C.LN_THREADS
+    assert int(re.search(r"constexpr int LN_GROUP = (\d+);", src).group(1)) == C.LN_GROUP
+    assert int(re.search(r"constexpr int CS_CHUNK = (\d+);", src).group(1)) == R.CS_CHUNK
+    assert int(re.search(r"constexpr int CS_THREADS = (\d+);", src).group(1)) == R.CS_THREADS
     hdr = open(os.path.join(ROOT, "recursivefactorization.jl_amd", "csrc", "rflu_internal.hpp")).read()
     for dtype, name in ((np.complex128, "CF64"), (np.complex64, "CF32")):
         assert int(re.search(rf"constexpr int64_t CBATCHED_MAX_DIM_{name} = (\d+);", hdr).group(1)) == C.CBATCHED_LIMIT[dtype]

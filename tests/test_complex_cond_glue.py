@@ -55,8 +55,10 @@ def test_source_is_wired_and_documented():
     pkg = os.path.join(ROOT, "recursivefactorization.jl_amd")
     from recursivefactorization.jl_amd import build as B
 
-    assert "complex_condest.hip" in B.SOURCES and "complex_condest.hip" in B.EXTRA_DEPS
-    assert os.path.exists(os.path.join(pkg, "csrc", "complex_condest.hip"))
+    assert "condest.hip" in B.SOURCES and "complex_condest.hip" not in B.SOURCES + list(B.EXTRA_DEPS)   # one source, real and complex
+    assert not os.path.exists(os.path.join(pkg, "csrc", "complex_condest.hip"))
+    condest = open(os.path.join(pkg, "csrc", "condest.hip")).read()
+    assert "RFLU_CONDEST_FOR(CplxElem<double>)" in condest and "RFLU_CONDEST_FOR(CplxElem<float>)" in condest
     assert "cgecon_batched_kernel" in open(os.path.join(pkg, "csrc", "batched_complex.hip")).read()
     solve = open(os.path.join(pkg, "csrc", "complex_solve.hip")).read()
     assert "template int csolve_fwd_narrow<double>(" in solve

@@ -1,5 +1,5 @@
 """-m gpu: complex operator norms and the complex condition estimate (rflu_lange_c*, rflu_gecon_c*, rflu_gecon_batched_c*;
-csrc/complex_condest.hip, cgecon_batched_kernel of csrc/batched_complex.hip, cgecon_dev of csrc/driver.cpp) and the Python functions
+csrc/condest.hip, cgecon_batched_kernel of csrc/batched_complex.hip, cgecon_dev of csrc/driver.cpp) and the Python functions
 above them.  Outputs are written into NaN-filled words.
 
   * norms: matrices whose entries lie on the axes with small integer parts equal the integer reference by `==` (both norms, both
