@@ -547,7 +547,7 @@ int rflu_residual_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const d
                           int64_t ldx, const double* B_dev, int64_t ldb, double* R_dev, int64_t ldr);
 
 /* ---- COMPLEX MIXED PRECISION: ComplexF32 factors of a ComplexF64 matrix, ComplexF64 iterative refinement (LAPACK zcgesv's scheme;
- * csrc/complex_mixed.hip) ----
+ * csrc/mixed.hip) ----
  * A ComplexF64 factorization costs four times the real flops, so this is the element type where the Float32 rate matters most.  The
  * contracts are those of rflu_mixed_getrf_f64_dev / rflu_mixed_getrs_f64_dev / rflu_residual_f64_dev above, word for word, except:
  *   - storage and leading dimensions follow the other complex entries: double* / float* to interleaved (re, im) pairs, lda / ldf / ldb /

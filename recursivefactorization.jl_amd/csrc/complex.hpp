@@ -95,19 +95,7 @@ template <typename R>
 int csolve_fwd_image(Handle* h, int64_t n, int64_t nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* X, int64_t ldx);
 template <typename R>
 int cgetrs_fwd_rm_dev(Handle* h, int64_t n, int64_t nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* B, int64_t ldb);
-// complex_mixed.hip.  A, X, B, R column-major ComplexF64; F row-major ComplexF32; every ld in complex elements.
-// F <- ComplexF32(A) in row-major, *anorm_dev (device) <- ||A||_inf (row sums of moduli); partial sums in Handle::mixed_part
-int launch_cdemote_relayout(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, double* anorm_dev);
-// R <- B - A X for nrhs <= RESIDUAL_PASS; A is read once
-int launch_cresidual_few(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
-                         int64_t ldb, double* R, int64_t ldr);
-// out (+)= (TO) in on column-major n x nrhs blocks / out[r][c] (+)= (TO) in[c][r]
-template <typename TI, typename TO>
-int launch_cconvert(Handle* h, int64_t n, int64_t nrhs, const TI* in, int64_t ld_in, TO* out, int64_t ld_out, bool add);
-template <typename TI, typename TO>
-int launch_cconvert_transpose(Handle* h, int64_t rows_out, int64_t cols_out, const TI* in, int64_t ld_in, TO* out, int64_t ld_out, bool add);
-// norms[2k] = max_i |R[i, k]|, norms[2k + 1] = max_i |X[i, k]| (moduli, NaN-keeping)
-int launch_ccolnorms(Handle* h, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* X, int64_t ldx, double* norms);
+// (the kernels of the refinement, real and complex: mixed.hip, declared in rflu_internal.hpp)
 
 // complex_inverse.hip: inv!(F) in place on column-major factors (*info: the first u_ii with both parts zero, F is
 // then untouched), and logabsdet as (log|det|, det / |det|); dstride counts complex elements between diagonal entries

@@ -930,9 +930,12 @@ static int cgetri_batched(Handle* h, int64_t batch, int64_t n, const R* F, int64
     return RFLU_OK;
 }
 
-// ---- mixed precision: Float32 factors of a Float64 matrix, Float64 iterative refinement (LAPACK dsgesv's scheme; kernels: mixed.hip) ----
-// The Float32 factors stay in the row-major layout getrf_rm<float> leaves them in and every solve of the loop is getrs_rm<float> on
-// them: no n x n layout change after the first (getrs_cm_dev would pay one per solve).
+// ---- mixed precision: Float32 / ComplexF32 factors of a Float64 / ComplexF64 matrix, iterative refinement in the wide type (LAPACK
+// dsgesv's and zcgesv's scheme; kernels: mixed.hip; DESIGN.md sections 4.3, 4.10) ---------------------------------------------------------
+// One host path for both families, E = RealElem<double> / CplxElem<double>: leading dimensions count elements, a pointer steps by
+// E::PARTS words per element, norms are absolute values or moduli.  The narrow factors stay in the row-major layout their factorization
+// leaves them in and every solve of the loop works on them: no n x n layout change after the first.  What differs -- the factorization
+// and the narrow solve with the shape of its workspace -- is the entry's lambda.
 static int ensure_mixed_norms(Handle* h, int64_t count)
 {
     const size_t need = (size_t)std::max<int64_t>(count, 2) * sizeof(double);
@@ -947,214 +950,105 @@ static int ensure_mixed_norms(Handle* h, int64_t count)
     return RFLU_OK;
 }
 
-static int mixed_getrf(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, int64_t* ipiv, int pivot,
-                       int64_t blocksize, double* anorm_out, int64_t* info)
+// F <- narrow(A) with ||A||_inf on the way, then factor(info) on F: getrf_rm<float> or cgetrf_rm_dev<float>, which wait for the stream
+template <typename E, typename Factor>
+static int mixed_getrf(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, const int64_t* ipiv, int pivot,
+                       double* anorm_out, int64_t* info, Factor factor)
 {
     if (n < 0 || n > INT32_MAX || lda < std::max<int64_t>(n, 1) || ldf < std::max<int64_t>(n, 1)) {
-        set_error("mixed_getrf: bad arguments n=%lld lda=%lld ldf=%lld", (long long)n, (long long)lda, (long long)ldf);
+        set_error("%smixed_getrf: bad arguments n=%lld lda=%lld ldf=%lld", E::WHO, (long long)n, (long long)lda, (long long)ldf);
         return RFLU_ERR_ARG;
     }
-    if (anorm_out == nullptr || info == nullptr) { set_error("mixed_getrf: null anorm_out or info pointer"); return RFLU_ERR_ARG; }
-    if (n > 0 && (A == nullptr || F == nullptr)) { set_error("mixed_getrf: null matrix pointer"); return RFLU_ERR_ARG; }
-    if (pivot && ipiv == nullptr && n > 0) { set_error("mixed_getrf: pivot != 0 needs an ipiv buffer"); return RFLU_ERR_ARG; }
+    if (anorm_out == nullptr || info == nullptr) { set_error("%smixed_getrf: null anorm_out or info pointer", E::WHO); return RFLU_ERR_ARG; }
+    if (n > 0 && (A == nullptr || F == nullptr)) { set_error("%smixed_getrf: null matrix pointer", E::WHO); return RFLU_ERR_ARG; }
+    if (pivot && ipiv == nullptr && n > 0) { set_error("%smixed_getrf: pivot != 0 needs an ipiv buffer", E::WHO); return RFLU_ERR_ARG; }
     *anorm_out = 0.0;
     *info = 0;
     if (n == 0) return RFLU_OK;
     RFLU_TRY(ensure_mixed_norms(h, 2));
-    RFLU_TRY(launch_demote_relayout(h, n, A, lda, F, ldf, static_cast<double*>(h->mixed_norms)));
+    RFLU_TRY(launch_demote_relayout<E>(h, n, A, lda, F, ldf, static_cast<double*>(h->mixed_norms)));
     RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, h->mixed_norms, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    RFLU_TRY(getrf_rm<float>(h, n, n, F, ldf, ipiv, pivot, blocksize, info));   // waits for the stream: the norm has arrived
+    RFLU_TRY(factor(info));   // waits for the stream: the norm has arrived
     *anorm_out = static_cast<const double*>(h->mixed_norms_host)[0];
     return RFLU_OK;
 }
 
+// C <- C - A B on row-major operands of the family
+static int mixed_gemm(RealElem<double>, Handle* h, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb,
+                      double* C, int64_t ldc) { return gemm_public<double>(h, M, N, K, A, lda, B, ldb, C, ldc); }
+static int mixed_gemm(CplxElem<double>, Handle* h, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb,
+                      double* C, int64_t ldc) { return launch_cgemm<double>(h, M, N, K, A, lda, B, ldb, C, ldc); }
+
 // R <- B - A X.  Few right-hand sides: residual_few in passes of RESIDUAL_PASS (A streamed once per pass).  Many: read as row-major, a
 // column-major matrix is its transpose, so after R <- B the row-major GEMM C -= A B with C = R^T (nrhs x n), A = X^T, B = A^T is
-// R^T -= X^T A^T, in place on the column-major buffers.
+// R^T -= X^T A^T (plain transposes, nothing conjugated), in place on the column-major buffers.
+// The crossover is tune.mixed_gemv_max_rhs, chosen for real elements: a structural starting value for complex, not measured.
+template <typename E>
 static int mixed_residual(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
                           int64_t ldb, double* R, int64_t ldr)
 {
+    constexpr int P = E::PARTS;
     if (n <= 0 || nrhs <= 0) return RFLU_OK;
     if (nrhs <= h->tune.mixed_gemv_max_rhs) {
         for (int64_t k0 = 0; k0 < nrhs; k0 += RESIDUAL_PASS)
-            RFLU_TRY(launch_residual_few(h, n, std::min<int64_t>(RESIDUAL_PASS, nrhs - k0), A, lda, X + k0 * ldx, ldx, B + k0 * ldb, ldb,
-                                         R + k0 * ldr, ldr));
+            RFLU_TRY(launch_residual_few<E>(h, n, std::min<int64_t>(RESIDUAL_PASS, nrhs - k0), A, lda, X + P * k0 * ldx, ldx, B + P * k0 * ldb,
+                                            ldb, R + P * k0 * ldr, ldr));
         return RFLU_OK;
     }
-    RFLU_HIP(hipMemcpy2DAsync(R, (size_t)ldr * sizeof(double), B, (size_t)ldb * sizeof(double), (size_t)n * sizeof(double), (size_t)nrhs,
-                              hipMemcpyDeviceToDevice, h->stream));
-    return gemm_public<double>(h, nrhs, n, n, X, ldx, A, lda, R, ldr);
+    RFLU_HIP(hipMemcpy2DAsync(R, (size_t)ldr * P * sizeof(double), B, (size_t)ldb * P * sizeof(double), (size_t)n * P * sizeof(double),
+                              (size_t)nrhs, hipMemcpyDeviceToDevice, h->stream));
+    return mixed_gemm(E(), h, nrhs, n, n, X, ldx, A, lda, R, ldr);
 }
 
+template <typename E>
 static int residual_public(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
                            int64_t ldb, double* R, int64_t ldr)
 {
     const int64_t n1 = std::max<int64_t>(n, 1);
     if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldx < n1 || ldb < n1 || ldr < n1) {
-        set_error("residual: bad arguments n=%lld nrhs=%lld lda=%lld ldx=%lld ldb=%lld ldr=%lld", (long long)n, (long long)nrhs, (long long)lda,
-                  (long long)ldx, (long long)ldb, (long long)ldr);
-        return RFLU_ERR_ARG;
-    }
-    if (n == 0 || nrhs == 0) return RFLU_OK;
-    if (A == nullptr || X == nullptr || B == nullptr || R == nullptr) { set_error("residual: null pointer"); return RFLU_ERR_ARG; }
-    RFLU_TRY(mixed_residual(h, n, nrhs, A, lda, X, ldx, B, ldb, R, ldr));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
-
-// X <- A^-1 B: x_0 = F32^-1 demote(B); then r = B - A x in Float64, the norms, the decision (dsgesv's rule: converged when for every
-// column ||r_k||_inf <= ||x_k||_inf * anorm * eps * sqrt(n); written so that a NaN or Inf anywhere is NOT convergence), and while it is
-// not met x += F32^-1 demote(r).  One host read per step: the 2 nrhs norms.
-static int mixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const float* F, int64_t ldf, const int64_t* ipiv,
-                       double anorm, const double* B, int64_t ldb, double* X, int64_t ldx, int max_iter, int* iters)
-{
-    const int64_t n1 = std::max<int64_t>(n, 1);
-    if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldf < n1 || ldb < n1 || ldx < n1) {
-        set_error("mixed_getrs: bad arguments n=%lld nrhs=%lld lda=%lld ldf=%lld ldb=%lld ldx=%lld", (long long)n, (long long)nrhs,
-                  (long long)lda, (long long)ldf, (long long)ldb, (long long)ldx);
-        return RFLU_ERR_ARG;
-    }
-    if (iters == nullptr) { set_error("mixed_getrs: null iters pointer"); return RFLU_ERR_ARG; }
-    *iters = 0;
-    if (n == 0 || nrhs == 0) return RFLU_OK;
-    if (A == nullptr || F == nullptr || B == nullptr || X == nullptr) { set_error("mixed_getrs: null pointer"); return RFLU_ERR_ARG; }
-    if (max_iter <= 0) max_iter = 30;
-    const int64_t ldw = round_up(nrhs, 16);
-    RFLU_TRY(ensure_buffer(&h->mixed_rhs, &h->mixed_rhs_bytes, (size_t)n * (size_t)ldw * sizeof(float)));
-    RFLU_TRY(ensure_buffer(&h->mixed_r, &h->mixed_r_bytes, (size_t)n * (size_t)nrhs * sizeof(double)));
-    RFLU_TRY(ensure_mixed_norms(h, 2 * nrhs));
-    float* W = static_cast<float*>(h->mixed_rhs);
-    double* R = static_cast<double*>(h->mixed_r);
-    double* norms_dev = static_cast<double*>(h->mixed_norms);
-    const double* norms = static_cast<const double*>(h->mixed_norms_host);
-    const double scale = anorm * DBL_EPSILON * std::sqrt((double)n);
-
-    RFLU_TRY((launch_convert_transpose<double, float>(h, n, nrhs, B, ldb, W, ldw, false)));
-    RFLU_TRY(getrs_rm<float>(h, n, nrhs, F, ldf, ipiv, W, ldw));
-    RFLU_TRY((launch_convert_transpose<float, double>(h, nrhs, n, W, ldw, X, ldx, false)));
-    for (int step = 0;; ++step) {
-        RFLU_TRY(mixed_residual(h, n, nrhs, A, lda, X, ldx, B, ldb, R, n));
-        RFLU_TRY(launch_colnorms(h, n, nrhs, R, n, X, ldx, norms_dev));
-        RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, norms_dev, (size_t)(2 * nrhs) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        RFLU_HIP(hipStreamSynchronize(h->stream));
-        bool converged = true;
-        for (int64_t k = 0; k < nrhs && converged; ++k)
-            if (!(norms[2 * k] <= norms[2 * k + 1] * scale)) converged = false;
-        if (converged) { *iters = step; return RFLU_OK; }
-        if (step >= max_iter) { *iters = -(step + 1); return RFLU_OK; }
-        RFLU_TRY((launch_convert_transpose<double, float>(h, n, nrhs, R, n, W, ldw, false)));
-        RFLU_TRY(getrs_rm<float>(h, n, nrhs, F, ldf, ipiv, W, ldw));
-        RFLU_TRY((launch_convert_transpose<float, double>(h, nrhs, n, W, ldw, X, ldx, true)));
-    }
-}
-
-// ---- complex mixed precision: ComplexF32 factors of a ComplexF64 matrix, ComplexF64 refinement (LAPACK zcgesv's scheme; kernels:
-// complex_mixed.hip, the solve on the row-major factors: complex_solve.hip) -----------------------------------------
-// The loop, the rule and the buffers are those of mixed_getrf / mixed_getrs above; norms are moduli, leading dimensions count complex
-// elements.  Up to CNARROW right-hand sides the ComplexF32 right-hand sides stay column-major (the narrow solve works on columns: an
-// element-wise conversion, no transpose), more go through a row-major image.
-static int cmixed_getrf(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, int64_t* ipiv, int pivot,
-                        double* anorm_out, int64_t* info)
-{
-    if (n < 0 || n > INT32_MAX || lda < std::max<int64_t>(n, 1) || ldf < std::max<int64_t>(n, 1)) {
-        set_error("complex mixed_getrf: bad arguments n=%lld lda=%lld ldf=%lld", (long long)n, (long long)lda, (long long)ldf);
-        return RFLU_ERR_ARG;
-    }
-    if (anorm_out == nullptr || info == nullptr) { set_error("complex mixed_getrf: null anorm_out or info pointer"); return RFLU_ERR_ARG; }
-    if (n > 0 && (A == nullptr || F == nullptr)) { set_error("complex mixed_getrf: null matrix pointer"); return RFLU_ERR_ARG; }
-    if (pivot && ipiv == nullptr && n > 0) { set_error("complex mixed_getrf: pivot != 0 needs an ipiv buffer"); return RFLU_ERR_ARG; }
-    *anorm_out = 0.0;
-    *info = 0;
-    if (n == 0) return RFLU_OK;
-    RFLU_TRY(ensure_mixed_norms(h, 2));
-    RFLU_TRY(launch_cdemote_relayout(h, n, A, lda, F, ldf, static_cast<double*>(h->mixed_norms)));
-    RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, h->mixed_norms, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    RFLU_TRY(cgetrf_rm_dev<float>(h, n, F, ldf, ipiv, pivot, info));   // waits for the stream: the norm has arrived
-    *anorm_out = static_cast<const double*>(h->mixed_norms_host)[0];
-    return RFLU_OK;
-}
-
-// R <- B - A X.  Few right-hand sides: cresidual_few in passes of RESIDUAL_PASS.  Many: R <- B, then the row-major complex GEMM
-// C -= A B with C = R^T (nrhs x n), A = X^T, B = A^T (plain transposes, nothing conjugated), in place on the column-major buffers.
-// The crossover is tune.mixed_gemv_max_rhs, the real path's value: a structural starting value for complex, not measured.
-static int cmixed_residual(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
-                           int64_t ldb, double* R, int64_t ldr)
-{
-    if (n <= 0 || nrhs <= 0) return RFLU_OK;
-    if (nrhs <= h->tune.mixed_gemv_max_rhs) {
-        for (int64_t k0 = 0; k0 < nrhs; k0 += RESIDUAL_PASS)
-            RFLU_TRY(launch_cresidual_few(h, n, std::min<int64_t>(RESIDUAL_PASS, nrhs - k0), A, lda, X + 2 * k0 * ldx, ldx, B + 2 * k0 * ldb, ldb,
-                                          R + 2 * k0 * ldr, ldr));
-        return RFLU_OK;
-    }
-    RFLU_HIP(hipMemcpy2DAsync(R, (size_t)ldr * 2 * sizeof(double), B, (size_t)ldb * 2 * sizeof(double), (size_t)n * 2 * sizeof(double),
-                              (size_t)nrhs, hipMemcpyDeviceToDevice, h->stream));
-    return launch_cgemm<double>(h, nrhs, n, n, X, ldx, A, lda, R, ldr);
-}
-
-static int cresidual_public(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
-                            int64_t ldb, double* R, int64_t ldr)
-{
-    const int64_t n1 = std::max<int64_t>(n, 1);
-    if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldx < n1 || ldb < n1 || ldr < n1) {
-        set_error("complex residual: bad arguments n=%lld nrhs=%lld lda=%lld ldx=%lld ldb=%lld ldr=%lld", (long long)n, (long long)nrhs,
+        set_error("%sresidual: bad arguments n=%lld nrhs=%lld lda=%lld ldx=%lld ldb=%lld ldr=%lld", E::WHO, (long long)n, (long long)nrhs,
                   (long long)lda, (long long)ldx, (long long)ldb, (long long)ldr);
         return RFLU_ERR_ARG;
     }
     if (n == 0 || nrhs == 0) return RFLU_OK;
-    if (A == nullptr || X == nullptr || B == nullptr || R == nullptr) { set_error("complex residual: null pointer"); return RFLU_ERR_ARG; }
-    RFLU_TRY(cmixed_residual(h, n, nrhs, A, lda, X, ldx, B, ldb, R, ldr));
+    if (A == nullptr || X == nullptr || B == nullptr || R == nullptr) { set_error("%sresidual: null pointer", E::WHO); return RFLU_ERR_ARG; }
+    RFLU_TRY(mixed_residual<E>(h, n, nrhs, A, lda, X, ldx, B, ldb, R, ldr));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
 
-// W <- F32^-1 W on the ComplexF32 right-hand sides in the form the width chose (column-major, ld = ldw, or the row-major image)
-static int cmixed_solve_work(Handle* h, bool narrow, int64_t n, int64_t nrhs, const float* F, int64_t ldf, const int64_t* ipiv, float* W,
-                             int64_t ldw)
-{
-    return narrow ? csolve_fwd_narrow<float>(h, n, (int)nrhs, F, ldf, ipiv, W, ldw) : csolve_fwd_image<float>(h, n, nrhs, F, ldf, ipiv, W, ldw);
-}
-
-static int cmixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const float* F, int64_t ldf, const int64_t* ipiv,
-                        double anorm, const double* B, int64_t ldb, double* X, int64_t ldx, int max_iter, int* iters)
+// X <- A^-1 B: x_0 = F32^-1 narrow(B); then r = B - A x in the wide type, the norms, the decision (dsgesv's rule: converged when for
+// every column ||r_k||_inf <= ||x_k||_inf * anorm * eps * sqrt(n); written so that a NaN or Inf anywhere is NOT convergence), and while
+// it is not met x += F32^-1 narrow(r).  One host read per step: the 2 nrhs norms.  *iters: the steps taken, or -(steps + 1) when the
+// rule is still not met after max_iter of them.
+// correct(S, lds, add): X (+)= F32^-1 narrow(S) through the entry's workspace, the first w_bytes of Handle::mixed_rhs.
+template <typename E, typename Correct>
+static int mixed_refine(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const float* F, int64_t ldf, double anorm,
+                        const double* B, int64_t ldb, double* X, int64_t ldx, int max_iter, int* iters, size_t w_bytes, Correct correct)
 {
     const int64_t n1 = std::max<int64_t>(n, 1);
     if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldf < n1 || ldb < n1 || ldx < n1) {
-        set_error("complex mixed_getrs: bad arguments n=%lld nrhs=%lld lda=%lld ldf=%lld ldb=%lld ldx=%lld", (long long)n, (long long)nrhs,
+        set_error("%smixed_getrs: bad arguments n=%lld nrhs=%lld lda=%lld ldf=%lld ldb=%lld ldx=%lld", E::WHO, (long long)n, (long long)nrhs,
                   (long long)lda, (long long)ldf, (long long)ldb, (long long)ldx);
         return RFLU_ERR_ARG;
     }
-    if (iters == nullptr) { set_error("complex mixed_getrs: null iters pointer"); return RFLU_ERR_ARG; }
+    if (iters == nullptr) { set_error("%smixed_getrs: null iters pointer", E::WHO); return RFLU_ERR_ARG; }
     *iters = 0;
     if (n == 0 || nrhs == 0) return RFLU_OK;
-    if (A == nullptr || F == nullptr || B == nullptr || X == nullptr) { set_error("complex mixed_getrs: null pointer"); return RFLU_ERR_ARG; }
+    if (A == nullptr || F == nullptr || B == nullptr || X == nullptr) { set_error("%smixed_getrs: null pointer", E::WHO); return RFLU_ERR_ARG; }
     if (max_iter <= 0) max_iter = 30;
-    const bool narrow = nrhs <= CNARROW;
-    const int64_t ldw = narrow ? cworkspace_ld(n) : cworkspace_ld(nrhs);
-    RFLU_TRY(ensure_buffer(&h->mixed_rhs, &h->mixed_rhs_bytes, (size_t)(narrow ? nrhs : n) * (size_t)ldw * 2 * sizeof(float)));
-    RFLU_TRY(ensure_buffer(&h->mixed_r, &h->mixed_r_bytes, (size_t)n * (size_t)nrhs * 2 * sizeof(double)));
+    RFLU_TRY(ensure_buffer(&h->mixed_rhs, &h->mixed_rhs_bytes, w_bytes));
+    RFLU_TRY(ensure_buffer(&h->mixed_r, &h->mixed_r_bytes, (size_t)n * (size_t)nrhs * E::PARTS * sizeof(double)));
     RFLU_TRY(ensure_mixed_norms(h, 2 * nrhs));
-    float* W = static_cast<float*>(h->mixed_rhs);
     double* R = static_cast<double*>(h->mixed_r);
     double* norms_dev = static_cast<double*>(h->mixed_norms);
     const double* norms = static_cast<const double*>(h->mixed_norms_host);
     const double scale = anorm * DBL_EPSILON * std::sqrt((double)n);
-    // W <- demote(S), W <- F32^-1 W, X (+)= promote(W)
-    auto correct = [&](const double* S, int64_t lds, bool add) -> int {
-        if (narrow) {
-            RFLU_TRY((launch_cconvert<double, float>(h, n, nrhs, S, lds, W, ldw, false)));
-            RFLU_TRY(cmixed_solve_work(h, true, n, nrhs, F, ldf, ipiv, W, ldw));
-            return launch_cconvert<float, double>(h, n, nrhs, W, ldw, X, ldx, add);
-        }
-        RFLU_TRY((launch_cconvert_transpose<double, float>(h, n, nrhs, S, lds, W, ldw, false)));
-        RFLU_TRY(cmixed_solve_work(h, false, n, nrhs, F, ldf, ipiv, W, ldw));
-        return launch_cconvert_transpose<float, double>(h, nrhs, n, W, ldw, X, ldx, add);
-    };
 
     RFLU_TRY(correct(B, ldb, false));
     for (int step = 0;; ++step) {
-        RFLU_TRY(cmixed_residual(h, n, nrhs, A, lda, X, ldx, B, ldb, R, n));
-        RFLU_TRY(launch_ccolnorms(h, n, nrhs, R, n, X, ldx, norms_dev));
+        RFLU_TRY(mixed_residual<E>(h, n, nrhs, A, lda, X, ldx, B, ldb, R, n));
+        RFLU_TRY(launch_colnorms<E>(h, n, nrhs, R, n, X, ldx, norms_dev));
         RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, norms_dev, (size_t)(2 * nrhs) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         RFLU_HIP(hipStreamSynchronize(h->stream));
         bool converged = true;
@@ -1164,6 +1058,44 @@ static int cmixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int
         if (step >= max_iter) { *iters = -(step + 1); return RFLU_OK; }
         RFLU_TRY(correct(R, n, true));
     }
+}
+
+// Real: the Float32 right-hand sides are a row-major n x nrhs image (rows of round_up(nrhs, 16) floats), solved by getrs_rm<float>
+static int mixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const float* F, int64_t ldf, const int64_t* ipiv,
+                       double anorm, const double* B, int64_t ldb, double* X, int64_t ldx, int max_iter, int* iters)
+{
+    typedef RealElem<double> E;
+    const int64_t ldw = round_up(nrhs, 16);
+    auto correct = [&](const double* S, int64_t lds, bool add) -> int {
+        float* W = static_cast<float*>(h->mixed_rhs);
+        RFLU_TRY((launch_convert_transpose<E, double, float>(h, n, nrhs, S, lds, W, ldw, false)));
+        RFLU_TRY(getrs_rm<float>(h, n, nrhs, F, ldf, ipiv, W, ldw));
+        return launch_convert_transpose<E, float, double>(h, nrhs, n, W, ldw, X, ldx, add);
+    };
+    return mixed_refine<E>(h, n, nrhs, A, lda, F, ldf, anorm, B, ldb, X, ldx, max_iter, iters, (size_t)n * (size_t)ldw * sizeof(float), correct);
+}
+
+// Complex (the solve on the row-major factors: complex_solve.hip): up to CNARROW right-hand sides the ComplexF32 right-hand sides stay
+// column-major (the narrow solve works on columns: an element-wise conversion, no transpose), more go through a row-major image.
+static int cmixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const float* F, int64_t ldf, const int64_t* ipiv,
+                        double anorm, const double* B, int64_t ldb, double* X, int64_t ldx, int max_iter, int* iters)
+{
+    typedef CplxElem<double> E;
+    const bool narrow = nrhs <= CNARROW;
+    const int64_t ldw = narrow ? cworkspace_ld(n) : cworkspace_ld(nrhs);
+    auto correct = [&](const double* S, int64_t lds, bool add) -> int {
+        float* W = static_cast<float*>(h->mixed_rhs);
+        if (narrow) {
+            RFLU_TRY((launch_cconvert<double, float>(h, n, nrhs, S, lds, W, ldw, false)));
+            RFLU_TRY(csolve_fwd_narrow<float>(h, n, (int)nrhs, F, ldf, ipiv, W, ldw));
+            return launch_cconvert<float, double>(h, n, nrhs, W, ldw, X, ldx, add);
+        }
+        RFLU_TRY((launch_convert_transpose<E, double, float>(h, n, nrhs, S, lds, W, ldw, false)));
+        RFLU_TRY(csolve_fwd_image<float>(h, n, nrhs, F, ldf, ipiv, W, ldw));
+        return launch_convert_transpose<E, float, double>(h, nrhs, n, W, ldw, X, ldx, add);
+    };
+    return mixed_refine<E>(h, n, nrhs, A, lda, F, ldf, anorm, B, ldb, X, ldx, max_iter, iters,
+                           (size_t)(narrow ? nrhs : n) * (size_t)ldw * 2 * sizeof(float), correct);
 }
 
 // ---- what the other host sources call (driver.hpp) -------------------------------------------------------------------------------------
@@ -1604,7 +1536,10 @@ int rflu_mixed_getrf_f64_dev(rflu_handle_t handle, int64_t n, const double* A_de
                              int64_t* ipiv_dev, int pivot, int64_t blocksize, double* anorm_out, int64_t* info)
 {
     CHECK_HANDLE(handle);
-    return mixed_getrf(H(handle), n, A_dev, lda, F32_dev, ldf, ipiv_dev, pivot, blocksize, anorm_out, info);
+    Handle* h = H(handle);
+    return mixed_getrf<RealElem<double>>(h, n, A_dev, lda, F32_dev, ldf, ipiv_dev, pivot, anorm_out, info, [&](int64_t* inf) {
+        return getrf_rm<float>(h, n, n, F32_dev, ldf, ipiv_dev, pivot, blocksize, inf);
+    });
 }
 
 int rflu_mixed_getrs_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const float* F32_dev,
@@ -1619,7 +1554,7 @@ int rflu_residual_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const d
                           int64_t ldx, const double* B_dev, int64_t ldb, double* R_dev, int64_t ldr)
 {
     CHECK_HANDLE(handle);
-    return residual_public(H(handle), n, nrhs, A_dev, lda, X_dev, ldx, B_dev, ldb, R_dev, ldr);
+    return residual_public<RealElem<double>>(H(handle), n, nrhs, A_dev, lda, X_dev, ldx, B_dev, ldb, R_dev, ldr);
 }
 
 /* experiment hook (not in rflu.h): a stream restricted to an arbitrary CU mask (8 x 32 bits); the caller owns it */
@@ -1789,7 +1724,10 @@ int rflu_mixed_getrf_cf64_dev(rflu_handle_t handle, int64_t n, const double* A_d
                               int64_t* ipiv_dev, int pivot, double* anorm_out, int64_t* info)
 {
     CHECK_HANDLE(handle);
-    return cmixed_getrf(H(handle), n, A_dev, lda, F32_dev, ldf, ipiv_dev, pivot, anorm_out, info);
+    Handle* h = H(handle);
+    return mixed_getrf<CplxElem<double>>(h, n, A_dev, lda, F32_dev, ldf, ipiv_dev, pivot, anorm_out, info, [&](int64_t* inf) {
+        return cgetrf_rm_dev<float>(h, n, F32_dev, ldf, ipiv_dev, pivot, inf);
+    });
 }
 
 int rflu_mixed_getrs_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const float* F32_dev,
@@ -1804,7 +1742,7 @@ int rflu_residual_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const 
                            int64_t ldx, const double* B_dev, int64_t ldb, double* R_dev, int64_t ldr)
 {
     CHECK_HANDLE(handle);
-    return cresidual_public(H(handle), n, nrhs, A_dev, lda, X_dev, ldx, B_dev, ldb, R_dev, ldr);
+    return residual_public<CplxElem<double>>(H(handle), n, nrhs, A_dev, lda, X_dev, ldx, B_dev, ldb, R_dev, ldr);
 }
 
 int rflu_mixed_solve_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F32_dev, int64_t ldf,

@@ -189,7 +189,7 @@ struct Handle {
     size_t rhs_work_bytes = 0;
     void* hostB_dev = nullptr;   // device copy of host right-hand sides (getrs host entry)
     size_t hostB_bytes = 0;
-    // mixed-precision solve (mixed.hip, driver.cpp: mixed_getrf / mixed_getrs)
+    // mixed-precision solve (mixed.hip, driver.cpp: mixed_getrf / mixed_refine), real and complex
     void* mixed_rhs = nullptr;   // Float32 row-major right-hand sides / corrections
     size_t mixed_rhs_bytes = 0;
     void* mixed_r = nullptr;     // Float64 residual, column-major n x nrhs
@@ -477,6 +477,7 @@ struct RealElem {
     static constexpr int PARTS = 1;
     static constexpr const char* WHO = "";   // in front of the entry's name in every message
     static __device__ __forceinline__ double abs(const R* p) { return __builtin_fabs((double)p[0]); }
+    static __device__ __forceinline__ double modulus(const R* p) { return abs(p); }
 };
 template <typename R>
 struct CplxElem {
@@ -490,6 +491,8 @@ struct CplxElem {
         if (x != x || y != y) return __builtin_nan("");
         return hypot(x, y);
     }
+    // plain Float64 hypot, NOT abs: (Inf, NaN) gives Inf.  What the mixed-precision kernels (mixed.hip) take as the modulus
+    static __device__ __forceinline__ double modulus(const R* p) { return hypot((double)p[0], (double)p[1]); }
 };
 // *out (host) = the 1- or Inf-norm of the m x n matrix A; element (i, j) at [i + j*lda] or (row_major) [i*lda + j].  Synchronises.
 template <typename E>
@@ -520,17 +523,24 @@ template <typename T>
 int launch_gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major,
                          const double* anorm, double* rcond);
 
-// mixed.hip: the kernels of the mixed-precision solve.  A, X, B, R column-major Float64; F row-major Float32.
+// mixed.hip: the kernels of the mixed-precision solve, E = RealElem<double> or CplxElem<double>.  A, X, B, R column-major Float64 /
+// ComplexF64; F row-major Float32 / ComplexF32; every ld in elements.
 constexpr int RESIDUAL_PASS = 8;   // right-hand sides per launch of residual_few
-// F <- Float32(A) in row-major, *anorm_dev (device) <- ||A||_inf; partial sums in Handle::mixed_part
+// F <- narrow(A) in row-major, *anorm_dev (device) <- ||A||_inf (complex: row sums of moduli); partial sums in Handle::mixed_part
+template <typename E>
 int launch_demote_relayout(Handle* h, int64_t n, const double* A, int64_t lda, float* F, int64_t ldf, double* anorm_dev);
 // R <- B - A X for nrhs <= RESIDUAL_PASS; A is read once
+template <typename E>
 int launch_residual_few(Handle* h, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
                         int64_t ldb, double* R, int64_t ldr);
 // out[r][c] = (TO) in[c][r], or += with add: element type and layout of the right-hand sides in one pass
-template <typename TI, typename TO>
+template <typename E, typename TI, typename TO>
 int launch_convert_transpose(Handle* h, int64_t rows_out, int64_t cols_out, const TI* in, int64_t ld_in, TO* out, int64_t ld_out, bool add);
-// norms[2k] = ||r_k||_inf, norms[2k + 1] = ||x_k||_inf (a NaN anywhere in a column is kept)
+// complex only: out (+)= (TO) in on column-major n x nrhs blocks, the element type alone
+template <typename TI, typename TO>
+int launch_cconvert(Handle* h, int64_t n, int64_t nrhs, const TI* in, int64_t ld_in, TO* out, int64_t ld_out, bool add);
+// norms[2k] = ||r_k||_inf, norms[2k + 1] = ||x_k||_inf (complex: largest modulus; a NaN anywhere in a column is kept)
+template <typename E>
 int launch_colnorms(Handle* h, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* X, int64_t ldx, double* norms);
 
 }  // namespace rflu

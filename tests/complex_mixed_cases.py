@@ -1,7 +1,7 @@
 """Inputs, CPU references and bars of the complex mixed-precision tests (tests/test_complex_mixed_cases.py proves them on the CPU,
 tests/test_gpu_complex_mixed.py uses them on the GPU).  Pure numpy / scipy, no GPU.
 
-  * grid_input / cpu_refine: the refinement of csrc/driver.cpp (cmixed_getrs) restated with scipy's ComplexF32 lu_factor and residuals
+  * grid_input / cpu_refine: the refinement of csrc/driver.cpp (mixed_refine) restated with scipy's ComplexF32 lu_factor and residuals
     in np.clongdouble; the rule is ||r_k||_inf <= ||x_k||_inf ||A||_inf eps64 sqrt(n) per column, every norm in MODULI.
   * exact_solve_case: CONSTRUCTED row-major factors L\\U and interchanges with a Gaussian-integer solution: every partial sum of both
     substitutions is exact in Float32 in any order, so the forward solve must return X by ==.  See its docstring.
@@ -170,7 +170,7 @@ def exact_solve_case(n, nrhs):
 
 # ---- the demoted image, element by element (part A of tests/mixed_cases.py, complex) ---------------------------------------------------
 CDEMOTE_SIZES = [1, 2, 63, 64, 65, 129, 193]       # both sides of the 64 x 64 tile, several tiles in the diagonal order
-CDM_T = 64                                         # csrc/complex_mixed.hip
+CDM_T = 64                                         # csrc/mixed.hip
 CMUTATIONS = ["truncation", "half_away", "dropped_last_column"]
 
 

@@ -49,8 +49,9 @@ def test_library_exports_the_symbols_and_the_version():
 def test_sources_are_wired_and_use_no_atomics():
     csrc = os.path.join(ROOT, "recursivefactorization.jl_amd", "csrc")
     build = open(os.path.join(ROOT, "recursivefactorization.jl_amd", "build.py")).read()
-    assert '"complex_mixed.hip"' in build and '"complex_mixed.hip": [' in build        # SOURCES and EXTRA_DEPS
-    for name in ("complex_mixed.hip", "complex_solve.hip"):
+    # the kernels of the real and of the complex refinement are one source: in SOURCES, and in EXTRA_DEPS with the complex headers
+    assert '"mixed.hip", ' in build and '"mixed.hip": ["complex.hpp", "complex_dev.hpp"]' in build
+    for name in ("mixed.hip", "complex_solve.hip"):
         code = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, name)).read())
         assert "atomic" not in code, name                                                 # reproducible from run to run
     # cfma lives in the shared header, once

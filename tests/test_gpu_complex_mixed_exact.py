@@ -1,5 +1,5 @@
 """-m gpu: the complex mixed-precision solve (rflu_mixed_getrf_cf64_dev / rflu_mixed_getrs_cf64_dev / rflu_residual_cf64_dev;
-csrc/complex_mixed.hip and cmixed_getrf / cmixed_getrs of csrc/driver.cpp) held to EXACT references: the complex counterpart of
+csrc/mixed.hip and mixed_getrf / mixed_refine of csrc/driver.cpp) held to EXACT references: the complex counterpart of
 tests/test_gpu_mixed_exact.py, whose parts A, B and C it follows and whose helpers it uses.  Inputs: tests/complex_mixed_cases.py
 (cdemote_input, crefine_case) and tests/mixed_cases.py (residual_case), proved on the CPU by tests/test_complex_mixed_cases.py and
 tests/test_mixed_cases.py.  Every comparison is `==` except the norm of the random family, which keeps the (n + 2) eps bar of
@@ -19,7 +19,7 @@ GETRF, GETRS, RESIDUAL = "rflu_mixed_getrf_cf64_dev", "rflu_mixed_getrs_cf64_dev
 
 # ---- A. the demoted image ------------------------------------------------------------------------------------------------------------
 def cdemote_variant(a_address, f_address, ldf):
-    """launch_cdemote_relayout's choice (csrc/complex_mixed.hip): VIN = one 16-byte load per element of A, possible when A sits on a
+    """launch_demote_relayout<CplxElem<double>>'s choice (csrc/mixed.hip): VIN = one 16-byte load per element of A, possible when A sits on a
     16-byte boundary, whatever lda (an element is 16 bytes); VOUT = float4 stores of two adjacent elements of a row of F32, possible
     when F32 sits on a 16-byte boundary and ldf is even."""
     return a_address % 16 == 0, f_address % 16 == 0 and ldf % 2 == 0

@@ -1,5 +1,5 @@
 """-m gpu: the real mixed-precision solve (rflu_mixed_getrf_f64_dev / rflu_mixed_getrs_f64_dev / rflu_residual_f64_dev; csrc/mixed.hip and
-mixed_getrf / mixed_getrs of csrc/driver.cpp) held to EXACT references.  tests/test_gpu_mixed.py accepts any run that reaches dsgesv's
+mixed_getrf / mixed_refine of csrc/driver.cpp) held to EXACT references.  tests/test_gpu_mixed.py accepts any run that reaches dsgesv's
 rule within 10 steps, and refinement repairs what is wrong underneath it; here every comparison is `==`:
 
   A. the Float32 image that demote_relayout_kernel<VIN, VOUT> writes, element by element, through inputs whose factorization does no
