@@ -583,6 +583,60 @@ int rflu_residual_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const 
 int rflu_mixed_solve_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F32_dev, int64_t ldf,
                               const int64_t* ipiv_dev, float* B_dev, int64_t ldb);
 
+/* ---- REFINEMENT AND ERROR BOUNDS: LAPACK xGERFS with trans = 'N' (what gesvx runs behind getrf / getrs): iterative refinement of a
+ * computed solution in the WORKING precision, the componentwise backward error berr and the forward error bound ferr of every
+ * right-hand side.  Float64 / Float32.  Kernels: csrc/refine.hip; driver: gerfs_dev in csrc/driver.cpp; DESIGN.md section 4.13.
+ * rflu_gecon_* says how bad A can be for ANY right-hand side; berr and ferr say how good THIS X is for THIS B.
+ *
+ * rflu_gerfs_*: all matrices are column-major DEVICE memory.  A (n x n, lda) is the original matrix, F (ldf) and ipiv what
+ * rflu_getrf_*_dev left (ipiv == NULL: NotIPIV), B (n x nrhs, ldb) the right-hand sides: A, F and B are ONLY READ.  X (n x nrhs, ldx)
+ * holds a computed solution and is refined IN PLACE; X overlapping A, F or B is undefined.  ferr (may be NULL), berr (required) and
+ * steps (may be NULL) are HOST arrays of nrhs entries; *info: host, required.
+ *   - Per column k, with u the unit roundoff of the element type (2^-53 / 2^-24, LAPACK's eps):  r = b - A x,  w = |b| + |A| |x|,
+ *     berr = max_i |r_i| / w_i.  While berr > u and 2 berr <= lstres (which starts at 3) and fewer than max_iter steps were taken
+ *     (max_iter <= 0 means 5, LAPACK's ITMAX): solve A d = r with the factors, x += d, lstres = berr, recompute.  The last iterate
+ *     stays even when it is the worse one, as in LAPACK.  steps[k] = the corrections applied to column k; berr[k] belongs to the X
+ *     that is returned.
+ *   - ferr[k] is LAPACK's bound: with wt_i = |r_i| + (n + 1) u w_i, ferr[k] = est(||A^-1 diag(wt)||_inf) / max_i |x_i| (no division
+ *     when that maximum is 0).  est is the estimator of rflu_gecon_* on M = diag(wt) A^-T (||A^-1 diag(wt)||_inf = ||M||_1): M x is
+ *     the transposed solve (P^T L^-T U^-T, with ipiv) followed by x o= wt, M^T x is x o= wt followed by the forward solve.  At most 11
+ *     solves with one right-hand side per column, 2n^2 flops each: for many right-hand sides ferr is the expensive part.
+ *     ferr == NULL skips the estimator entirely; berr, X and steps then come out bit for bit as with it.
+ *   - FOUR DELIBERATE DIFFERENCES from LAPACK: (1) there are no safe1 / safe2 guards: a row with w_i == 0 (then r_i == 0 too)
+ *     contributes 0 to berr, where LAPACK gives 1.  (2) r and w are accumulated in FLOAT64 FOR BOTH ELEMENT TYPES, one fused
+ *     multiply-add per term, the columns of A in ascending order inside a column slice and the slices combined in slice order: a fixed
+ *     order, no read-modify-write on shared words, the split a function of n alone.  The results are bit-identical from run to run and
+ *     whatever the alignment of A and the values of lda / ldb / ldx.  The Float32 entry therefore refines with an extra-precise
+ *     residual (its correction is the Float32 rounding of that residual), and its bound stays valid.  (3) The estimator's all-ones
+ *     start vector and integer closing vector are those of rflu_gecon_* (see there).  (4) Up to 8 columns advance in lock step: one
+ *     pass over A and one solve on an n x 8 block per step; a column that has stopped is solved again but NOT updated.  A column's
+ *     results do not depend on its neighbours or on nrhs, bit for bit.
+ *   - One layout change per call: the row-major image of F is made once in the handle's workspace; every correction runs on it and
+ *     every transposed solve of the estimator on F in place.  No n x n copy per step or per right-hand side.  One host read of a few
+ *     scalars per step.  Work goes on the handle's stream and is complete on return.
+ *   - n == 0 or nrhs == 0: success, nothing launched, berr / ferr / steps of the nrhs columns are 0, *info = 0.  An exactly zero u_ii:
+ *     *info = i (1-based), found before any solve as in rflu_getri_*; X, berr, ferr and steps are then untouched.  Otherwise *info = 0.
+ *     A NaN in a column's r or w: berr[k] = NaN, no step for that column, ferr[k] = NaN; a NaN confined to one column of X or B touches
+ *     that column's outputs only.  A non-finite vector inside the estimator while berr is no NaN: ferr[k] = +Inf.  A column with b = 0
+ *     and x = 0: berr = ferr = 0.
+ *   - RFLU_ERR_ARG with a message: negative n or nrhs, a leading dimension below max(n, 1), berr == NULL, info == NULL, NULL data
+ *     pointers with n, nrhs > 0, n > 65536 when ferr is requested (the transposed chain's limit).
+ *   - The handle's workspaces are shared with the other entries and refilled by each of them: a solve, an inverse, a factorization, a
+ *     condition estimate or a mixed-precision solve after rflu_gerfs_* on the same handle is bit-identical to one on a fresh handle.
+ * rflu_berr_*: the first half alone -- the Oettli-Prager componentwise backward error max_i |b - A x|_i / (|b| + |A| |x|)_i of ANY X,
+ * by the same kernels and with the same rules (zero rows, NaN, empty problems, argument checks).  It needs no factors and writes
+ * nothing on the device that the caller sees. */
+int rflu_gerfs_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const double* F_dev,
+                       int64_t ldf, const int64_t* ipiv_dev, const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx,
+                       double* ferr, double* berr, int max_iter, int* steps, int64_t* info);
+int rflu_gerfs_f32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* A_dev, int64_t lda, const float* F_dev,
+                       int64_t ldf, const int64_t* ipiv_dev, const float* B_dev, int64_t ldb, float* X_dev, int64_t ldx,
+                       double* ferr, double* berr, int max_iter, int* steps, int64_t* info);
+int rflu_berr_f64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const double* A_dev, int64_t lda, const double* X_dev,
+                      int64_t ldx, const double* B_dev, int64_t ldb, double* berr);
+int rflu_berr_f32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* A_dev, int64_t lda, const float* X_dev,
+                      int64_t ldx, const float* B_dev, int64_t ldb, double* berr);
+
 /* ---- building blocks on the INTERNAL row-major layout: element (i,j) at R[i*ld + j] (device pointers).
  * These are the four kernels of the path plus the bookkeeping the multi-GPU block-column driver and the parity
  * tests need.  Pivot rows are GLOBAL 0-based row positions r0.. of the slab; ipiv entries are 1-based rows.

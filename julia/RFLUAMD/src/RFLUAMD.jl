@@ -1101,6 +1101,74 @@ function ldiv_mixed!(X::Ptr{Float64}, ldx::Integer, F::MixedLU, B::Ptr{Float64},
     return F.iters >= 0
 end
 
+# ---- iterative refinement with error bounds: LAPACK gerfs, trans = 'N' (rflu_gerfs_*_dev / rflu_berr_*_dev, include/rflu.h) ----
+# Device pointers, column-major, like the mixed-precision entries.  A is the ORIGINAL matrix, F / ipiv what getrf_dev! left (C_NULL =
+# NotIPIV); A, F and B are only read, X is refined in place.  Residuals are accumulated in Float64 for both element types.
+"raw entry: refine `X` in place; returns `(info, ferr, berr, steps)` (`ferr` is `nothing` when skipped; `info != 0`: a zero `u_ii`, nothing written)"
+function gerfs_dev!(X::Ptr{Float64}, ldx::Integer, A::Ptr{Float64}, n::Integer, nrhs::Integer, lda::Integer, F::Ptr{Float64}, ldf::Integer,
+                    ipiv::Ptr{Int64}, B::Ptr{Float64}, ldb::Integer; max_iter::Integer = 5, ferr::Bool = true)
+    fe, be, steps, info = zeros(Float64, max(nrhs, 1)), zeros(Float64, max(nrhs, 1)), zeros(Cint, max(nrhs, 1)), Ref{Int64}(0)
+    st = GC.@preserve fe be steps ccall((:rflu_gerfs_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cint}, Ref{Int64}),
+               handle(), n, nrhs, A, lda, F, ldf, ipiv, B, ldb, X, ldx, ferr ? pointer(fe, 1) : Ptr{Float64}(C_NULL), pointer(be, 1),
+               Cint(max_iter), pointer(steps, 1), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return BlasInt(info[]), (ferr ? fe[1:nrhs] : nothing), be[1:nrhs], Int.(steps[1:nrhs])
+end
+
+function gerfs_dev!(X::Ptr{Float32}, ldx::Integer, A::Ptr{Float32}, n::Integer, nrhs::Integer, lda::Integer, F::Ptr{Float32}, ldf::Integer,
+                    ipiv::Ptr{Int64}, B::Ptr{Float32}, ldb::Integer; max_iter::Integer = 5, ferr::Bool = true)
+    fe, be, steps, info = zeros(Float64, max(nrhs, 1)), zeros(Float64, max(nrhs, 1)), zeros(Cint, max(nrhs, 1)), Ref{Int64}(0)
+    st = GC.@preserve fe be steps ccall((:rflu_gerfs_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Ptr{Int64}, Ptr{Float32}, Int64, Ptr{Float32}, Int64,
+                Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cint}, Ref{Int64}),
+               handle(), n, nrhs, A, lda, F, ldf, ipiv, B, ldb, X, ldx, ferr ? pointer(fe, 1) : Ptr{Float64}(C_NULL), pointer(be, 1),
+               Cint(max_iter), pointer(steps, 1), info)
+    st == RFLU_OK || error("librflu: ", last_error())
+    return BlasInt(info[]), (ferr ? fe[1:nrhs] : nothing), be[1:nrhs], Int.(steps[1:nrhs])
+end
+
+"raw entry: the componentwise backward error `max_i |b - A x|_i / (|b| + |A| |x|)_i` of every column of any `X`; needs no factors"
+function berr_dev(A::Ptr{Float64}, n::Integer, nrhs::Integer, lda::Integer, X::Ptr{Float64}, ldx::Integer, B::Ptr{Float64}, ldb::Integer)
+    be = zeros(Float64, max(nrhs, 1))
+    st = GC.@preserve be ccall((:rflu_berr_f64_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}),
+               handle(), n, nrhs, A, lda, X, ldx, B, ldb, pointer(be, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return be[1:nrhs]
+end
+
+function berr_dev(A::Ptr{Float32}, n::Integer, nrhs::Integer, lda::Integer, X::Ptr{Float32}, ldx::Integer, B::Ptr{Float32}, ldb::Integer)
+    be = zeros(Float64, max(nrhs, 1))
+    st = GC.@preserve be ccall((:rflu_berr_f32_dev, librflu), Cint,
+               (Ptr{Cvoid}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Ptr{Float64}),
+               handle(), n, nrhs, A, lda, X, ldx, B, ldb, pointer(be, 1))
+    st == RFLU_OK || error("librflu: ", last_error())
+    return be[1:nrhs]
+end
+
+"""
+    refine!(F::LU, A, B, X, nrhs; factors, ipiv = C_NULL, lda, ldf, ldb, ldx, max_iter = 5, ferr = true) -> (ferr, berr, steps)
+
+LAPACK gerfs for the system `F` factored: refine the computed solution at the device pointer `X` (`n x nrhs`, column-major) of
+`A X = B` in place and return, per right-hand side, the forward error bound (`nothing` with `ferr = false`: the bound costs up to 11
+one-column solves per right-hand side), the componentwise backward error of the returned `X` and the corrections applied.  `F`
+supplies the size and `info`; the factors live in HBM at `factors` (column-major, as `getrf_dev!` left them) with their pivots at
+`ipiv` (`C_NULL` for NotIPIV).  `A` is the original matrix.  Leading dimensions default to `n`.  Throws `SingularException` for a
+zero `u_ii`; `X` is then untouched.  `F'`, complex element types, row-major storage and batches are not served.
+"""
+function refine!(F::LU{T}, A::Ptr{T}, B::Ptr{T}, X::Ptr{T}, nrhs::Integer; factors::Ptr{T}, ipiv::Ptr{Int64} = Ptr{Int64}(C_NULL),
+                 lda::Integer = size(F.factors, 1), ldf::Integer = size(F.factors, 1), ldb::Integer = size(F.factors, 1),
+                 ldx::Integer = size(F.factors, 1), max_iter::Integer = 5, ferr::Bool = true) where {T <: GPUEltype}
+    checknonsingular(F.info)
+    n = LinearAlgebra.checksquare(F.factors)
+    info, fe, be, steps = gerfs_dev!(X, max(ldx, 1), A, n, nrhs, max(lda, 1), factors, max(ldf, 1), ipiv, B, max(ldb, 1);
+                                     max_iter = max_iter, ferr = ferr)
+    checknonsingular(info)
+    return fe, be, steps
+end
+
 # ---- complex mixed precision: ComplexF32 factors of a ComplexF64 matrix + ComplexF64 refinement (rflu_mixed_*_cf64_dev) ----
 # The C entries take double* / float* to interleaved (re, im) pairs, which is the storage of Complex{T}: the pointers are reinterpreted.
 # Leading dimensions count complex elements.  There is no blocksize.

@@ -49,6 +49,9 @@ _TYPED = {
     "rflu_gecon_rm_{s}_dev": (c_int, [c_p, c_int, c_i64, c_p, c_i64, c_dbl, c_p]),
     "rflu_gecon_{s}": (c_int, [c_p, c_int, c_i64, c_p, c_i64, c_dbl, c_p]),
     "rflu_gecon_batched_{s}_dev": (c_int, [c_p, c_int, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_p]),
+    # iterative refinement with error bounds (xGERFS, trans = 'N') and the componentwise backward error alone
+    "rflu_gerfs_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_int, c_p, c_p]),
+    "rflu_berr_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p]),
     "rflu_panel_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_p]),
     "rflu_laswp_rm_{s}_dev": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64]),
     "rflu_trsm_rm_{s}_dev": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64]),

@@ -1098,8 +1098,163 @@ static int cmixed_getrs(Handle* h, int64_t n, int64_t nrhs, const double* A, int
                            (size_t)(narrow ? nrhs : n) * (size_t)ldw * 2 * sizeof(float), correct);
 }
 
+// ---- iterative refinement with error bounds: LAPACK xGERFS, trans = 'N' (refine.hip) -----------------------------
+// the argument rules the two entries share
+template <typename T>
+static int refine_args(const char* who, int64_t n, int64_t nrhs, const T* A, int64_t lda, const T* X, int64_t ldx, const T* B, int64_t ldb,
+                       const double* berr)
+{
+    const int64_t n1 = std::max<int64_t>(n, 1);
+    if (n < 0 || nrhs < 0 || n > INT32_MAX || nrhs > INT32_MAX || lda < n1 || ldx < n1 || ldb < n1) {
+        set_error("%s: bad arguments n=%lld nrhs=%lld lda=%lld ldx=%lld ldb=%lld", who, (long long)n, (long long)nrhs, (long long)lda,
+                  (long long)ldx, (long long)ldb);
+        return RFLU_ERR_ARG;
+    }
+    if (berr == nullptr) { set_error("%s: null berr pointer", who); return RFLU_ERR_ARG; }
+    if (n > 0 && nrhs > 0 && (A == nullptr || X == nullptr || B == nullptr)) { set_error("%s: null matrix pointer", who); return RFLU_ERR_ARG; }
+    return RFLU_OK;
+}
+
+// r, w (-> R, Wt), the solve's block (-> D, may be NULL) and {berr, max|x|} of p <= REFINE_PASS columns; one host read, 2 p values
+template <typename T>
+static int refine_measure(Handle* h, int64_t n, int64_t p, const T* A, int64_t lda, const T* X, int64_t ldx, const T* B, int64_t ldb,
+                          double* R, double* Wt, T* D)
+{
+    double* out_dev = static_cast<double*>(h->mixed_norms);
+    RFLU_TRY(launch_absresidual<T>(h, n, p, A, lda, X, ldx, B, ldb, R, Wt, D));
+    RFLU_TRY(launch_berr_reduce<T>(h, n, p, R, Wt, X, ldx, out_dev));
+    RFLU_HIP(hipMemcpyAsync(h->mixed_norms_host, out_dev, (size_t)(2 * p) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
+template <typename T>
+static int berr_dev(Handle* h, int64_t n, int64_t nrhs, const T* A, int64_t lda, const T* X, int64_t ldx, const T* B, int64_t ldb, double* berr)
+{
+    RFLU_TRY(refine_args<T>("berr", n, nrhs, A, lda, X, ldx, B, ldb, berr));
+    for (int64_t k = 0; k < nrhs; ++k) berr[k] = 0.0;
+    if (n == 0 || nrhs == 0) return RFLU_OK;
+    RFLU_TRY(ensure_buffer(&h->mixed_r, &h->mixed_r_bytes, 2 * (size_t)n * REFINE_PASS * sizeof(double)));
+    RFLU_TRY(ensure_mixed_norms(h, 2 * REFINE_PASS));
+    double* R = static_cast<double*>(h->mixed_r);
+    double* Wt = R + n * REFINE_PASS;
+    const double* got = static_cast<const double*>(h->mixed_norms_host);
+    for (int64_t k0 = 0; k0 < nrhs; k0 += REFINE_PASS) {
+        const int64_t p = std::min<int64_t>(REFINE_PASS, nrhs - k0);
+        RFLU_TRY(refine_measure<T>(h, n, p, A, lda, X + k0 * ldx, ldx, B + k0 * ldb, ldb, R, Wt, nullptr));
+        for (int64_t k = 0; k < p; ++k) berr[k0 + k] = got[2 * k];
+    }
+    return RFLU_OK;
+}
+
+// The loop of xGERFS on passes of REFINE_PASS columns in lock step.  ONE layout change per call: W = the row-major image of F in h->work;
+// every correction is getrs_rm(W, ipiv) on the n x REFINE_PASS row-major block the combine kernel wrote (always all REFINE_PASS columns, so
+// that a column meets the same solve kernel whatever nrhs is), every transposed solve of the forward error bound getrs_trans_view on F in
+// place.  Workspaces: mixed_part (the slices' shares), mixed_r (r and w), mixed_rhs (the block), cond_work (the estimator's x, sgn, wt).
+template <typename T>
+static int gerfs_dev(Handle* h, int64_t n, int64_t nrhs, const T* A, int64_t lda, const T* F, int64_t ldf, const int64_t* ipiv, const T* B,
+                     int64_t ldb, T* X, int64_t ldx, double* ferr, double* berr, int max_iter, int* steps, int64_t* info)
+{
+    RFLU_TRY(refine_args<T>("gerfs", n, nrhs, A, lda, X, ldx, B, ldb, berr));
+    if (ldf < std::max<int64_t>(n, 1)) { set_error("gerfs: ldf=%lld is below n=%lld", (long long)ldf, (long long)n); return RFLU_ERR_ARG; }
+    if (info == nullptr) { set_error("gerfs: null info pointer"); return RFLU_ERR_ARG; }
+    if (n > 0 && nrhs > 0 && F == nullptr) { set_error("gerfs: null factor pointer"); return RFLU_ERR_ARG; }
+    if (ferr != nullptr && n > (int64_t)NB * 256 * 4) {
+        set_error("gerfs: n = %lld exceeds the %d rows the cooperative transposed solve covers (ferr = NULL skips the bound)", (long long)n,
+                  NB * 256 * 4);
+        return RFLU_ERR_ARG;
+    }
+    *info = 0;
+    if (n == 0 || nrhs == 0) {
+        for (int64_t k = 0; k < nrhs; ++k) {
+            berr[k] = 0.0;
+            if (ferr) ferr[k] = 0.0;
+            if (steps) steps[k] = 0;
+        }
+        return RFLU_OK;
+    }
+    int64_t zero1 = 0;
+    RFLU_TRY(launch_logabsdet<T>(h, n, F, ldf + 1, nullptr, nullptr, nullptr, &zero1));
+    if (zero1 != 0) { *info = zero1; return RFLU_OK; }   // an exactly zero u_ii: before any solve, nothing written
+    if (max_iter <= 0) max_iter = 5;
+    const double u = sizeof(T) == 8 ? 0x1p-53 : 0x1p-24;
+
+    const int64_t ldw = workspace_ld(h, n);
+    RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldw * sizeof(T)));
+    RFLU_TRY(ensure_buffer(&h->mixed_r, &h->mixed_r_bytes, 2 * (size_t)n * REFINE_PASS * sizeof(double)));
+    RFLU_TRY(ensure_buffer(&h->mixed_rhs, &h->mixed_rhs_bytes, (size_t)n * REFINE_LDD * sizeof(T)));
+    RFLU_TRY(ensure_buffer(&h->cond_work, &h->cond_work_bytes, 3 * (size_t)n * sizeof(T)));
+    RFLU_TRY(ensure_mixed_norms(h, 2 * REFINE_PASS));
+    T* W = static_cast<T*>(h->work);
+    double* R = static_cast<double*>(h->mixed_r);
+    double* Wt = R + n * REFINE_PASS;
+    T* D = static_cast<T*>(h->mixed_rhs);
+    T* x = static_cast<T*>(h->cond_work);
+    T* sgn = x + n;
+    T* wt = sgn + n;
+    const double* got = static_cast<const double*>(h->mixed_norms_host);
+    RFLU_TRY(launch_transpose<T>(h, n, n, F, ldf, W, ldw));
+    // the block's padding columns REFINE_PASS .. REFINE_LDD - 1 are never read or written by the solve (nrhs = REFINE_PASS)
+
+    for (int64_t k0 = 0; k0 < nrhs; k0 += REFINE_PASS) {
+        const int64_t p = std::min<int64_t>(REFINE_PASS, nrhs - k0);
+        const T* Bp = B + k0 * ldb;
+        T* Xp = X + k0 * ldx;
+        double lstres[REFINE_PASS], be[REFINE_PASS], xmax[REFINE_PASS];
+        int taken[REFINE_PASS];
+        unsigned active = (1u << p) - 1u;
+        for (int k = 0; k < REFINE_PASS; ++k) { lstres[k] = 3.0; taken[k] = 0; be[k] = xmax[k] = 0.0; }
+        for (;;) {
+            RFLU_TRY(refine_measure<T>(h, n, p, A, lda, Xp, ldx, Bp, ldb, R, Wt, D));
+            for (int k = 0; k < p; ++k) {
+                be[k] = got[2 * k];
+                xmax[k] = got[2 * k + 1];
+                if (!((active >> k) & 1u)) continue;
+                // xGERFS's test; written so that a NaN stops the column
+                if (be[k] > u && 2.0 * be[k] <= lstres[k] && taken[k] < max_iter) lstres[k] = be[k];
+                else active &= ~(1u << k);
+            }
+            if (active == 0) break;
+            RFLU_TRY(getrs_rm<T>(h, n, REFINE_PASS, W, ldw, ipiv, D, REFINE_LDD));
+            RFLU_TRY(launch_refine_update<T>(h, n, p, active, D, Xp, ldx));
+            for (int k = 0; k < p; ++k)
+                if ((active >> k) & 1u) ++taken[k];
+        }
+        for (int k = 0; k < p; ++k) {
+            berr[k0 + k] = be[k];
+            if (steps) steps[k0 + k] = taken[k];
+        }
+        if (ferr == nullptr) continue;
+        // r and w of the pass's final X are still in R and Wt: the estimator's buffers are others
+        for (int k = 0; k < p; ++k) {
+            if (be[k] != be[k]) { ferr[k0 + k] = be[k]; continue; }
+            RFLU_TRY(launch_refine_weights<T>(h, n, R + (int64_t)k * n, Wt + (int64_t)k * n, wt));
+            RFLU_HIP(hipMemsetAsync(sgn, 0, (size_t)n * sizeof(T), h->stream));
+            // M = diag(wt) A^-T: ||A^-1 diag(wt)||_inf = ||M||_1
+            auto apply = [&](bool transposed) -> int {
+                if (transposed) {
+                    RFLU_TRY(launch_refine_scale<T>(h, n, wt, x));
+                    return getrs_rm<T>(h, n, 1, W, ldw, ipiv, x, 1);
+                }
+                RFLU_TRY(getrs_trans_view<T>(h, n, 1, F, ldf, ipiv, x, 1));
+                return launch_refine_scale<T>(h, n, wt, x);
+            };
+            double est = 0.0;
+            bool bad = false;
+            typedef RealElem<T> E;
+            RFLU_TRY(higham_estimate(
+                n, true, [&](int mode, int64_t j) { return launch_cond_fill<E>(h, n, x, mode, j); }, apply,
+                [&](int64_t jq, int write, CondStats* st) { return launch_cond_stats<E>(h, n, x, sgn, jq, write, st); }, &est, &bad));
+            if (bad) ferr[k0 + k] = HUGE_VAL;
+            else ferr[k0 + k] = xmax[k] != 0.0 ? est / xmax[k] : est;
+        }
+    }
+    RFLU_HIP(hipStreamSynchronize(h->stream));
+    return RFLU_OK;
+}
+
 // ---- what the other host sources call (driver.hpp) -------------------------------------------------------------------------------------
-#define RFLU_INSTANTIATE_DRIVER(T)                                                                                                    \
+#define RFLU_INSTANTIATE_DRIVER(T)                                                                                                   \
     template int trsm_rec<T>(Handle*, int64_t, int64_t, const T*, int64_t, T*, int64_t, const T*);                                    \
     template int trsm_public<T>(Handle*, int64_t, int64_t, const T*, int64_t, T*, int64_t);                                           \
     template int getrs_cm_dev<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t);                          \
@@ -1127,7 +1282,7 @@ static Handle* H(rflu_handle_t h) { return reinterpret_cast<Handle*>(h); }
 
 extern "C" {
 
-int rflu_version(void) { return 110; }
+int rflu_version(void) { return 111; }
 
 const char* rflu_last_error(void) { return g_err; }
 
@@ -1521,6 +1676,20 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
         CHECK_HANDLE(handle);                                                                                         \
         return gecon_batched<RealElem<T>>(H(handle), norm, batch, n, F, lda, strideF, row_major, anorm_dev,           \
                                           rcond_dev);                                                                 \
+    }                                                                                                                 \
+    int rflu_gerfs_##SFX##_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const T* A, int64_t lda, const T* F,    \
+                               int64_t ldf, const int64_t* ipiv, const T* B, int64_t ldb, T* X, int64_t ldx,          \
+                               double* ferr, double* berr, int max_iter, int* steps, int64_t* info)                   \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return gerfs_dev<T>(H(handle), n, nrhs, A, lda, F, ldf, ipiv, B, ldb, X, ldx, ferr, berr, max_iter, steps,    \
+                            info);                                                                                    \
+    }                                                                                                                 \
+    int rflu_berr_##SFX##_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const T* A, int64_t lda, const T* X,     \
+                              int64_t ldx, const T* B, int64_t ldb, double* berr)                                     \
+    {                                                                                                                 \
+        CHECK_HANDLE(handle);                                                                                         \
+        return berr_dev<T>(H(handle), n, nrhs, A, lda, X, ldx, B, ldb, berr);                                         \
     }                                                                                                                 \
     int rflu_fill_uniform_##SFX##_dev(rflu_handle_t handle, T* A, int64_t m, int64_t n, int64_t ld, int row_major,    \
                                       uint64_t seed, int64_t M_global, int64_t i0, int64_t j0, double diag_add)       \

@@ -543,4 +543,26 @@ int launch_cconvert(Handle* h, int64_t n, int64_t nrhs, const TI* in, int64_t ld
 template <typename E>
 int launch_colnorms(Handle* h, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* X, int64_t ldx, double* norms);
 
+// refine.hip: the kernels of rflu_gerfs_* / rflu_berr_*, T = double or float.  A, X, B column-major T; every
+// sum Float64 in a fixed order.  Enqueued only.
+constexpr int REFINE_PASS = 8;    // right-hand sides that advance in lock step: one pass over A, one solve on an n x REFINE_PASS block
+constexpr int REFINE_LDD = 16;    // leading dimension of that row-major block (rows of 16 elements, as the other right-hand-side images)
+// for nr <= REFINE_PASS columns: R[i + k n] = (b - A x)_i and Wt[i + k n] = (|b| + |A| |x|)_i in Float64 (both n x REFINE_PASS,
+// column-major) and, D != NULL, D[i * REFINE_LDD + k] = (T) R[i, k] for k < nr, 0 for nr <= k < REFINE_PASS.  A is read once; the partial
+// sums go through Handle::mixed_part
+template <typename T>
+int launch_absresidual(Handle* h, int64_t n, int64_t nr, const T* A, int64_t lda, const T* X, int64_t ldx, const T* B, int64_t ldb,
+                       double* R, double* Wt, T* D);
+// out[2k] = max_i |R[i, k]| / Wt[i, k] (a row with Wt == 0 gives 0; a NaN is kept), out[2k + 1] = max_i |X[i, k]|; one workgroup a column
+template <typename T>
+int launch_berr_reduce(Handle* h, int64_t n, int64_t nr, const double* R, const double* Wt, const T* X, int64_t ldx, double* out);
+// X[i, k] += D[i * REFINE_LDD + k] for the columns k < nr whose bit is set in mask
+template <typename T>
+int launch_refine_update(Handle* h, int64_t n, int64_t nr, unsigned mask, const T* D, T* X, int64_t ldx);
+// wt[i] = (T)(|r_i| + (n + 1) u w_i), u the unit roundoff of T; and x[i] *= wt[i] on n contiguous elements
+template <typename T>
+int launch_refine_weights(Handle* h, int64_t n, const double* r, const double* w, T* wt);
+template <typename T>
+int launch_refine_scale(Handle* h, int64_t n, const T* wt, T* x);
+
 }  // namespace rflu

@@ -26,6 +26,8 @@ Reference interface mirrored (citations into /root/reference/src/lu.jl):
     inv / inv!, det, logabsdet, logdet on the LU object (stdlib LinearAlgebra)            -> ``inv`` / ``inv_`` / ``det`` / ``logabsdet`` /
                                                                                              ``logdet``; batched: ``inv_batched`` /
                                                                                              ``logabsdet_batched`` / ``det_batched``
+    (no counterpart: LAPACK gerfs, the refinement and error bounds of gesvx)                -> ``refine_`` / ``solve_refined`` /
+                                                                                             ``backward_error`` / ``Refinement``
     Adjoint/Transpose wrappers                                                     :85-87   -> ``Adjoint`` / ``lu(A.T ...)``;
                                                                                              ``ldiv_(Adjoint(F), B)`` solves A' x = b
 
@@ -46,6 +48,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -757,6 +760,160 @@ def cond(A, p=1, *, handle=None) -> float:
     anorm = opnorm(A, p, handle=handle)
     rc = rcond(lu(A, check=False, handle=handle), anorm, p, handle=handle)
     return float("inf") if rc == 0.0 else 1.0 / rc
+
+
+# ---- iterative refinement with error bounds (LAPACK gerfs, what gesvx runs behind getrf / getrs) ---------------------------------------
+class Refinement(NamedTuple):
+    """What ``refine_`` found per right-hand side: ``ferr`` (forward error bound, ``None`` when skipped), ``berr`` (componentwise
+    backward error of the returned solution), ``steps`` (corrections applied); NumPy arrays of length nrhs."""
+
+    ferr: object
+    berr: object
+    steps: object
+
+
+def _refine_dtype(dtype, what: str) -> str:
+    if str(dtype).replace("torch.", "") in ("complex128", "complex64"):
+        raise TypeError(f"{what} serves Float64/Float32 only (got {dtype}); complex element types are not served: refine a complex "
+                        "solution with ldiv_complex_mixed, or check it on the CPU")
+    return _sfx(dtype)
+
+
+def _refine_factors(F, what: str):
+    """The refusals of ``refine_`` / ``solve_refined`` that concern the factorization -- before anything touches the library."""
+    if isinstance(F, Adjoint):
+        raise TypeError(f"{what} serves A x = b only (LAPACK trans = 'N'), not Adjoint(F): solve with ldiv_(Adjoint(F), B) and check "
+                        "the result with backward_error on the transposed matrix")
+    if isinstance(F, MixedLU):
+        raise TypeError(f"{what} needs factors in the working precision (lu / lu_); a MixedLU is refined by ldiv_mixed itself")
+    if isinstance(F, BatchedLU):
+        raise TypeError(f"{what} serves one factorization (lu / lu_), not a BatchedLU: refine the members one by one")
+    if not isinstance(F, LU):
+        raise TypeError(f"{what} needs the LU that lu / lu_ returned")
+    if F.factors is not None and hasattr(F.factors, "dtype"):
+        _refine_dtype(F.factors.dtype, what)
+    A, n, sfx, kind, ld = _square_factors(F, what)
+    if kind == "rm":
+        raise ValueError(f"{what} serves column-major factors only (lu_ on a column-major tensor); row-major factors: transpose the "
+                         "system into column-major storage first")
+    return A, n, sfx, kind, ld
+
+
+def _refine_operand(M, n: int, name: str, what: str, sfx: str, dev, matrix: bool = False):
+    """A column-major device view of an operand with n rows: (tensor, ncols, ld, was_numpy).  A vector counts as one column.
+    dev None: the checks alone, nothing is copied (every operand is checked before the first one travels)."""
+    import torch
+
+    if getattr(M, "ndim", None) not in ((2,) if matrix else (1, 2)) or int(M.shape[0]) != n or (matrix and int(M.shape[1]) != n):
+        raise ValueError(f"{what}: {name} must be {'n x n' if matrix else 'a vector of n entries or an n x nrhs matrix'}")
+    if _refine_dtype(M.dtype, what) != sfx:
+        raise TypeError(f"{what}: {name} must have the element type of the other operands")
+    cols = 1 if M.ndim == 1 else int(M.shape[1])
+    host = not _is_torch(M)
+    if host:
+        if not isinstance(M, np.ndarray):
+            raise TypeError(f"{what}: {name} must be a numpy.ndarray or a CUDA torch.Tensor")
+        if matrix and n > 1 and M.flags.c_contiguous and not M.flags.f_contiguous:
+            raise ValueError(f"{what}: a row-major {name} is not served; pass it column-major (np.asfortranarray)")
+        if dev is None:
+            return None, cols, max(n, 1), host
+        M = torch.from_numpy(np.ascontiguousarray(M.T)).to(dev).T if M.ndim == 2 else torch.from_numpy(np.ascontiguousarray(M)).to(dev)
+    elif not M.is_cuda:
+        raise _ffi.RfluError("torch input must live on the MI355X (device='cuda'); host data goes in as NumPy")
+    if M.ndim == 1:
+        if n > 1 and M.stride(0) != 1:
+            raise ValueError(f"{what}: a vector {name} must be contiguous (stride 1)")
+        return M, 1, max(n, 1), host
+    if n > 1 and not (M.stride(0) == 1 and (cols <= 1 or M.stride(1) >= n)):
+        raise ValueError(f"{what}: {name} must be column-major (unit row stride, column stride >= n); a row-major {name} is not served")
+    return M, cols, (max(int(M.stride(1)), n, 1) if cols > 1 else max(n, 1)), host
+
+
+def refine_(F, A, B, X, *, max_iter=5, ferr=True, handle=None) -> Refinement:
+    """Refine the computed solution ``X`` of ``A X = B`` IN PLACE in the working precision and say how good it is (LAPACK gerfs with
+    trans = 'N', ``rflu_gerfs_*_dev``): per right-hand side the componentwise backward error ``berr = max_i |b - A x|_i / (|b| + |A| |x|)_i``
+    of the returned ``X``, LAPACK's forward error bound ``ferr >= ||x - x_true||_inf / ||x||_inf`` (up to the estimator's slack) and
+    the corrections applied.  ``A`` is the ORIGINAL matrix (a copy taken before ``lu_``), ``F`` its column-major factors.  Residuals
+    are accumulated in Float64 for both element types.  ``ferr=False`` skips the bound, which costs up to 11 one-column solves per
+    right-hand side.  CUDA tensors must be column-major (a vector counts as one column); NumPy arrays are copied up and ``X`` is copied
+    back.  Raises ``SingularException`` for an exactly zero ``u_ii`` (``X`` is then untouched)."""
+    import torch
+
+    Ff, n, sfx, kind, ldf = _refine_factors(F, "refine!")
+    if F.info != 0:
+        raise SingularException(abs(F.info))
+    cols = [_refine_operand(M, n, name, "refine!", sfx, None, matrix=mat)[1] for M, name, mat in ((A, "A", True), (B, "B", False), (X, "X", False))]
+    if cols[1] != cols[2]:
+        raise ValueError("refine!: X and B must have the same number of columns")
+    dev = torch.device("cuda", handle.device if handle is not None else 0) if kind == "host" else Ff.device
+    Fd = _refine_operand(Ff, n, "the factors", "refine!", sfx, dev, matrix=True)[0] if kind == "host" else Ff
+    Ad, _, lda, _ = _refine_operand(A, n, "A", "refine!", sfx, dev, matrix=True)
+    Bd, nrhs, ldb, _ = _refine_operand(B, n, "B", "refine!", sfx, dev)
+    Xd, nx, ldx, x_host = _refine_operand(X, n, "X", "refine!", sfx, dev)
+    if nx != nrhs:
+        raise ValueError("refine!: X and B must have the same number of columns")
+    if kind == "host":
+        ldf = max(int(Fd.stride(1)), n, 1) if n > 1 else 1
+    if isinstance(F.ipiv, NotIPIV):
+        keep, ip = None, ctypes.c_void_p(0)
+    else:
+        keep = F.ipiv if _is_torch(F.ipiv) else torch.from_numpy(np.ascontiguousarray(F.ipiv, dtype=np.int64)).to(dev)
+        ip = ctypes.c_void_p(keep.data_ptr())
+    berr = np.zeros(nrhs, dtype=np.float64)
+    fe = np.zeros(nrhs, dtype=np.float64) if ferr else None
+    steps = np.zeros(nrhs, dtype=np.intc)
+    if n > 0 and nrhs > 0:
+        h = handle or _ffi.default_handle(Ad.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(Ad.device).cuda_stream)
+        info = ctypes.c_int64(0)
+        h.call(f"rflu_gerfs_{sfx}_dev", n, nrhs, ctypes.c_void_p(Ad.data_ptr()), lda, ctypes.c_void_p(Fd.data_ptr()), ldf, ip,
+               ctypes.c_void_p(Bd.data_ptr()), ldb, ctypes.c_void_p(Xd.data_ptr()), ldx,
+               ctypes.c_void_p(fe.ctypes.data if ferr else 0), ctypes.c_void_p(berr.ctypes.data), int(max_iter),
+               ctypes.c_void_p(steps.ctypes.data), ctypes.byref(info))
+        if info.value != 0:
+            raise SingularException(int(info.value))
+        if x_host:
+            X[...] = Xd.cpu().numpy()
+    del keep
+    return Refinement(fe, berr, steps.astype(np.int64))
+
+
+def solve_refined(F, A, B, **kw):
+    """``(X, Refinement)``: a copy of ``B``, ``ldiv_(F, X)``, then ``refine_(F, A, B, X, **kw)`` -- LAPACK gesvx without equilibration."""
+    _refine_factors(F, "solve_refined")
+    X = B.clone() if _is_torch(B) else np.array(B, order="F", copy=True)
+    ldiv_(F, X, handle=kw.get("handle"))
+    return X, refine_(F, A, B, X, **kw)
+
+
+def backward_error(A, X, B, *, handle=None):
+    """The componentwise (Oettli-Prager) backward error ``max_i |b - A x|_i / (|b| + |A| |x|)_i`` of every column of ANY ``X``
+    (``rflu_berr_*_dev``), as a NumPy array of length nrhs.  Float64 sums for both element types; a row whose terms are all zero
+    contributes 0; needs no factors.  Operands as ``refine_``: column-major CUDA tensors, or NumPy arrays (copied up)."""
+    import torch
+
+    if isinstance(A, Adjoint):
+        raise TypeError("backward_error serves A x = b only, not Adjoint(A): pass the transposed matrix in column-major storage")
+    if getattr(A, "ndim", None) != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("backward_error needs a square matrix")
+    sfx = _refine_dtype(A.dtype, "backward_error")
+    n = int(A.shape[0])
+    cols = [_refine_operand(M, n, name, "backward_error", sfx, None, matrix=mat)[1] for M, name, mat in ((A, "A", True), (X, "X", False), (B, "B", False))]
+    if cols[1] != cols[2]:
+        raise ValueError("backward_error: X and B must have the same number of columns")
+    dev = A.device if _is_torch(A) else torch.device("cuda", handle.device if handle is not None else 0)
+    Ad, _, lda, _ = _refine_operand(A, n, "A", "backward_error", sfx, dev, matrix=True)
+    Xd, nrhs, ldx, _ = _refine_operand(X, n, "X", "backward_error", sfx, dev)
+    Bd, nb, ldb, _ = _refine_operand(B, n, "B", "backward_error", sfx, dev)
+    if nb != nrhs:
+        raise ValueError("backward_error: X and B must have the same number of columns")
+    berr = np.zeros(nrhs, dtype=np.float64)
+    if n > 0 and nrhs > 0:
+        h = handle or _ffi.default_handle(Ad.device.index or 0)
+        h.set_stream(torch.cuda.current_stream(Ad.device).cuda_stream)
+        h.call(f"rflu_berr_{sfx}_dev", n, nrhs, ctypes.c_void_p(Ad.data_ptr()), lda, ctypes.c_void_p(Xd.data_ptr()), ldx,
+               ctypes.c_void_p(Bd.data_ptr()), ldb, ctypes.c_void_p(berr.ctypes.data))
+    return berr
 
 
 def _complex_trans(F, trans, what: str):
