@@ -358,7 +358,7 @@ int rflu_getrs_trans_cf64_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, con
                               double* B_dev, int64_t ldb, int conj);
 int rflu_getrs_trans_cf32_dev(rflu_handle_t handle, int64_t n, int64_t nrhs, const float* F_dev, int64_t lda, const int64_t* ipiv_dev,
                               float* B_dev, int64_t ldb, int conj);
-/* COMPLEX INVERSE, DETERMINANT: inv! / inv, det, logabsdet, logdet on a ComplexF64 / ComplexF32 LU (csrc/complex_inverse.hip, DESIGN.md
+/* COMPLEX INVERSE, DETERMINANT: inv! / inv, det, logabsdet, logdet on a ComplexF64 / ComplexF32 LU (csrc/inverse.hip, DESIGN.md
  * section 4.8).  Storage as in the other complex entries: double* / float* to interleaved (re, im) pairs; lda / ld / strideF count
  * COMPLEX elements; a pointer aligned to the real type is enough.  The contract is that of rflu_getri_* and rflu_logabsdet_* in the
  * INVERSE, DETERMINANT block above, word for word: ipiv NULL = NotIPIV; in-order launches on the handle's stream, no kernel waits for

@@ -616,7 +616,7 @@ function gecon_batched_dev!(rcond::Ptr{Float64}, F::Ptr{Float32}, batch::Integer
     return nothing
 end
 
-# ---- inv! / logabsdet from ComplexF64 / ComplexF32 factors (rflu_getri_c* / rflu_logabsdet_c*, csrc/complex_inverse.hip): the methods of
+# ---- inv! / logabsdet from ComplexF64 / ComplexF32 factors (rflu_getri_c* / rflu_logabsdet_c*, csrc/inverse.hip): the methods of
 # getri! / getri_dev! / logabsdet_dev / logabsdet_host / logabsdet_batched_dev! for the complex pointer and matrix types.  Column-major
 # only (there is no row-major complex entry); the sign is det / |det|, a ComplexF64 (batched: `sign` points at `batch` ComplexF64 values).
 function getri!(F::StridedMatrix{ComplexF64}, ipiv::Ptr{Int64})

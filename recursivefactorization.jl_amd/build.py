@@ -12,7 +12,7 @@ LIB = os.path.join(HERE, "librflu_exp.so" if os.environ.get("RFLU_EXPERIMENTS", 
 # RFLU_EXPERIMENTS=1 in the environment of the BUILD adds the kernels that were measured and lost (the sub-panel
 # leaf of round 4) -- objects and library of their own (build_exp/, librflu_exp.so) so that the default build never contains them
 EXPERIMENTS = os.environ.get("RFLU_EXPERIMENTS", "0") not in ("", "0")
-SOURCES = ["gemm.hip", "engine.hip", "panel.hip", "panel_f32.hip", "panel_local.hip", "panel_local_f32.hip", "panel_local_xcd.hip", "panel_local_xcd_f32.hip", "panel_single.hip", "panel_single_f32.hip", "trsm.hip", "trsv.hip", "laswp.hip", "butterfly.hip", "batched.hip", "mixed.hip", "inverse.hip", "condest.hip", "refine.hip", "complex_gemm.hip", "complex.hip", "complex_solve.hip", "complex_inverse.hip", "batched_complex.hip", "driver.cpp", "streams.cpp", "schedule.cpp", "mgpu.cpp", "host_entry.cpp"]
+SOURCES = ["gemm.hip", "engine.hip", "panel.hip", "panel_f32.hip", "panel_local.hip", "panel_local_f32.hip", "panel_local_xcd.hip", "panel_local_xcd_f32.hip", "panel_single.hip", "panel_single_f32.hip", "trsm.hip", "trsv.hip", "laswp.hip", "butterfly.hip", "batched.hip", "mixed.hip", "inverse.hip", "condest.hip", "refine.hip", "complex_gemm.hip", "complex.hip", "complex_solve.hip", "batched_complex.hip", "driver.cpp", "streams.cpp", "schedule.cpp", "mgpu.cpp", "host_entry.cpp"]
 if EXPERIMENTS:
     SOURCES += ["panel_blocked.hip", "panel_blocked_f32.hip"]
 HEADERS = ["rflu_internal.hpp", os.path.join("..", "..", "include", "rflu.h")]   # included by every source
@@ -22,7 +22,7 @@ EXTRA_DEPS = {"gemm.hip": ["gemm_tile.hpp"], "engine.hip": ["gemm_tile.hpp", "la
               "streams.cpp": ["schedule_plan.hpp", "driver.hpp"], "schedule.cpp": ["engine.hpp", "schedule_plan.hpp", "driver.hpp"], "mgpu.cpp": ["schedule_plan.hpp", "driver.hpp"],
               "host_entry.cpp": ["engine.hpp", "schedule_plan.hpp", "driver.hpp", "host_wayback.hpp", "complex.hpp"],
               "complex_gemm.hip": ["gemm_tile.hpp", "complex.hpp"], "complex.hip": ["complex.hpp", "complex_dev.hpp"], "complex_solve.hip": ["complex.hpp", "complex_dev.hpp"],
-              "complex_inverse.hip": ["complex.hpp", "complex_dev.hpp"], "mixed.hip": ["complex.hpp", "complex_dev.hpp"],
+              "inverse.hip": ["complex.hpp", "complex_dev.hpp"], "mixed.hip": ["complex.hpp", "complex_dev.hpp"],
               "batched.hip": ["batched_kernels.hpp"], "batched_complex.hip": ["complex.hpp", "complex_dev.hpp", "batched_kernels.hpp"],
               "laswp.hip": ["laswp_strip.hpp", "trsm_row.hpp"], "trsm.hip": ["trsm_row.hpp"], "trsv.hip": ["trsm_row.hpp"],
               "panel.hip": _PANEL_H, "panel_local.hip": _PANEL_H, "panel_single.hip": _PANEL_H, "panel_blocked.hip": _PANEL_H,

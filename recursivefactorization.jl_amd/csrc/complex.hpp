@@ -76,7 +76,7 @@ int ctri_upper_rec(Handle* h, int64_t n, int64_t nrhs, const R* T, int64_t ldt, 
 template <typename R>
 int cgetrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t lda, const int64_t* ipiv, R* B, int64_t ldb, int conj);
 
-// complex_solve.hip, for complex_inverse.hip: x = P^T z, the interchanges of rows [0, rows) undone last first; element (k, c) at
+// complex_solve.hip, for inverse.hip: x = P^T z, the interchanges of rows [0, rows) undone last first; element (k, c) at
 // A[2 * (k * rs + c * cs)]
 template <typename R>
 int launch_claswp_rev(Handle* h, R* A, int64_t rs, int64_t cs, int64_t rows, int64_t ncols, const int64_t* ipiv);
@@ -97,35 +97,6 @@ template <typename R>
 int cgetrs_fwd_rm_dev(Handle* h, int64_t n, int64_t nrhs, const R* W, int64_t ldw, const int64_t* ipiv, R* B, int64_t ldb);
 // (the kernels of the refinement, real and complex: mixed.hip, declared in rflu_internal.hpp)
 
-// complex_inverse.hip: inv!(F) in place on column-major factors (*info: the first u_ii with both parts zero, F is
-// then untouched), and logabsdet as (log|det|, det / |det|); dstride counts complex elements between diagonal entries
-inline int cgetri_check_args(int64_t n, const void* F, int64_t lda, const int64_t* info)
-{
-    if (n < 0 || lda < (n > 1 ? n : 1) || info == nullptr || (n > 0 && F == nullptr)) {
-        set_error("complex getri: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
-        return RFLU_ERR_ARG;
-    }
-    return RFLU_OK;
-}
-inline int clogabsdet_check_args(int64_t n, const void* F, int64_t ld, const double* logabs, const double* sign_re, const double* sign_im)
-{
-    if (n < 0 || ld < (n > 1 ? n : 1) || logabs == nullptr || sign_re == nullptr || sign_im == nullptr || (n > 0 && F == nullptr)) {
-        set_error("complex logabsdet: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
-        return RFLU_ERR_ARG;
-    }
-    return RFLU_OK;
-}
-template <typename R>
-int launch_clogabsdet(Handle* h, int64_t n, const R* F, int64_t dstride, const int64_t* ipiv, double* logabs, double* sign_re,
-                      double* sign_im, int64_t* zero1);
-template <typename R>
-int cgetri_cm_dev(Handle* h, int64_t n, R* F, int64_t lda, const int64_t* ipiv, int64_t* info);
-template <typename R>
-int clogabsdet_dev(Handle* h, int64_t n, const R* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign_re, double* sign_im);
-template <typename R>
-int clogabsdet_batched_dev(Handle* h, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, const int64_t* ipiv,
-                           int64_t stride_ipiv, double* logabs_dev, double* sign_dev);
-
 // the complex condition estimate (the norms and the vector kernels are condest.hip, declared in rflu_internal.hpp)
 // batched_complex.hip: the whole estimator on a matrix held in LDS, one launch for n <= CBATCHED_MAX_DIM_CF64 / _CF32
 template <typename R>
@@ -138,10 +109,6 @@ template <typename R>
 int cgecon_host(Handle* h, int norm, int64_t n, const R* F, int64_t lda, double anorm, double* rcond);
 
 // host_entry.cpp: caller-owned column-major host arrays; copied back only on success
-template <typename R>
-int cgetri_host(Handle* h, int64_t n, R* F, int64_t lda, const int64_t* ipiv, int64_t* info);
-template <typename R>
-int clogabsdet_host(Handle* h, int64_t n, const R* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign_re, double* sign_im);
 template <typename R>
 int cgetrf_host(Handle* h, int64_t m, int64_t n, R* A, int64_t lda, int64_t* ipiv, int pivot, int64_t* info);
 template <typename R>

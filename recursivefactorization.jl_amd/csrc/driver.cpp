@@ -521,62 +521,59 @@ static int cgetrs_batched(Handle* h, int64_t batch, int64_t n, int64_t nrhs, con
     return RFLU_OK;
 }
 
-// ---- inv / det / logabsdet from the factors (include/rflu.h; kernels and the two sweeps: inverse.hip) ----------
-template <typename T>
-static int logabsdet_dev(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign)
+// ---- inv / det / logabsdet from the factors, real and complex (include/rflu.h; kernels and the two sweeps: inverse.hip, DESIGN.md
+// sections 4.4, 4.8, 4.9).  E is the element trait of rflu_internal.hpp: sizes, leading dimensions and strides count elements, every
+// message starts with E::WHO.  The sign is one word for real elements and (re, im) for complex ones: sign_im belongs to the latter only.
+template <typename E>
+static int logabsdet_dev(Handle* h, int64_t n, const typename E::real* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign_re,
+                         double* sign_im)
 {
-    if (n < 0 || ld < std::max<int64_t>(n, 1) || logabs == nullptr || sign == nullptr || (n > 0 && F == nullptr)) {
-        set_error("logabsdet: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
-        return RFLU_ERR_ARG;
-    }
-    *logabs = 0.0;
-    *sign = 1.0;
+    RFLU_TRY(logabsdet_check_args<E>(n, F, ld, logabs, sign_re, sign_im));   // ... and the empty product in the outputs
     if (n == 0) return RFLU_OK;
-    return launch_logabsdet<T>(h, n, F, ld + 1, ipiv, logabs, sign, nullptr);
+    return launch_logabsdet<E>(h, n, F, ld + 1, ipiv, logabs, sign_re, sign_im, nullptr);
 }
 
-template <typename T>
-static int logabsdet_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, const int64_t* ipiv,
-                             int64_t stride_ipiv, double* logabs_dev, double* sign_dev)
+// sign_dev: E::PARTS words per matrix
+template <typename E>
+static int logabsdet_batched(Handle* h, int64_t batch, int64_t n, const typename E::real* F, int64_t lda, int64_t strideF,
+                             const int64_t* ipiv, int64_t stride_ipiv, double* logabs_dev, double* sign_dev)
 {
     if (batch < 0 || n < 0) {
-        set_error("logabsdet_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
+        set_error("%slogabsdet_batched: negative size batch=%lld n=%lld", E::WHO, (long long)batch, (long long)n);
         return RFLU_ERR_ARG;
     }
     if (batch == 0) return RFLU_OK;
-    if (logabs_dev == nullptr || sign_dev == nullptr || (n > 0 && F == nullptr)) { set_error("logabsdet_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (logabs_dev == nullptr || sign_dev == nullptr || (n > 0 && F == nullptr)) { set_error("%slogabsdet_batched: null pointer", E::WHO); return RFLU_ERR_ARG; }
     if (n > 0 && (lda < n || (batch > 1 && strideF < (n - 1) * lda + n))) {
-        set_error("logabsdet_batched: lda=%lld strideF=%lld too small for n=%lld", (long long)lda, (long long)strideF, (long long)n);
+        set_error("%slogabsdet_batched: lda=%lld strideF=%lld too small for n=%lld", E::WHO, (long long)lda, (long long)strideF, (long long)n);
         return RFLU_ERR_ARG;
     }
-    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("logabsdet_batched: stride_ipiv=%lld < n", (long long)stride_ipiv); return RFLU_ERR_ARG; }
-    if (n == 0) {   // the empty product: (0, 1) for every matrix
-        std::vector<double> z((size_t)batch, 0.0), o((size_t)batch, 1.0);
-        RFLU_HIP(hipMemcpyAsync(logabs_dev, z.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        RFLU_HIP(hipMemcpyAsync(sign_dev, o.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("%slogabsdet_batched: stride_ipiv=%lld < n", E::WHO, (long long)stride_ipiv); return RFLU_ERR_ARG; }
+    if (n == 0) {   // the empty product: (0, 1) or (0, 1 + 0i) for every matrix
+        std::vector<double> z((size_t)batch, 0.0), o(E::PARTS * (size_t)batch, 0.0);
+        for (int64_t b = 0; b < batch; ++b) o[E::PARTS * (size_t)b] = 1.0;
+        RFLU_HIP(hipMemcpyAsync(logabs_dev, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        RFLU_HIP(hipMemcpyAsync(sign_dev, o.data(), o.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         RFLU_HIP(hipStreamSynchronize(h->stream));
         return RFLU_OK;
     }
-    RFLU_TRY(launch_logabsdet_batched<T>(h, batch, n, F, lda + 1, strideF, ipiv, stride_ipiv, logabs_dev, sign_dev));
+    RFLU_TRY(launch_logabsdet_batched<E>(h, batch, n, F, lda + 1, strideF, ipiv, stride_ipiv, logabs_dev, sign_dev));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
 
 // column-major device entry: F read as a row-major array with ld = lda IS the transposed view, and A^-1 column-major IS A^-T row-major:
 // no layout change, whatever lda and the pointer's alignment (misaligned: the GEMM's element-wise loads, same arithmetic)
-template <typename T>
-int getri_cm_dev(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)
+template <typename E>
+int getri_cm_dev(Handle* h, int64_t n, typename E::real* F, int64_t lda, const int64_t* ipiv, int64_t* info)
 {
-    if (n < 0 || lda < std::max<int64_t>(n, 1) || info == nullptr || (n > 0 && F == nullptr)) {
-        set_error("getri: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
-        return RFLU_ERR_ARG;
-    }
+    RFLU_TRY(getri_check_args<E>(n, F, lda, info));
     *info = 0;
     if (n == 0) return RFLU_OK;
-    return getri_view<T>(h, n, F, lda, ipiv, info);
+    return getri_view<E>(h, n, F, lda, ipiv, info);
 }
 
-// row-major factors: one layout change into the handle's workspace, the sweeps there, one layout change back
+// row-major real factors: one layout change into the handle's workspace, the sweeps there, one layout change back
 template <typename T>
 static int getri_rm(Handle* h, int64_t n, T* R, int64_t ld, const int64_t* ipiv, int64_t* info)
 {
@@ -590,46 +587,70 @@ static int getri_rm(Handle* h, int64_t n, T* R, int64_t ld, const int64_t* ipiv,
     RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldv * sizeof(T)));
     T* V = static_cast<T*>(h->work);
     RFLU_TRY(launch_transpose<T>(h, n, n, R, ld, V, ldv));
-    RFLU_TRY(getri_view<T>(h, n, V, ldv, ipiv, info));
+    RFLU_TRY(getri_view<RealElem<T>>(h, n, V, ldv, ipiv, info));
     if (*info != 0) return RFLU_OK;
     RFLU_TRY(launch_transpose<T>(h, n, n, V, ldv, R, ld));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
 
-template <typename T>
-static int getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,
-                         int64_t stride_ipiv, T* Ainv, int64_t ldi, int64_t strideI, int64_t* info_dev)
+// the batched inverse (kernels: batched.hip / batched_complex.hip), out of place.  Complex elements take `trans`:
+// Ainv_b <- inv(op(A_b)), op = A / transpose(A) / A' by 0 / 1 / 2; real entries pass 0.  Above the one-launch limit a loop over the
+// single-matrix getri on a copy: real row-major batches through getri_rm, complex ones are column-major only and 'T' / 'C' take one
+// layout change of the result through the handle's workspace (conjugating for 'C') and a copy back -- correct, not fast.
+template <typename E>
+static int getri_batched(Handle* h, int64_t batch, int64_t n, const typename E::real* F, int64_t lda, int64_t strideF, int row_major,
+                         const int64_t* ipiv, int64_t stride_ipiv, typename E::real* Ainv, int64_t ldi, int64_t strideI, int trans,
+                         int64_t* info_dev)
 {
+    typedef typename E::real R;
+    constexpr bool CPLX = E::PARTS == 2;
+    constexpr size_t ES = E::PARTS * sizeof(R);   // bytes of an element
     if (batch < 0 || n < 0) {
-        set_error("getri_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
+        set_error("%sgetri_batched: negative size batch=%lld n=%lld", E::WHO, (long long)batch, (long long)n);
+        return RFLU_ERR_ARG;
+    }
+    if (CPLX && (trans < 0 || trans > 2)) {
+        set_error("%sgetri_batched: trans must be 0 (A), 1 (transpose) or 2 (adjoint), got %d", E::WHO, trans);
         return RFLU_ERR_ARG;
     }
     if (batch == 0 || n == 0) return RFLU_OK;
-    if (F == nullptr || Ainv == nullptr || info_dev == nullptr) { set_error("getri_batched: null pointer"); return RFLU_ERR_ARG; }
+    if (F == nullptr || Ainv == nullptr || info_dev == nullptr) { set_error("%sgetri_batched: null pointer", E::WHO); return RFLU_ERR_ARG; }
     if (lda < n || ldi < n || (batch > 1 && (strideF < (n - 1) * lda + n || strideI < (n - 1) * ldi + n))) {
-        set_error("getri_batched: lda=%lld strideF=%lld ldi=%lld strideI=%lld too small for n=%lld", (long long)lda, (long long)strideF,
-                  (long long)ldi, (long long)strideI, (long long)n);
+        set_error("%sgetri_batched: lda=%lld strideF=%lld ldi=%lld strideI=%lld too small for n=%lld", E::WHO, (long long)lda,
+                  (long long)strideF, (long long)ldi, (long long)strideI, (long long)n);
         return RFLU_ERR_ARG;
     }
-    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("getri_batched: stride_ipiv=%lld < n", (long long)stride_ipiv); return RFLU_ERR_ARG; }
-    if (batched_fits(n, n)) {
-        RFLU_TRY(launch_getri_batched<T>(h, batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi, strideI, info_dev));
+    if (ipiv && batch > 1 && stride_ipiv < n) { set_error("%sgetri_batched: stride_ipiv=%lld < n", E::WHO, (long long)stride_ipiv); return RFLU_ERR_ARG; }
+    if (CPLX ? cbatched_fits<R>(n, n) : batched_fits(n, n)) {
+        if constexpr (CPLX) RFLU_TRY(launch_cgetri_batched<R>(h, batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi, strideI, trans, info_dev));
+        else RFLU_TRY(launch_getri_batched<R>(h, batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi, strideI, info_dev));
         RFLU_HIP(hipStreamSynchronize(h->stream));
         h->last_path = RFLU_PATH_HIP_BATCHED;
         return RFLU_OK;
     }
+    if (CPLX && row_major) return refuse_large_row_major<R>("complex getri_batched");
     std::vector<int64_t> infos((size_t)batch, 0);
     for (int64_t b = 0; b < batch; ++b) {
-        const T* Fb = F + b * strideF;
         const int64_t* ip = ipiv ? ipiv + b * stride_ipiv : nullptr;
-        T* Xb = Ainv + b * strideI;
-        RFLU_HIP(hipMemcpy2DAsync(Xb, (size_t)ldi * sizeof(T), Fb, (size_t)lda * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
+        R* Xb = Ainv + E::PARTS * b * strideI;
+        RFLU_HIP(hipMemcpy2DAsync(Xb, (size_t)ldi * ES, F + E::PARTS * b * strideF, (size_t)lda * ES, (size_t)n * ES, (size_t)n,
                                   hipMemcpyDeviceToDevice, h->stream));
-        if (row_major) RFLU_TRY(getri_rm<T>(h, n, Xb, ldi, ip, &infos[(size_t)b]));
-        else RFLU_TRY(getri_cm_dev<T>(h, n, Xb, ldi, ip, &infos[(size_t)b]));
-        if (infos[(size_t)b] != 0)   // a singular matrix: its output is NaN, as the one-launch path's division by zero leaves it non-finite
-            RFLU_HIP(hipMemset2DAsync(Xb, (size_t)ldi * sizeof(T), 0xff, (size_t)n * sizeof(T), (size_t)n, h->stream));
+        int rc;
+        if constexpr (CPLX) rc = getri_cm_dev<E>(h, n, Xb, ldi, ip, &infos[(size_t)b]);   // (row-major batches were refused above)
+        else rc = row_major ? getri_rm<R>(h, n, Xb, ldi, ip, &infos[(size_t)b]) : getri_cm_dev<E>(h, n, Xb, ldi, ip, &infos[(size_t)b]);
+        RFLU_TRY(rc);
+        if (infos[(size_t)b] != 0) {   // a singular matrix: its output is NaN, as the one-launch path's division by zero leaves it non-finite
+            RFLU_HIP(hipMemset2DAsync(Xb, (size_t)ldi * ES, 0xff, (size_t)n * ES, (size_t)n, h->stream));
+        } else if constexpr (CPLX) {
+            if (trans) {
+                const int64_t ldw = cworkspace_ld(n);
+                RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldw * ES));
+                R* W = static_cast<R*>(h->work);
+                RFLU_TRY(launch_ctranspose<R>(h, n, n, Xb, ldi, W, ldw, trans == 2));
+                RFLU_HIP(hipMemcpy2DAsync(Xb, (size_t)ldi * ES, W, (size_t)ldw * ES, (size_t)n * ES, (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+            }
+        }
     }
     RFLU_HIP(hipMemcpyAsync(info_dev, infos.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     RFLU_HIP(hipStreamSynchronize(h->stream));
@@ -771,7 +792,7 @@ int gecon_dev(Handle* h, int norm, int64_t n, const T* F, int64_t ld, int row_ma
     if (anorm != anorm) { *rcond = anorm; return RFLU_OK; }
     if (anorm == 0.0) return RFLU_OK;
     int64_t zero1 = 0;
-    RFLU_TRY(launch_logabsdet<T>(h, n, F, ld + 1, nullptr, nullptr, nullptr, &zero1));
+    RFLU_TRY(launch_logabsdet<RealElem<T>>(h, n, F, ld + 1, nullptr, nullptr, nullptr, nullptr, &zero1));
     if (zero1 != 0) return RFLU_OK;   // an exactly zero u_ii: rcond = 0 before any solve is launched
 
     const int64_t ldw = workspace_ld(h, n);
@@ -810,7 +831,7 @@ int cgecon_dev(Handle* h, int norm, int64_t n, const R* F, int64_t lda, double a
     if (anorm != anorm) { *rcond = anorm; return RFLU_OK; }
     if (anorm == 0.0) return RFLU_OK;
     int64_t zero1 = 0;
-    RFLU_TRY(launch_clogabsdet<R>(h, n, F, lda + 1, nullptr, nullptr, nullptr, nullptr, &zero1));
+    RFLU_TRY(launch_logabsdet<CplxElem<R>>(h, n, F, lda + 1, nullptr, nullptr, nullptr, nullptr, &zero1));
     if (zero1 != 0) return RFLU_OK;   // a u_ii with both parts zero: rcond = 0 before any solve is launched
 
     const int64_t ldw = cworkspace_ld(n);
@@ -870,62 +891,6 @@ static int gecon_batched(Handle* h, int norm, int64_t batch, int64_t n, const ty
         RFLU_TRY(CPLX ? cgecon_dev<R>(h, norm, n, Fb, lda, an, &host[(size_t)b]) : gecon_dev<R>(h, norm, n, Fb, lda, row_major, an, &host[(size_t)b]));
     }
     RFLU_HIP(hipMemcpyAsync(rcond_dev, host.data(), (size_t)batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
-
-// the complex batched inverse (kernel: batched_complex.hip): Ainv_b <- inv(op(A_b)), op by trans = 0 / 1 / 2.
-// Above the one-launch limit, column-major only: the real loop's steps on the single-matrix complex getri, then for 'T' / 'C' one layout
-// change of the result through the handle's workspace (conjugating for 'C') and a copy back -- correct, not fast.
-template <typename R>
-static int cgetri_batched(Handle* h, int64_t batch, int64_t n, const R* F, int64_t lda, int64_t strideF, int row_major, const int64_t* ipiv,
-                          int64_t stride_ipiv, R* Ainv, int64_t ldi, int64_t strideI, int trans, int64_t* info_dev)
-{
-    if (batch < 0 || n < 0) {
-        set_error("complex getri_batched: negative size batch=%lld n=%lld", (long long)batch, (long long)n);
-        return RFLU_ERR_ARG;
-    }
-    if (trans < 0 || trans > 2) {
-        set_error("complex getri_batched: trans must be 0 (A), 1 (transpose) or 2 (adjoint), got %d", trans);
-        return RFLU_ERR_ARG;
-    }
-    if (batch == 0 || n == 0) return RFLU_OK;
-    if (F == nullptr || Ainv == nullptr || info_dev == nullptr) { set_error("complex getri_batched: null pointer"); return RFLU_ERR_ARG; }
-    if (lda < n || ldi < n || (batch > 1 && (strideF < (n - 1) * lda + n || strideI < (n - 1) * ldi + n))) {
-        set_error("complex getri_batched: lda=%lld strideF=%lld ldi=%lld strideI=%lld too small for n=%lld", (long long)lda,
-                  (long long)strideF, (long long)ldi, (long long)strideI, (long long)n);
-        return RFLU_ERR_ARG;
-    }
-    if (ipiv && batch > 1 && stride_ipiv < n) {
-        set_error("complex getri_batched: stride_ipiv=%lld < n", (long long)stride_ipiv);
-        return RFLU_ERR_ARG;
-    }
-    if (cbatched_fits<R>(n, n)) {
-        RFLU_TRY(launch_cgetri_batched<R>(h, batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi, strideI, trans, info_dev));
-        RFLU_HIP(hipStreamSynchronize(h->stream));
-        h->last_path = RFLU_PATH_HIP_BATCHED;
-        return RFLU_OK;
-    }
-    if (row_major) return refuse_large_row_major<R>("complex getri_batched");
-    const size_t esize = 2 * sizeof(R);
-    const int64_t ldw = cworkspace_ld(n);
-    std::vector<int64_t> infos((size_t)batch, 0);
-    for (int64_t b = 0; b < batch; ++b) {
-        R* Xb = Ainv + 2 * b * strideI;
-        RFLU_HIP(hipMemcpy2DAsync(Xb, (size_t)ldi * esize, F + 2 * b * strideF, (size_t)lda * esize, (size_t)n * esize, (size_t)n,
-                                  hipMemcpyDeviceToDevice, h->stream));
-        RFLU_TRY(cgetri_cm_dev<R>(h, n, Xb, ldi, ipiv ? ipiv + b * stride_ipiv : nullptr, &infos[(size_t)b]));
-        if (infos[(size_t)b] != 0) {   // a singular matrix: its output is NaN, as the one-launch path's division by zero leaves it non-finite
-            RFLU_HIP(hipMemset2DAsync(Xb, (size_t)ldi * esize, 0xff, (size_t)n * esize, (size_t)n, h->stream));
-        } else if (trans) {
-            RFLU_TRY(ensure_buffer(&h->work, &h->work_bytes, (size_t)n * (size_t)ldw * esize));
-            R* W = static_cast<R*>(h->work);
-            RFLU_TRY(launch_ctranspose<R>(h, n, n, Xb, ldi, W, ldw, trans == 2));
-            RFLU_HIP(hipMemcpy2DAsync(Xb, (size_t)ldi * esize, W, (size_t)ldw * esize, (size_t)n * esize, (size_t)n, hipMemcpyDeviceToDevice,
-                                      h->stream));
-        }
-    }
-    RFLU_HIP(hipMemcpyAsync(info_dev, infos.data(), (size_t)batch * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
@@ -1174,7 +1139,7 @@ static int gerfs_dev(Handle* h, int64_t n, int64_t nrhs, const T* A, int64_t lda
         return RFLU_OK;
     }
     int64_t zero1 = 0;
-    RFLU_TRY(launch_logabsdet<T>(h, n, F, ldf + 1, nullptr, nullptr, nullptr, &zero1));
+    RFLU_TRY(launch_logabsdet<RealElem<T>>(h, n, F, ldf + 1, nullptr, nullptr, nullptr, nullptr, &zero1));
     if (zero1 != 0) { *info = zero1; return RFLU_OK; }   // an exactly zero u_ii: before any solve, nothing written
     if (max_iter <= 0) max_iter = 5;
     const double u = sizeof(T) == 8 ? 0x1p-53 : 0x1p-24;
@@ -1259,7 +1224,8 @@ static int gerfs_dev(Handle* h, int64_t n, int64_t nrhs, const T* A, int64_t lda
     template int trsm_public<T>(Handle*, int64_t, int64_t, const T*, int64_t, T*, int64_t);                                           \
     template int getrs_cm_dev<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t);                          \
     template int getrs_trans_cm_dev<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t);                    \
-    template int getri_cm_dev<T>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);                                            \
+    template int getri_cm_dev<RealElem<T>>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);                                  \
+    template int getri_cm_dev<CplxElem<T>>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);                                  \
     template int gecon_dev<T>(Handle*, int, int64_t, const T*, int64_t, int, double, double*);
 RFLU_INSTANTIATE_DRIVER(double)
 RFLU_INSTANTIATE_DRIVER(float)
@@ -1600,25 +1566,26 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
                                    double* logabs_out, double* sign_out)                                              \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return logabsdet_dev<T>(H(handle), n, F, ld, ipiv, logabs_out, sign_out);                                     \
+        return logabsdet_dev<RealElem<T>>(H(handle), n, F, ld, ipiv, logabs_out, sign_out, nullptr);                  \
     }                                                                                                                 \
     int rflu_logabsdet_##SFX(rflu_handle_t handle, int64_t n, const T* F, int64_t ld, const int64_t* ipiv,             \
                              double* logabs_out, double* sign_out)                                                    \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return logabsdet_host<T>(H(handle), n, F, ld, ipiv, logabs_out, sign_out);                                    \
+        return logabsdet_host<RealElem<T>>(H(handle), n, F, ld, ipiv, logabs_out, sign_out, nullptr);                 \
     }                                                                                                                 \
     int rflu_logabsdet_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, const T* F, int64_t lda,   \
                                            int64_t strideF, const int64_t* ipiv, int64_t stride_ipiv,                 \
                                            double* logabs_dev, double* sign_dev)                                      \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return logabsdet_batched<T>(H(handle), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs_dev, sign_dev);   \
+        return logabsdet_batched<RealElem<T>>(H(handle), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs_dev,    \
+                                              sign_dev);                                                          \
     }                                                                                                                 \
     int rflu_getri_##SFX##_dev(rflu_handle_t handle, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info) \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return getri_cm_dev<T>(H(handle), n, F, lda, ipiv, info);                                                     \
+        return getri_cm_dev<RealElem<T>>(H(handle), n, F, lda, ipiv, info);                                           \
     }                                                                                                                 \
     int rflu_getri_rm_##SFX##_dev(rflu_handle_t handle, int64_t n, T* R, int64_t ld, const int64_t* ipiv,             \
                                   int64_t* info)                                                                      \
@@ -1629,15 +1596,15 @@ int rflu_debug_heat(rflu_handle_t handle, double usec)
     int rflu_getri_##SFX(rflu_handle_t handle, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)      \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return getri_host<T>(H(handle), n, F, lda, ipiv, info);                                                       \
+        return getri_host<RealElem<T>>(H(handle), n, F, lda, ipiv, info);                                             \
     }                                                                                                                 \
     int rflu_getri_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, const T* F, int64_t lda,       \
                                        int64_t strideF, int row_major, const int64_t* ipiv, int64_t stride_ipiv,      \
                                        T* Ainv, int64_t ldi, int64_t strideI, int64_t* info_dev)                      \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return getri_batched<T>(H(handle), batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi,        \
-                                strideI, info_dev);                                                                   \
+        return getri_batched<RealElem<T>>(H(handle), batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv,   \
+                                          ldi, strideI, 0, info_dev);                                                 \
     }                                                                                                                 \
     int rflu_lange_##SFX##_dev(rflu_handle_t handle, int norm, int64_t m, int64_t n, const T* A, int64_t lda,          \
                                int row_major, double* out)                                                            \
@@ -1819,40 +1786,40 @@ int rflu_debug_panel_trace_all(rflu_handle_t handle, long long* out, long long m
     int rflu_getri_##SFX##_dev(rflu_handle_t handle, int64_t n, R* F, int64_t lda, const int64_t* ipiv, int64_t* info) \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return cgetri_cm_dev<R>(H(handle), n, F, lda, ipiv, info);                                                    \
+        return getri_cm_dev<CplxElem<R>>(H(handle), n, F, lda, ipiv, info);                                           \
     }                                                                                                                 \
     int rflu_getri_##SFX(rflu_handle_t handle, int64_t n, R* F, int64_t lda, const int64_t* ipiv, int64_t* info)      \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return cgetri_host<R>(H(handle), n, F, lda, ipiv, info);                                                      \
+        return getri_host<CplxElem<R>>(H(handle), n, F, lda, ipiv, info);                                             \
     }                                                                                                                 \
     int rflu_getri_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, const R* F, int64_t lda,       \
                                        int64_t strideF, int row_major, const int64_t* ipiv, int64_t stride_ipiv,      \
                                        R* Ainv, int64_t ldi, int64_t strideI, int trans, int64_t* info_dev)           \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return cgetri_batched<R>(H(handle), batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv, ldi,       \
-                                 strideI, trans, info_dev);                                                           \
+        return getri_batched<CplxElem<R>>(H(handle), batch, n, F, lda, strideF, row_major, ipiv, stride_ipiv, Ainv,   \
+                                          ldi, strideI, trans, info_dev);                                             \
     }                                                                                                                 \
     int rflu_logabsdet_##SFX##_dev(rflu_handle_t handle, int64_t n, const R* F, int64_t ld, const int64_t* ipiv,      \
                                    double* logabs_out, double* sign_re_out, double* sign_im_out)                      \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return clogabsdet_dev<R>(H(handle), n, F, ld, ipiv, logabs_out, sign_re_out, sign_im_out);                    \
+        return logabsdet_dev<CplxElem<R>>(H(handle), n, F, ld, ipiv, logabs_out, sign_re_out, sign_im_out);           \
     }                                                                                                                 \
     int rflu_logabsdet_##SFX(rflu_handle_t handle, int64_t n, const R* F, int64_t ld, const int64_t* ipiv,            \
                              double* logabs_out, double* sign_re_out, double* sign_im_out)                            \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return clogabsdet_host<R>(H(handle), n, F, ld, ipiv, logabs_out, sign_re_out, sign_im_out);                   \
+        return logabsdet_host<CplxElem<R>>(H(handle), n, F, ld, ipiv, logabs_out, sign_re_out, sign_im_out);          \
     }                                                                                                                 \
     int rflu_logabsdet_batched_##SFX##_dev(rflu_handle_t handle, int64_t batch, int64_t n, const R* F, int64_t lda,   \
                                            int64_t strideF, const int64_t* ipiv, int64_t stride_ipiv,                 \
                                            double* logabs_dev, double* sign_dev)                                      \
     {                                                                                                                 \
         CHECK_HANDLE(handle);                                                                                         \
-        return clogabsdet_batched_dev<R>(H(handle), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs_dev,         \
-                                         sign_dev);                                                                   \
+        return logabsdet_batched<CplxElem<R>>(H(handle), batch, n, F, lda, strideF, ipiv, stride_ipiv, logabs_dev,    \
+                                              sign_dev);                                                              \
     }                                                                                                                 \
     int rflu_lange_##SFX##_dev(rflu_handle_t handle, int norm, int64_t m, int64_t n, const R* A, int64_t lda,          \
                                int row_major, double* out)                                                            \

@@ -37,8 +37,35 @@ template <typename T> int trsm_rec(Handle* h, int64_t n, int64_t nrhs, const T* 
 template <typename T> int trsm_public(Handle* h, int64_t n, int64_t nrhs, const T* L, int64_t ldl, T* B, int64_t ldb);
 template <typename T> int getrs_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb);
 template <typename T> int getrs_trans_cm_dev(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb);
-template <typename T> int getri_cm_dev(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info);
+// E: the element trait (rflu_internal.hpp), here and below
+template <typename E> int getri_cm_dev(Handle* h, int64_t n, typename E::real* F, int64_t lda, const int64_t* ipiv, int64_t* info);
 template <typename T> int gecon_dev(Handle* h, int norm, int64_t n, const T* F, int64_t ld, int row_major, double anorm, double* rcond);
+
+// the argument rules of getri and logabsdet, one copy for the device entries (driver.cpp) and the host entries (host_entry.cpp); the
+// latter also leaves the empty product in the outputs.  The sign is one word for real elements, (re, im) for complex ones: sign_im
+// belongs to those alone
+template <typename E>
+inline int getri_check_args(int64_t n, const void* F, int64_t lda, const int64_t* info)
+{
+    if (n < 0 || lda < (n > 1 ? n : 1) || info == nullptr || (n > 0 && F == nullptr)) {
+        set_error("%sgetri: bad arguments n=%lld lda=%lld (or a null pointer)", E::WHO, (long long)n, (long long)lda);
+        return RFLU_ERR_ARG;
+    }
+    return RFLU_OK;
+}
+template <typename E>
+inline int logabsdet_check_args(int64_t n, const void* F, int64_t ld, double* logabs, double* sign_re, double* sign_im)
+{
+    constexpr bool CPLX = E::PARTS == 2;
+    if (n < 0 || ld < (n > 1 ? n : 1) || logabs == nullptr || sign_re == nullptr || (CPLX && sign_im == nullptr) || (n > 0 && F == nullptr)) {
+        set_error("%slogabsdet: bad arguments n=%lld ld=%lld (or a null pointer)", E::WHO, (long long)n, (long long)ld);
+        return RFLU_ERR_ARG;
+    }
+    *logabs = 0.0;
+    *sign_re = 1.0;
+    if (CPLX) *sign_im = 0.0;
+    return RFLU_OK;
+}
 
 // ---- streams.cpp ------------------------------------------------------------------------------------------------------------------
 int get_event(Handle* h, size_t idx, hipEvent_t* ev);   // the handle's reusable events (timing disabled), by number
@@ -61,8 +88,9 @@ template <typename T> int laswp_rm(Handle* h, T* R, int64_t ld, int64_t m, int64
 // ---- host_entry.cpp: caller-owned column-major host arrays, staged through device buffers of the handle ---------------------------
 template <typename T> int getrf_host(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv, int pivot, int64_t blocksize, int64_t* info);
 template <typename T> int getrs_host(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, const int64_t* ipiv, T* B, int64_t ldb, bool trans);
-template <typename T> int getri_host(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info);
-template <typename T> int logabsdet_host(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign);
+// (sign_im: complex elements only)
+template <typename E> int getri_host(Handle* h, int64_t n, typename E::real* F, int64_t lda, const int64_t* ipiv, int64_t* info);
+template <typename E> int logabsdet_host(Handle* h, int64_t n, const typename E::real* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign_re, double* sign_im);
 template <typename T> int gecon_host(Handle* h, int norm, int64_t n, const T* F, int64_t lda, double anorm, double* rcond);
 
 }  // namespace rflu

@@ -51,6 +51,13 @@ static int copy_out(T* host, int64_t ld, const T* dev, int64_t rows, int64_t col
     return RFLU_OK;
 }
 
+// the element as these helpers stage it: a complex array arrives as R* pointing at interleaved (re, im) pairs; HostElem<E> is the staged
+// element of the element trait E (rflu_internal.hpp)
+template <typename R>
+struct HostCx { R re, im; };
+template <typename E> struct HostElem { typedef typename E::real type; };
+template <typename R> struct HostElem<CplxElem<R>> { typedef HostCx<R> type; };
+
 // the two pinned bounce buffers of the way back, `bytes` each.  *available = false, no buffers kept: no pinned memory to be had (no error)
 static int ensure_bounce(Handle* h, size_t bytes, bool* available)
 {
@@ -95,44 +102,40 @@ int getrs_host(Handle* h, int64_t n, int64_t nrhs, const T* F, int64_t lda, cons
     return RFLU_OK;
 }
 
-// ---- logabsdet (only the diagonal and ipiv travel) and inv from host factors ----------------------------------------------------------
-template <typename T>
-int logabsdet_host(Handle* h, int64_t n, const T* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign)
+// ---- logabsdet (only the diagonal and ipiv travel) and inv from host factors, real and complex (E: the element trait) ----------------
+template <typename E>
+int logabsdet_host(Handle* h, int64_t n, const typename E::real* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign_re,
+                   double* sign_im)
 {
-    if (n < 0 || ld < std::max<int64_t>(n, 1) || logabs == nullptr || sign == nullptr || (n > 0 && F == nullptr)) {
-        set_error("logabsdet: bad arguments n=%lld ld=%lld (or a null pointer)", (long long)n, (long long)ld);
-        return RFLU_ERR_ARG;
-    }
-    *logabs = 0.0;
-    *sign = 1.0;
+    typedef typename HostElem<E>::type Z;
+    RFLU_TRY(logabsdet_check_args<E>(n, F, ld, logabs, sign_re, sign_im));   // ... and the empty product in the outputs
     if (n == 0) return RFLU_OK;
-    std::vector<T> diag((size_t)n);
-    for (int64_t i = 0; i < n; ++i) diag[(size_t)i] = F[i * (ld + 1)];
-    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * sizeof(T)));
+    const Z* Fz = reinterpret_cast<const Z*>(F);
+    std::vector<Z> diag((size_t)n);
+    for (int64_t i = 0; i < n; ++i) diag[(size_t)i] = Fz[i * (ld + 1)];
+    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * sizeof(Z)));
     const int64_t* dipiv;
-    RFLU_HIP(hipMemcpyAsync(h->hostB_dev, diag.data(), (size_t)n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    RFLU_HIP(hipMemcpyAsync(h->hostB_dev, diag.data(), (size_t)n * sizeof(Z), hipMemcpyHostToDevice, h->stream));
     RFLU_TRY(stage_ipiv(h, ipiv, n, &dipiv));
     RFLU_HIP(hipStreamSynchronize(h->stream));   // `diag` is pageable and leaves scope
-    return launch_logabsdet<T>(h, n, static_cast<const T*>(h->hostB_dev), 1, dipiv, logabs, sign, nullptr);
+    return launch_logabsdet<E>(h, n, static_cast<const typename E::real*>(h->hostB_dev), 1, dipiv, logabs, sign_re, sign_im, nullptr);
 }
 
-template <typename T>
-int getri_host(Handle* h, int64_t n, T* F, int64_t lda, const int64_t* ipiv, int64_t* info)
+template <typename E>
+int getri_host(Handle* h, int64_t n, typename E::real* F, int64_t lda, const int64_t* ipiv, int64_t* info)
 {
-    if (n < 0 || lda < std::max<int64_t>(n, 1) || info == nullptr || (n > 0 && F == nullptr)) {
-        set_error("getri: bad arguments n=%lld lda=%lld (or a null pointer)", (long long)n, (long long)lda);
-        return RFLU_ERR_ARG;
-    }
+    typedef typename HostElem<E>::type Z;
+    RFLU_TRY(getri_check_args<E>(n, F, lda, info));
     *info = 0;
     if (n == 0) return RFLU_OK;
-    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(T)));
-    T* dF = static_cast<T*>(h->hostA_dev);
+    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(Z)));
+    Z* dF = static_cast<Z*>(h->hostA_dev);
     const int64_t* dipiv;
-    RFLU_TRY(copy_in(dF, F, lda, n, n, h->stream));
+    RFLU_TRY(copy_in(dF, reinterpret_cast<const Z*>(F), lda, n, n, h->stream));
     RFLU_TRY(stage_ipiv(h, ipiv, n, &dipiv));
-    RFLU_TRY(getri_cm_dev<T>(h, n, dF, n, dipiv, info));
+    RFLU_TRY(getri_cm_dev<E>(h, n, reinterpret_cast<typename E::real*>(dF), n, dipiv, info));
     if (*info != 0) return RFLU_OK;   // F stays as it is
-    RFLU_TRY(copy_out(F, lda, dF, n, n, h->stream));
+    RFLU_TRY(copy_out(reinterpret_cast<Z*>(F), lda, dF, n, n, h->stream));
     RFLU_HIP(hipStreamSynchronize(h->stream));
     return RFLU_OK;
 }
@@ -440,9 +443,6 @@ int getrf_host(Handle* h, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv
 // ---- ComplexF64 / ComplexF32 (complex.hip): H2D, the device entry, D2H -- the factors travel only after success, so a failed call
 // leaves the caller's matrix as it was.  R* points at interleaved (re, im) pairs, lda / ldb count complex elements.
 template <typename R>
-struct HostCx { R re, im; };
-
-template <typename R>
 int cgetrf_host(Handle* h, int64_t m, int64_t n, R* A, int64_t lda, int64_t* ipiv, int pivot, int64_t* info)
 {
     typedef HostCx<R> Z;
@@ -502,46 +502,6 @@ int cgetrs_trans_host(Handle* h, int64_t n, int64_t nrhs, const R* F, int64_t ld
     return RFLU_OK;
 }
 
-// inv!(F) and logabsdet from complex host factors: as getri_host / logabsdet_host (the diagonal and ipiv travel alone for the latter)
-template <typename R>
-int cgetri_host(Handle* h, int64_t n, R* F, int64_t lda, const int64_t* ipiv, int64_t* info)
-{
-    typedef HostCx<R> Z;
-    RFLU_TRY(cgetri_check_args(n, F, lda, info));
-    *info = 0;
-    if (n == 0) return RFLU_OK;
-    RFLU_TRY(ensure_buffer(&h->hostA_dev, &h->hostA_bytes, (size_t)n * (size_t)n * sizeof(Z)));
-    Z* dF = static_cast<Z*>(h->hostA_dev);
-    const int64_t* dipiv;
-    RFLU_TRY(copy_in(dF, reinterpret_cast<const Z*>(F), lda, n, n, h->stream));
-    RFLU_TRY(stage_ipiv(h, ipiv, n, &dipiv));
-    RFLU_TRY(cgetri_cm_dev<R>(h, n, reinterpret_cast<R*>(dF), n, dipiv, info));
-    if (*info != 0) return RFLU_OK;   // F stays as it is
-    RFLU_TRY(copy_out(reinterpret_cast<Z*>(F), lda, dF, n, n, h->stream));
-    RFLU_HIP(hipStreamSynchronize(h->stream));
-    return RFLU_OK;
-}
-
-template <typename R>
-int clogabsdet_host(Handle* h, int64_t n, const R* F, int64_t ld, const int64_t* ipiv, double* logabs, double* sign_re, double* sign_im)
-{
-    typedef HostCx<R> Z;
-    RFLU_TRY(clogabsdet_check_args(n, F, ld, logabs, sign_re, sign_im));
-    *logabs = 0.0;
-    *sign_re = 1.0;
-    *sign_im = 0.0;
-    if (n == 0) return RFLU_OK;
-    const Z* Fz = reinterpret_cast<const Z*>(F);
-    std::vector<Z> diag((size_t)n);
-    for (int64_t i = 0; i < n; ++i) diag[(size_t)i] = Fz[i * (ld + 1)];
-    RFLU_TRY(ensure_buffer(&h->hostB_dev, &h->hostB_bytes, (size_t)n * sizeof(Z)));
-    const int64_t* dipiv;
-    RFLU_HIP(hipMemcpyAsync(h->hostB_dev, diag.data(), (size_t)n * sizeof(Z), hipMemcpyHostToDevice, h->stream));
-    RFLU_TRY(stage_ipiv(h, ipiv, n, &dipiv));
-    RFLU_HIP(hipStreamSynchronize(h->stream));   // `diag` is pageable and leaves scope
-    return launch_clogabsdet<R>(h, n, static_cast<const R*>(h->hostB_dev), 1, dipiv, logabs, sign_re, sign_im, nullptr);
-}
-
 // rcond from complex host factors: H2D, then the device entry (which checks norm and anorm and serves the special values)
 template <typename R>
 int cgecon_host(Handle* h, int norm, int64_t n, const R* F, int64_t lda, double anorm, double* rcond)
@@ -562,8 +522,8 @@ int cgecon_host(Handle* h, int norm, int64_t n, const R* F, int64_t lda, double 
 #define RFLU_INSTANTIATE_HOST(T)                                                                                                      \
     template int getrf_host<T>(Handle*, int64_t, int64_t, T*, int64_t, int64_t*, int, int64_t, int64_t*);                             \
     template int getrs_host<T>(Handle*, int64_t, int64_t, const T*, int64_t, const int64_t*, T*, int64_t, bool);                      \
-    template int getri_host<T>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);                                              \
-    template int logabsdet_host<T>(Handle*, int64_t, const T*, int64_t, const int64_t*, double*, double*);                            \
+    template int getri_host<RealElem<T>>(Handle*, int64_t, T*, int64_t, const int64_t*, int64_t*);                                    \
+    template int logabsdet_host<RealElem<T>>(Handle*, int64_t, const T*, int64_t, const int64_t*, double*, double*, double*);         \
     template int gecon_host<T>(Handle*, int, int64_t, const T*, int64_t, double, double*);
 RFLU_INSTANTIATE_HOST(double)
 RFLU_INSTANTIATE_HOST(float)
@@ -571,8 +531,8 @@ RFLU_INSTANTIATE_HOST(float)
     template int cgetrf_host<R>(Handle*, int64_t, int64_t, R*, int64_t, int64_t*, int, int64_t*);                                     \
     template int cgetrs_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t);                           \
     template int cgetrs_trans_host<R>(Handle*, int64_t, int64_t, const R*, int64_t, const int64_t*, R*, int64_t, int);             \
-    template int cgetri_host<R>(Handle*, int64_t, R*, int64_t, const int64_t*, int64_t*);                                             \
-    template int clogabsdet_host<R>(Handle*, int64_t, const R*, int64_t, const int64_t*, double*, double*, double*);               \
+    template int getri_host<CplxElem<R>>(Handle*, int64_t, R*, int64_t, const int64_t*, int64_t*);                                    \
+    template int logabsdet_host<CplxElem<R>>(Handle*, int64_t, const R*, int64_t, const int64_t*, double*, double*, double*);         \
     template int cgecon_host<R>(Handle*, int, int64_t, const R*, int64_t, double, double*);
 RFLU_INSTANTIATE_HOST_COMPLEX(double)
 RFLU_INSTANTIATE_HOST_COMPLEX(float)

@@ -245,7 +245,7 @@ struct Handle {
     bool gemm_attr_set[2] = {false, false};   // dynamic-LDS opt-in of the GEMM kernels done on this handle's device (f64, f32)
     bool eng_attr_set[2] = {false, false};    // same for the persistent update engine (engine.hip)
     bool batched_attr_set[3][4] = {};         // same for the batched kernels (batched_kernels.hpp): [getrf|getrs|getri][f64, f32, cf64, cf32]
-    bool cinv_attr_set[2] = {false, false};   // same for the 64x64 triangular inverses of the complex getri (complex_inverse.hip): [cf64, cf32]
+    bool cinv_attr_set[2] = {false, false};   // same for the 64x64 triangular inverses of the complex getri (inverse.hip): [cf64, cf32]
     size_t gecon_lds_asked[2] = {0, 0};       // dynamic LDS asked for the batched condition estimate so far (batched.hip: gecon_batched_kernel): [f64, f32]
     size_t cgecon_lds_asked[2] = {0, 0};      // the same for the complex estimate (batched_complex.hip: cgecon_batched_kernel): [cf64, cf32]
     void* eng_state = nullptr;                // device: EngState (engine.hpp)
@@ -454,23 +454,9 @@ int launch_getri_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_
 template <typename T>
 int launch_tri_inv_trans(Handle* h, int64_t n, const T* V, int64_t ld, T* Ginv, T* Hinv);
 
-// inverse.hip.  The diagonal entry i is F[i * dstride] (dstride = ld + 1 in both layouts); results on the HOST,
-// the stream is synchronised.  zero1: 1-based index of the first exactly-zero entry, 0 = none.
-constexpr int64_t GETRI_W = 512;   // block-column / block-row width of getri's two sweeps
-int64_t getri_width(int64_t n);    // ... for an n x n matrix (smaller matrices: n rounded up to 64)
-template <typename T>
-int launch_logabsdet(Handle* h, int64_t n, const T* F, int64_t dstride, const int64_t* ipiv, double* logabs, double* sign, int64_t* zero1);
-template <typename T>
-int launch_logabsdet_batched(Handle* h, int64_t batch, int64_t n, const T* F, int64_t dstride, int64_t strideF, const int64_t* ipiv,
-                             int64_t stride_ipiv, double* logabs, double* sign);
-// V: row-major n x n image of F^T, overwritten by A^-T; *info (host): first exactly-zero u_ii, V then untouched.  Complete on return.
-template <typename T>
-int getri_view(Handle* h, int64_t n, T* V, int64_t ld, const int64_t* ipiv, int64_t* info);
-
-// condest.hip (DESIGN.md sections 4.11, 4.12): operator norms and the vector kernels of the condition estimate, one source for the four
-// element types.  An ELEMENT is what a leading dimension counts: RealElem<R> is one R, CplxElem<R> one interleaved (re, im) pair of R, and
-// every array crosses as R* (R = double / float).  Every sum is Float64 in a fixed order (no read-modify-write on shared words): results
-// repeat bit for bit.
+// The element trait of the sources that serve the four element types from one text (condest.hip, mixed.hip, inverse.hip).  An ELEMENT
+// is what a leading dimension counts: RealElem<R> is one R, CplxElem<R> one interleaved (re, im) pair of R, and every array crosses as
+// R* (R = double / float).
 template <typename R>
 struct RealElem {
     typedef R real;
@@ -494,6 +480,26 @@ struct CplxElem {
     // plain Float64 hypot, NOT abs: (Inf, NaN) gives Inf.  What the mixed-precision kernels (mixed.hip) take as the modulus
     static __device__ __forceinline__ double modulus(const R* p) { return hypot((double)p[0], (double)p[1]); }
 };
+
+// inverse.hip (DESIGN.md sections 4.4, 4.8), one source for the four element types.  The diagonal entry i is element i * dstride of F
+// (dstride = ld + 1 in both layouts); results on the HOST, the stream is synchronised.  The sign is *sign_re for real elements (sign_im is
+// not touched), the phase (*sign_re, *sign_im) for complex ones.  zero1: 1-based index of the first exactly-zero entry (complex: both parts zero), 0 = none.
+constexpr int64_t GETRI_W = 512;   // block-column / block-row width of getri's two sweeps
+int64_t getri_width(int64_t n);    // ... for an n x n matrix (smaller matrices: n rounded up to 64)
+template <typename E>
+int launch_logabsdet(Handle* h, int64_t n, const typename E::real* F, int64_t dstride, const int64_t* ipiv, double* logabs, double* sign_re,
+                     double* sign_im, int64_t* zero1);
+// logabs[b], sign[E::PARTS * b ...] (device) for matrix b, strideF elements after the one before.  Enqueued only.
+template <typename E>
+int launch_logabsdet_batched(Handle* h, int64_t batch, int64_t n, const typename E::real* F, int64_t dstride, int64_t strideF,
+                             const int64_t* ipiv, int64_t stride_ipiv, double* logabs, double* sign);
+// V: row-major n x n image of F^T (the plain transpose), overwritten by A^-T; *info (host): first exactly-zero u_ii, V then untouched.
+// Complete on return.
+template <typename E>
+int getri_view(Handle* h, int64_t n, typename E::real* V, int64_t ld, const int64_t* ipiv, int64_t* info);
+
+// condest.hip (DESIGN.md sections 4.11, 4.12): operator norms and the vector kernels of the condition estimate, one source for the four
+// element types.  Every sum is Float64 in a fixed order (no read-modify-write on shared words): results repeat bit for bit.
 // *out (host) = the 1- or Inf-norm of the m x n matrix A; element (i, j) at [i + j*lda] or (row_major) [i*lda + j].  Synchronises.
 template <typename E>
 int launch_lange(Handle* h, int norm, int64_t m, int64_t n, const typename E::real* A, int64_t lda, int row_major, double* out);

@@ -4,8 +4,8 @@ tests/test_gpu_complex_inv.py, scripts/complex_inv_cpu_bars.py).  Pure numpy, no
   * rand_matrix: re and im uniform in [-1/2, 1/2) from seeded generators, in the element type's own precision;
   * rho: LAPACK's xGET03 ratios ||A X - I||_1 / (n eps_T ||A||_1 ||X||_1) and the same with X A, evaluated in complex128;
   * exact_case: CONSTRUCTED factors (nothing is computed by an elimination) whose inverse is known exactly -- see its docstring;
-  * kernel_order_logabsdet: the reduction of csrc/complex_inverse.hip restated on the host, in its own order;
-  * getri_transcription: the two sweeps of csrc/complex_inverse.hip in numpy with the index arithmetic of the drivers."""
+  * kernel_order_logabsdet: the complex reduction of csrc/inverse.hip restated on the host, in its own order;
+  * getri_transcription: the two sweeps of csrc/inverse.hip in numpy with the index arithmetic of the drivers."""
 import functools
 import math
 
@@ -218,8 +218,8 @@ def _cmul(a, b):
 
 
 def kernel_order_logabsdet(diag, ipiv):
-    """(logabs, phase, sum of |log|) over a downloaded diagonal as cld_chunk / cld_combine / cld_finish of csrc/complex_inverse.hip
-    order it: chunks of 1024, thread t of 256 takes entries t, t + 256, t + 512, t + 768 of its chunk in that order, the tree adds
+    """(logabs, phase, sum of |log|) over a downloaded diagonal as ld_chunk / ld_combine / ld_finish of csrc/inverse.hip order
+    it for complex elements: chunks of 1024, thread t of 256 takes entries t, t + 256, t + 512, t + 768 of its chunk in that order, the tree adds
     t and t + s for s = 128 .. 1, the chunks are combined in index order; Float64 throughout; parity and one renormalisation last."""
     d = np.asarray(diag, dtype=np.complex128)
     n = len(d)
@@ -293,9 +293,9 @@ def _trtri_sweep(V, n, W, wide=GETRI_W, recurse=True):
 
 
 def getri_transcription(F, ipiv, W=GETRI_W, recurse=True, reverse=True, conj_h=False):
-    """A^-1 from packed column-major factors F by the steps of cgetri_view.  The keyword arguments are the three mutations of the issue:
-    recurse=False skips the width-64 sweep inside a wide diagonal block, reverse=False applies the interchanges forwards, conj_h=True
-    conjugates H as it is saved."""
+    """A^-1 from packed column-major factors F by the steps of getri_view<E> (csrc/inverse.hip).  The keyword arguments are the three mutations of
+    the issue: recurse=False skips the width-64 sweep inside a wide diagonal block, reverse=False applies the interchanges forwards,
+    conj_h=True conjugates H as it is saved."""
     n = F.shape[0]
     V = np.array(np.asarray(F).T, order="C")               # the transposed view: F's memory read row-major
     nb = (n + NB - 1) // NB

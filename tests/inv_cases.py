@@ -5,8 +5,8 @@ tests/test_gpu_inv_exact.py).  Pure numpy (and the CPU oracle for the factors of
   * rho: LAPACK's xGET03 ratios ||A X - I||_1 / (n eps_T ||A||_1 ||X||_1) and the same with X A, evaluated in Float64;
   * exact_case: CONSTRUCTED real factors (nothing is computed by an elimination) whose inverse is known exactly -- see its docstring;
     complex_inv_cases.partial_sum_bits (with |M| = |re|) bounds the bits of every partial sum of any blocked inverse of them;
-  * getri_transcription (imported from complex_inv_cases: getri_view<T> of csrc/inverse.hip has the steps of cgetri_view, and the
-    transcription does not care about the element type): the two sweeps in numpy with the index arithmetic of the drivers;
+  * getri_transcription (imported from complex_inv_cases: getri_view<E> of csrc/inverse.hip is one host path for real and complex
+    elements, and the transcription does not care about the element type): the two sweeps in numpy with the index arithmetic of the drivers;
   * batched_restatement: getri_batched_kernel of csrc/batched.hip in numpy, in the kernel's own order and in the element's precision;
     compose_interchanges and bsubstitute (column- and row-reading) also serve the restatement of the batched SOLVE in
     tests/batched_solve_cases.py."""

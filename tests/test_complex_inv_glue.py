@@ -2,7 +2,7 @@
 in include/rflu.h with the argument lists the interface fixes, their ctypes bindings, the exports of the built library, the Julia
 ccalls, the build list and the documents, the argument checks the Python mirror makes BEFORE it touches the library, what the wrappers
 do with the adjoint and the transpose (against a stub handle), and a NumPy transcription of the two sweeps of
-csrc/complex_inverse.hip -- same index arithmetic -- against numpy.linalg.inv."""
+csrc/inverse.hip (one source for real and complex elements) -- same index arithmetic -- against numpy.linalg.inv."""
 import ctypes
 import math
 import os
@@ -57,13 +57,18 @@ def test_library_exports_the_symbols_and_the_version():
 
 
 def test_source_is_wired_and_documented():
-    assert "complex_inverse.hip" in build.SOURCES            # the source list is also what sources_digest() hashes
-    assert sorted(build.EXTRA_DEPS["complex_inverse.hip"]) == ["complex.hpp", "complex_dev.hpp"]
-    code = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "complex_inverse.hip")).read())
+    # one source serves the real and the complex elements: inverse.hip, built against the complex headers; its complex twin is gone
+    assert "inverse.hip" in build.SOURCES                    # the source list is also what sources_digest() hashes
+    assert "complex_inverse.hip" not in build.SOURCES and "complex_inverse.hip" not in build.EXTRA_DEPS
+    assert not os.path.exists(os.path.join(CSRC, "complex_inverse.hip"))
+    assert sorted(build.EXTRA_DEPS["inverse.hip"]) == ["complex.hpp", "complex_dev.hpp"]
+    text = open(os.path.join(CSRC, "inverse.hip")).read()
+    code = re.sub(r"//[^\n]*", "", text)
     for needle in ("atomic", "while (", "while(", "hipLaunchCooperativeKernel", "conj"):   # nothing waits, nothing is conjugated
         assert needle not in code, needle
-    assert '#include "rflu_internal.hpp"' in open(os.path.join(CSRC, "inverse.hip")).read()
-    assert "Cx<" not in open(os.path.join(CSRC, "inverse.hip")).read()                     # the real file stays real
+    assert '#include "complex_dev.hpp"' in text and "Cx<" in code
+    for elem in ("RealElem<double>", "RealElem<float>", "CplxElem<double>", "CplxElem<float>"):   # the four element types, one text
+        assert f"RFLU_INVERSE_FOR({elem})" in code, elem
     solve = open(os.path.join(CSRC, "complex_solve.hip")).read()
     assert "static int launch_claswp_rev" not in solve and "launch_claswp_rev" in open(os.path.join(CSRC, "complex.hpp")).read()
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):

@@ -1,5 +1,5 @@
 """-m gpu: inv / det / logabsdet from ComplexF64 / ComplexF32 LU factors (rflu_getri_c* / rflu_logabsdet_c* and the batched logabsdet,
-csrc/complex_inverse.hip) through inv_complex_ / inv_complex / logabsdet_complex / det_complex / logdet_complex /
+csrc/inverse.hip) through inv_complex_ / inv_complex / logabsdet_complex / det_complex / logdet_complex /
 logabsdet_complex_batched / det_complex_batched and the raw C ABI.
 
 Inputs (tests/complex_inv_cases.py): rand_matrix(n, ctype): re and im uniform in [-1/2, 1/2) from numpy.random.default_rng(95000 + n) and

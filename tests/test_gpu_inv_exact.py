@@ -1,5 +1,5 @@
 """-m gpu: the real inv / det / logabsdet (rflu_getri_{f64,f32}[_rm]_dev, rflu_getri_*, rflu_getri_batched_*_dev, rflu_logabsdet_*;
-getri_view<T> of csrc/inverse.hip and getri_batched_kernel of csrc/batched.hip) held to EXACT references.  tests/test_gpu_inv.py holds
+getri_view<E> of csrc/inverse.hip and getri_batched_kernel of csrc/batched.hip) held to EXACT references.  tests/test_gpu_inv.py holds
 the same entries to a residual bar of 1.0 that a correct inverse meets with two orders of room; here
 
   * constructed factors (tests/inv_cases.py: exact_case) whose inverse is certified in integer arithmetic come back by `==`: every

@@ -3,7 +3,7 @@
   * the constructed real factors are what their docstring says, their inverse is certified in integer arithmetic (exact_case does that
     when it builds a case), and every entry and every partial sum of ANY blocked inverse is exactly representable in Float32 -- so
     comparing whole buffers with `==` is a fair demand of the GPU, whatever its blocking and summation order;
-  * the transcription of getri_view<T> (csrc/inverse.hip) and the restatement of getri_batched_kernel (csrc/batched.hip) return that
+  * the transcription of getri_view<E> (csrc/inverse.hip) and the restatement of getri_batched_kernel (csrc/batched.hip) return that
     inverse by `==` in both precisions, and each mutation of them is caught at every size where it can differ -- and is shown NOT to
     differ below, so the size lists are seen to cover the switch;
   * on the random inputs of tests/test_gpu_inv.py the two restatements alone stay at or below half the GPU residual bar: the bar
